@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the mcmc_hip hot path: log-posterior evaluations per second (whole job).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1], SURVEY.md 8d "Config 2"): 30-dim single-mode
 gaussian_mixture (target from info_random_gaussian_mixture(default_rng(0)), committed as
@@ -26,9 +26,19 @@ per-checkpoint all-reduce of pooled sufficient statistics (RCCL).
 Before the W warmup steps the device is spun up with untimed launches of the same step for
 `--spinup-ms` (default 60) milliseconds: an idle MI355X runs the same kernel 18 % slower until
 it has been under load for about 35 ms (tools/ramp_probe.py), which is longer than W = 5
-warmup steps of 1.3 ms.  The timed region is untouched: exactly K full steps.
+warmup steps of 1.3 ms.  The timed sampler makes a fixed number of those launches
+(`--spinup-launches`, default 60, plus its first); the rest, as long as the clock needs, runs on a
+twin sampler of the same input, so that the timed sampler computes the same thing from run to run.  The timed region is untouched: exactly K full steps.
 
-Output (rank 0, stdout), every line a JSON object shorter than 4 KB:
+A plain run does only what the headline needs: set-up, spin-up, W warmup and K timed steps, and
+ONE JSON line (rank 0, stdout) -- metric, value, unit, ms_per_step (wall time of one timed
+step), higher_is_better, dtype, config, and the roofline block of the same run's kernel times.
+`--dump-outputs DIR` then writes what the timed sampler holds after its last step (`dump_outputs`).
+
+`--full` adds everything else, as it ran before it was an option: the >= 1 s cross-check region,
+the certificate of what the timed region produced (exit code 3 when it fails), the CPU baseline,
+the multi-rank diagnostics of the collective and the variants.  Output of a `--full` run (rank 0,
+stdout), every line a JSON object shorter than 4 KB:
   1. the headline -- metric, value, config, roofline, cpu_baseline -- as soon as its timed region
      and the CPU baseline are done (`"stage": "headline"`), BEFORE any variant runs;
   2. one `{"bench_variant": {...}}` line per extra measurement (each under its own try/except);
@@ -84,14 +94,25 @@ def parse():
                          "own semantics, mcmc.py:691-707) and drained to the host every launch")
     ap.add_argument("--evaluation", choices=("auto", "full", "incremental"), default="auto",
                     help="auto (the sampler's default): incremental evaluation where it applies")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the cross-check region, the certificate of the "
+                         "timed region, the CPU baseline, the multi-rank diagnostics and the "
+                         "variants (each of them can still be turned off on its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed sampler holds after its last "
+                         "step as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--no-variants", action="store_true",
-                    help="skip the extra, separately labelled measurements (evaluation: full, "
-                         "emit: chains, d = 100, the config-5 shape, planck_pliklite)")
+                    help="(--full) skip the extra, separately labelled measurements (evaluation: "
+                         "full, emit: chains, d = 100, the config-5 shape, planck_pliklite)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--spinup-ms", type=float, default=60.0,
                     help="untimed launches before the W warmup steps until the device has been "
                          "under load this long (a cold MI355X runs the same kernel 18 %% slower "
                          "for its first ~35 ms: tools/ramp_probe.py); 0 = none")
+    ap.add_argument("--spinup-launches", type=int, default=60,
+                    help="launches of the timed sampler itself during the spin-up, a fixed count "
+                         "(the rest of the spin-up runs on a twin): the timed region starts as far "
+                         "into the run on every box, and what it computes is the same")
     ap.add_argument("--checkpoint-on", dest="device_checkpoint", choices=("device", "reduce", "host"),
                     default=None,
                     help="device: window sums, the all-reduce (in place on the engine's stream), "
@@ -110,8 +131,8 @@ def parse():
                     const="device", help="= --checkpoint-on device")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cross-check-seconds", type=float, default=1.0,
-                    help="after the K timed steps, time the same loop again for at least this long "
-                         "and report it as `cross_check` (0 = skip)")
+                    help="(--full) after the K timed steps, time the same loop again for at least "
+                         "this long and report it as `cross_check` (0 = skip)")
     ap.add_argument("--workload", choices=("gaussian_mixture", "pliklite"), default="gaussian_mixture",
                     help="pliklite: ONLY the planck_pliklite variant (613 bins, d = 27), as its "
                          "own line -- the command the profiles of pl_chi2_kernel are taken with")
@@ -391,9 +412,74 @@ def measured_traffic(d, walkers, spl, kernel):
     return None, None
 
 
-def run_timed(a, d, mean, cov, emit, steps, warmup, evaluation=None, info=None, cross_check_s=0.0):
+def spin_up(a, info, size):
+    """Untimed launches of a TWIN of the timed sampler (same input, an engine of its own) until
+    the device has been under load for `--spinup-ms`: the clocks of an idle MI355X need ~35 ms
+    under load to reach their steady state.  How many launches that takes depends on the box;
+    the timed sampler's history, and so what it computes, does not.  Returns the twin, idle: the
+    caller closes it after its timed region (freeing it here would idle the device before it)."""
+    from cobaya_amd import dist
+    from cobaya_amd.model import ProblemSpec
+    from cobaya_amd.sampler import MCMCHip
+    # (max_rows 0: the twin's drained rows are not retained on the host)
+    twin = MCMCHip(dict(info["sampler"]["mcmc_hip"], max_rows=0), ProblemSpec.from_info(info))
+    try:
+        eng, one_step = twin.engine, twin.advance
+        twin._next_ckpt = twin._checkpoint_steps()
+        one_step()            # (the first launch also allocates the direction buffers)
+        eng.sync()
+        t_spin = time.perf_counter()
+        one_step()
+        eng.sync()
+        t_one = max(time.perf_counter() - t_spin, 1e-4)
+        # (the same number of launches on every rank: checkpoints hold a collective)
+        n_spin = np.array([min(500.0, math.ceil(1e-3 * a.spinup_ms / t_one))])
+        n_spin = int(round(float(dist.all_reduce_sum(n_spin)[0]) / size))
+        for _ in range(n_spin):
+            one_step()
+        if twin._ckpt_pending:
+            twin._finish_checkpoint()
+            twin._after_checkpoint()
+        eng.sync()
+    except BaseException:
+        twin.close()
+        raise
+    return twin
+
+
+DUMP_LIMIT = 64 << 20   # bytes of --dump-outputs in all (all ranks)
+
+
+def dump_outputs(out_dir, eng, rank, size):
+    """`--dump-outputs`: what a caller of the timed path holds after its last step -- the state of
+    every walker (point, log-posterior and its prior and likelihood parts, weight) and the
+    proposal covariance the learn checkpoints left -- as float64 DIR/<name>.npy (`_rank<r>` for
+    N > 1).  Beyond the size limit the walkers are a fixed, seeded sample, in order; their indices
+    go to walker_index.npy."""
+    s = eng.get_state()
+    arrays = {k: np.asarray(s[k], dtype=np.float64) for k in ("x", "logpost", "logprior", "loglike", "weight")}
+    cov = eng.get_proposal_cov()
+    W = len(arrays["x"])
+    row_bytes = sum(v[0].nbytes for v in arrays.values())
+    budget = DUMP_LIMIT // size - cov.nbytes - 4096   # (and the .npy headers)
+    if W * row_bytes > budget:
+        keep = budget // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(W, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["walker_index"] = idx.astype(np.float64)
+    arrays["proposal_cov"] = cov
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if size > 1 else ""
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{sfx}.npy"), v)
+
+
+def run_timed(a, d, mean, cov, emit, steps, warmup, evaluation=None, info=None, cross_check_s=0.0,
+              check=True, dump_dir=None, spinup_launches=0):
     """W untimed + K timed bench steps of one sampler; returns the raw measurements.  `info`:
-    an explicit input (variants); default: the d-dim gaussian_mixture workload."""
+    an explicit input (variants); default: the d-dim gaussian_mixture workload.  `check`: certify
+    what the timed region produced (`certify`); `dump_dir`: `dump_outputs` there;
+    `spinup_launches`: launches of this sampler in the spin-up besides its first."""
     from cobaya_amd import dist
     from cobaya_amd.model import ProblemSpec
     from cobaya_amd.sampler import MCMCHip
@@ -433,19 +519,12 @@ def run_timed(a, d, mean, cov, emit, steps, warmup, evaluation=None, info=None, 
     # device spin-up (untimed, reported as config.device_spinup_ms): the clocks of an idle
     # MI355X need ~35 ms under load to reach their steady state -- with W = 5 and K = 20 the
     # whole measurement would otherwise sit on that ramp
-    # (the same number of launches on every rank: checkpoints hold a collective)
+    twin = None
     if a.spinup_ms > 0:
-        one_step()            # (the first launch also allocates the direction buffers)
-        eng.sync()
-        t_spin = time.perf_counter()
-        one_step()
-        eng.sync()
-        t_one = max(time.perf_counter() - t_spin, 1e-4)
-        n_spin = np.array([min(500.0, math.ceil(1e-3 * a.spinup_ms / t_one))])
-        n_spin = int(round(float(dist.all_reduce_sum(n_spin)[0]) / size))
-        for _ in range(n_spin):
+        for _ in range(1 + spinup_launches):   # (the first also allocates the direction buffers)
             one_step()
         eng.sync()
+        twin = spin_up(a, info, size)
     for _ in range(warmup):
         one_step()
     eng.sync()
@@ -465,12 +544,16 @@ def run_timed(a, d, mean, cov, emit, steps, warmup, evaluation=None, info=None, 
     eng.sync()
     dist.barrier()
     dt = time.perf_counter() - t0
+    if twin is not None:
+        twin.close()
     if size > 1:   # MAX over ranks
         dt = float(dist.all_reduce_max(np.array([dt]))[0])
     # what the region produced (outside the clock): accepted steps of all ranks, and rank 0's
     # ensemble as it stands at the end of the K timed steps
     accepted = float(dist.all_reduce_sum(np.array([float(eng.counters()["accepted"] - acc0)]))[0])
-    x_end = eng.get_state()["x"]
+    x_end = eng.get_state()["x"] if check else None
+    if dump_dir:
+        dump_outputs(dump_dir, eng, dist.rank(), size)
     kt = eng.kernel_times()
     if sampler.spec.like_kind == "planck_pliklite":
         kt["binned"] = eng.binned_kernel_times()
@@ -508,9 +591,9 @@ def run_timed(a, d, mean, cov, emit, steps, warmup, evaluation=None, info=None, 
            "rows": rows_kept[0], "evals": float(a.walkers) * size * spl * steps,
            "rows_in_store": int(sampler._n_rows), "drain_slots": int(getattr(eng, "drain_slots", 0)),
            "rows_copied_on_host": int(sum(len(r) for r in sampler._rows if not sampler._is_slot_view(r))),
-           "cross_check": cross}
+           "cross_check": cross, "accepted": accepted}
     res["certificate"] = certify(info, x_end, accepted, res["evals"],
-                                 approx=approx)
+                                 approx=approx) if check else None
     sampler.close()
     return res
 
@@ -637,9 +720,11 @@ def main_pliklite(a, rank, size):
     """`--workload pliklite`: the planck_pliklite variant alone, as its own JSON line."""
     spl = a.steps_per_launch or 24
     info, tgt = make_pliklite_info(26, a.walkers, a.group_size, spl)
-    m = run_timed(a, 27, None, None, "snapshots", a.steps, a.warmup, info=info)
+    m = run_timed(a, 27, None, None, "snapshots", a.steps, a.warmup, info=info, check=a.full,
+                  dump_dir=a.dump_outputs, spinup_launches=a.spinup_launches)
     out = None
     if rank == 0:
+        cert = m["certificate"]
         out = {
             "metric": "log-posterior evals/sec (whole node), 27-dim planck_pliklite (613 bins)",
             "value": m["evals"] / m["dt"], "unit": "evals/s", "n_gpus": size, "steps": a.steps,
@@ -652,14 +737,14 @@ def main_pliklite(a, rank, size):
                        "d": 27, "walkers_per_gpu": a.walkers, "group_size": m["group_size"],
                        "metropolis_steps_per_launch": m["spl"], "evaluation": m["evaluation"],
                        "learn_checkpoints_in_timed_region": m["n_ckpt"]},
-            "acceptance_rate": m["certificate"]["acceptance_rate"],
-            "accepted": m["certificate"]["accepted"],
-            "posterior_check": m["certificate"].get("posterior_check"),
-            "certified": bool(m["certificate"]["ok"]),
+            "acceptance_rate": m["accepted"] / max(m["evals"], 1.0), "accepted": int(m["accepted"]),
+            "posterior_check": cert.get("posterior_check") if cert else None,
+            "certified": bool(cert["ok"]) if cert else None,
             "roofline": pliklite_roofline(m, tgt.n_bins, a.walkers, a.steps),
-            "cpu_baseline": None if a.no_cpu_baseline else cpu_baseline_pliklite(26, a.cpu_seconds)}
+            "cpu_baseline": cpu_baseline_pliklite(26, a.cpu_seconds)
+            if a.full and not a.no_cpu_baseline else None}
         line = dict(out, roofline=compact_roofline(out["roofline"]),
-                    posterior_check=compact_certificate(m["certificate"]))
+                    posterior_check=compact_certificate(cert))
         line["roofline"]["other_kernels_ms_per_metropolis_step"] = \
             out["roofline"]["other_kernels_ms_per_metropolis_step"]
         line["roofline"]["metropolis_step_ms"] = out["roofline"]["metropolis_step_ms"]
@@ -1031,9 +1116,11 @@ def main():
         return main_pliklite(a, rank, size)
     d = a.dim
     mean, cov = target(d)
-    m = run_timed(a, d, mean, cov, a.emit, a.steps, a.warmup, cross_check_s=a.cross_check_seconds)
+    m = run_timed(a, d, mean, cov, a.emit, a.steps, a.warmup,
+                  cross_check_s=a.cross_check_seconds if a.full else 0.0, check=a.full,
+                  dump_dir=a.dump_outputs, spinup_launches=a.spinup_launches)
     collective = dist.describe()
-    if size > 1:
+    if size > 1 and a.full:
         # diagnostics of a scaling run: the step-kernel time of every rank and the cost of the
         # checkpoint's all-reduce (2 d^2 + d + 5 doubles), measured after the timed region
         per = np.zeros(size)
@@ -1085,26 +1172,26 @@ def main():
                 "checkpoint_on": m["checkpoint_on"],
                 "parallelism": f"walkers sharded over {size} GPU(s); one all-reduce per "
                                "checkpoint"},
-            # what the timed region produced (certify()): a run that stopped accepting or left
-            # the target fails (exit code 3) instead of posting a rate
-            "acceptance_rate": cert["acceptance_rate"], "accepted": cert["accepted"],
-            "posterior_check": cert.get("posterior_check"),
-            "certified": bool(cert["ok"]),
+            # what the timed region produced (certify(), --full): a run that stopped accepting or
+            # left the target fails (exit code 3) instead of posting a rate
+            "acceptance_rate": m["accepted"] / max(m["evals"], 1.0), "accepted": int(m["accepted"]),
+            "posterior_check": cert.get("posterior_check") if cert else None,
+            "certified": bool(cert["ok"]) if cert else None,
             "cross_check": m["cross_check"],
             "collective": collective,
             "roofline": gaussian_roofline(m, d, a.walkers, a.steps),
             "cpu_baseline": None,
         }
-        if size == 1 and not a.no_cpu_baseline:
+        if size == 1 and a.full and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(d, mean, cov, m["group_size"], a.cpu_seconds,
                                                    m["evaluation"] == "incremental")
             except Exception as e:   # noqa: BLE001  (the headline is printed whatever happens here)
                 print(f"[bench] cpu_baseline failed: {type(e).__name__}: {e}", file=sys.stderr)
-        todo = variant_list(a, d, mean, cov, m) if size == 1 and not a.no_variants else []
+        todo = variant_list(a, d, mean, cov, m) if size == 1 and a.full and not a.no_variants else []
         vfile = os.path.relpath(variants_path(), ROOT) if todo else None
-        # THE line, before any variant runs: nothing below can lose it
-        print(headline_line(out, [], vfile, "headline"), flush=True)
+        if a.full:   # THE line, before any variant runs: nothing below can lose it
+            print(headline_line(out, [], vfile, "headline"), flush=True)
         for tag, run in todo:
             try:
                 v = run()
@@ -1121,7 +1208,7 @@ def main():
             except OSError as e:
                 print(f"[bench] could not write {vfile}: {e}", file=sys.stderr)
                 vfile = None
-        # ... and again as the LAST line of stdout
+        # ... and again as the LAST line of stdout (a plain run: the only line)
         print(headline_line(out, variants, vfile, "final"), flush=True)
     dist.barrier()
     dist.shutdown()     # (the communicator is destroyed while every rank is still there)
@@ -1130,7 +1217,7 @@ def main():
             c = v.get("certificate") or {}
             if "error" in v or not c.get("ok", False):
                 print(f"[bench] variant NOT CERTIFIED: {v.get('tag')}: {v.get('error') or c}", file=sys.stderr)
-        if not out["certified"]:
+        if out["certified"] is False:
             c = m["certificate"]
             print(f"[bench] NOT CERTIFIED: headline: acceptance {c['acceptance_rate']:.3f}, "
                   f"posterior_check {c.get('posterior_check')}", file=sys.stderr)

@@ -119,7 +119,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = bench("--gpus", "2", "--steps", "6", "--warmup", "6", "--walkers", "16384",
-                "--steps-per-launch", "900", env=env)
+                "--steps-per-launch", "900", "--full", env=env)
     assert res["n_gpus"] == 2 and res["scaling"] == "weak"
     c = res["collective"]
     assert c["world_size"] == 2 and c["nranks_seen"] == 2

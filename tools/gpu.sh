@@ -24,7 +24,7 @@
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-BENCH_QUICK="--no-cpu-baseline --no-variants --steps 20 --warmup 4 --cross-check-seconds 0.25"
+BENCH_QUICK="--full --no-cpu-baseline --no-variants --steps 20 --warmup 4 --cross-check-seconds 0.25"
 SQ="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INSTS_VALU SQ_INSTS_SMEM"
 LDS="SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_WAVES GRBM_GUI_ACTIVE"
 
@@ -69,6 +69,7 @@ tests)
 smoke)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tee gpurun_out/smoke.log ;;
 bench)
+  set -- --full "$@"   # (the summary below reads the certificate and the variants)
   timeout 900 python bench.py "$@" > gpurun_out/bench_${TAG:-line}.json 2> gpurun_out/bench_${TAG:-line}.err
   echo "bench rc=$?"; tail -c 600 gpurun_out/bench_${TAG:-line}.err
   python - gpurun_out/bench_${TAG:-line}.json <<'PY'
@@ -109,8 +110,7 @@ evidence)
   python tools/collect_evidence.py ${RND}_pl final_pl > /dev/null
   cp $EVIDENCE_DST/traffic.json profiles/traffic.json   # (on the box: the lines below quote it)
   if [ "$MODE" != quick ]; then
-    timeout 900 python bench.py > gpurun_out/final_bench.json 2> gpurun_out/final_bench.err
-    cp gpurun_out/final_bench.json $EVIDENCE_DST/${RND}_bench_full_line.json
+    timeout 900 python bench.py --full > $EVIDENCE_DST/${RND}_bench_full_line.json 2> $EVIDENCE_DST/final_bench.err
   fi
   requote() { TAG=$1; shift; timeout 600 python bench.py $BENCH_QUICK $* > $EVIDENCE_DST/${TAG}_bench.json 2>/dev/null; }
   requote $RND
