@@ -276,9 +276,11 @@ extern "C" hipError_t mcmc_hip_launch_inc_emit_17(const mcmc::IncStepArgs*, hipS
 extern "C" hipError_t mcmc_hip_launch_inc_emit_25(const mcmc::IncStepArgs*, hipStream_t) __attribute__((weak));
 // incremental_any.hip: the general incremental kernel (any number of modes / periodic parameters)
 extern "C" hipError_t mcmc_hip_launch_inc_any(const mcmc::IncStepArgs*, hipStream_t) __attribute__((weak));
-// incremental_duo.hip (round 6): the incremental step of a two-mode mixture with TWO lanes per walker
+// incremental_duo.hip (round 6): the incremental step of a mixture with TWO lanes per walker (K = 2 up to
+// d = 48, K = 3 up to d = 32, K = 4 up to d = 24: kernels.h duo_serves); one mode (MODE 0) up to d = 32
 extern "C" hipError_t mcmc_hip_launch_inc_duo_1(const mcmc::IncStepArgs*, hipStream_t) __attribute__((weak));
 extern "C" hipError_t mcmc_hip_launch_inc_duo_9(const mcmc::IncStepArgs*, hipStream_t) __attribute__((weak));
+extern "C" hipError_t mcmc_hip_launch_inc_duo1(const mcmc::IncStepArgs*, hipStream_t) __attribute__((weak));
 extern "C" hipError_t mcmc_hip_launch_whiten_directions_planes(const mcmc::IncDirArgs*, int,
                                                                hipStream_t) __attribute__((weak));
 extern "C" int mcmc_hip_inc_any_fits(int d, int n_modes, int n_periodic, int n_walkers,
@@ -1794,6 +1796,13 @@ bool inc_carries_prior(const mcmc_hip_ctx* h)
 // 2.55 / 2.11), 65 536: 2.91 / 1.85, 98 304: 3.94 / 3.35, 131 072: 5.14 / 3.68 -- two lanes win once the
 // four-lane kernel needs a second round of waves (49 152 walkers are its three waves per SIMD)
 constexpr int kDuoMinWalkers = 49152;
+// ... and for one mode (step_inc_duo_kernel, MODE 0, d <= 32) from this size on.  Measured (same box, d = 30,
+// step kernel ms per 1200 steps, four lanes / two; profiles/r07_one_mode_two_lanes.txt): 32 768 walkers
+// 0.751 / 0.762, 49 152: 0.926 / 0.935, 65 536: 1.096 / 0.990, 98 304: 1.863 / 1.821, 131 072: 2.156 / 1.952
+#ifndef MCMC_DUO1_MIN_WALKERS
+#define MCMC_DUO1_MIN_WALKERS 65536
+#endif
+constexpr int kDuo1MinWalkers = MCMC_DUO1_MIN_WALKERS;
 struct IncPlan {   // what the cutting of launches depends on besides the step counter
     int d, dq, K, nd, chunk_steps, Lc, Lf, ld, max_cyc, max_cyc_f, max_steps_vu;
     size_t colb, dd, ddf;
@@ -1981,17 +1990,25 @@ int step_incremental(mcmc_hip_ctx* h, int n_steps)
                           : dq <= 24 ? mcmc_hip_launch_inc_emit_17 : mcmc_hip_launch_inc_emit_25)
                        : (dq <= 8 ? mcmc_hip_launch_inc_step_1 : dq <= 16 ? mcmc_hip_launch_inc_step_9
                           : dq <= 24 ? mcmc_hip_launch_inc_step_17 : mcmc_hip_launch_inc_step_25);
-    // Two lanes per walker (incremental_duo.hip, round 6): two and three modes at d <= 32, four at
-    // d <= 24 (kernels.h: duo_serves) with carried mode log-densities, no block of one parameter -- where the ensemble gives every SIMD its two waves
-    // of 32 walkers (65 536 walkers per device); smaller ensembles keep the four-lane kernel, whose
-    // twice as many waves cover their latencies
+    // Two lanes per walker (incremental_duo.hip): mixtures with carried mode log-densities, two modes
+    // up to d = 48, three up to d = 32, four up to d = 24 (kernels.h: duo_serves), from kDuoMinWalkers
+    // = 49 152 walkers on; one mode (round 7: step_inc_duo_kernel) with one box [0, hi] for every
+    // dimension up to d = 32, from kDuo1MinWalkers on.  Metropolis steps without periodic parameters,
+    // emitted rows or a block of one parameter, whole workgroups of 128 walkers inside a basis group.
+    // Smaller ensembles keep the four-lane kernels, whose twice as many waves cover their latencies.
     {
-        bool duo = h->duo != 0 && !P.any && !emit && !P.drag && n_periodic == 0 && mcmc::duo_serves(K, dq) &&
-                   P.carry_modes && h->W % 128 == 0 && h->bgs % 128 == 0 &&
-                   (h->duo == 1 || h->W >= kDuoMinWalkers);
+        bool duo = h->duo != 0 && !P.any && !emit && !P.drag && n_periodic == 0 && h->W % 128 == 0 &&
+                   h->bgs % 128 == 0;
         for (size_t b = 0; h->blocked && b < h->blk_size.size() && duo; ++b) duo = h->blk_size[b] != 1;
-        auto duo_launch = dq <= 8 ? mcmc_hip_launch_inc_duo_1 : mcmc_hip_launch_inc_duo_9;
-        if (duo && duo_launch) launch = duo_launch;
+        bool box0 = (h->norm_mask4[0] | h->norm_mask4[1] | h->norm_mask4[2] | h->norm_mask4[3]) == 0u &&
+                    h->lo[0] == 0.0;   // (MODE 0 of step_inc_kernel: the same [0, hi] for every dimension)
+        for (int i = 1; i < d && box0; ++i) box0 = h->lo[i] == h->lo[0] && h->hi[i] == h->hi[0];
+        const bool duo_mix = duo && P.carry_modes && mcmc::duo_serves(K, dq) && (h->duo == 1 || h->W >= kDuoMinWalkers);
+        const bool duo_one = duo && K == 1 && P.carry && P.fold && box0 && dq <= mcmc::kDuo1MaxDq &&
+                             (h->duo == 1 || h->W >= kDuo1MinWalkers);
+        auto duo_launch = duo_one ? mcmc_hip_launch_inc_duo1
+                          : dq <= 8 ? mcmc_hip_launch_inc_duo_1 : mcmc_hip_launch_inc_duo_9;
+        if ((duo_mix || duo_one) && duo_launch) launch = duo_launch;
     }
     if (!launch || !mcmc_hip_launch_whiten_directions)
         return fail(h, MCMC_HIP_ERR_DEVICE, "the incremental kernels for d=%d are not linked in", d);

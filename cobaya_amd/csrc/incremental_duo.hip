@@ -26,9 +26,17 @@
 // d = 24: K = 2 1.978 -> 1.250, K = 3 2.605 -> 1.527, K = 4 2.882 -> 2.222; d = 16: K = 3 1.359 -> 1.054,
 // K = 4 1.563 -> 1.019; two modes above d = 32 (x in LDS): d = 36 3.66 -> 3.04, d = 40 4.38 -> 3.47, d = 48 5.66 -> 4.99.
 // Four modes at d = 30 do not fit (y_1 .. y_4 alone are 128 registers: with x in
-// registers as well the step loop spilled, 4.07 -> 19.9 ms) and stay on step_inc_mix_kernel.  One mode
-// gains nothing (0.893 -> 0.889 ms at d = 30: its per-lane work is small, the kernel is bound by its
-// FP64 fmas in either layout) and was not kept.
+// registers as well the step loop spilled, 4.07 -> 19.9 ms) and stay on step_inc_mix_kernel.
+//
+// ONE mode (round 7, step_inc_duo_kernel below, reported as step_inc_kernel<dq, 0, .., two lanes>):
+// the four-lane kernel is issue-bound, and about a third of its vector instructions are per walker and
+// run in all four lanes; on two lanes they run twice, and with the chains {h, h + 2} in lane h a
+// d = 30 walker has 15 dimensions per lane and no padded row.  The step's (v, u) pairs stay in registers
+// from the trial to the commit (256 registers at two waves per SIMD).  Measured at d = 30, 65 536
+// walkers, same box (profiles/r07_one_mode_two_lanes.txt): step kernel 1.11 -> 0.99 ms per 1 200
+// steps (bench.py: 0.902 -> 0.856), 20 % fewer vector instructions; chains {2 h, 2 h + 1} (16 rows,
+// two padded) 4 % slower than {h, h + 2}; the next step's pairs requested a step ahead 22 % slower.
+// Below 65 536 walkers the four-lane kernel is as fast or faster (capi.hip: kDuo1MinWalkers).
 //
 // Served: Metropolis steps, no periodic parameter, no emitted rows, no block of one parameter, whole
 // workgroups of 128 walkers inside one basis group -- for ensembles that fill the chip with it
@@ -510,6 +518,294 @@ hipError_t dispatch_duo_mix(const IncStepArgs& a, hipStream_t st)
     }
 }
 
+#if MCMC_DUO_DQ_LO == 1
+// ---------------------------------------------------------------- one mode
+// step_inc_kernel's MODE 0 step (one Gaussian mode, the box [0, hi] for every dimension; specification:
+// oracle/mcmc_oracle.c step_core_inc with `carry`) with TWO lanes per walker.  The columns are
+// step_inc_kernel's: (v_i, u_i) pairs, pair i at 16 i bytes.  Lane half h holds the NE dimensions
+// i = duo1_dim(e, h) of two of the four interleaved chains -- element e belongs to the lane's chain e & 1:
+//   SPLIT = false: chains {2 h, 2 h + 1}, i = 4 (e / 2) + 2 h + (e & 1), NE = 2 dq (d = 30: two padded rows in lane 1)
+//   SPLIT = true:  chains {h, h + 2},     i = 2 e + h,                   NE = ceil(d / 2) (d = 30: no padded row)
+// The sums over the dimensions stay (p0 + p1) + (p2 + p3): with SPLIT = false a lane adds its own two chains
+// and one pair swap adds the neighbour's; with SPLIT = true two swaps give p0 + p1 and p2 + p3 in both lanes.
+#ifndef MCMC_DUO1_SPLIT
+#define MCMC_DUO1_SPLIT 1   // (experiment hook: the chain assignment; measured, profiles/r07_one_mode_two_lanes.txt)
+#endif
+template <bool SPLIT>
+__host__ __device__ constexpr int duo1_off(int e) { return SPLIT ? 2 * e : 4 * (e >> 1) + (e & 1); }
+template <bool SPLIT>
+__device__ __forceinline__ int duo1_dim(int e, int h) { return duo1_off<SPLIT>(e) + (SPLIT ? h : 2 * h); }
+// (p0 + p1) + (p2 + p3) in both lanes of the walker from this lane's chains (q0, q1)
+template <bool SPLIT>
+__device__ __forceinline__ double duo1_sum(double q0, double q1)
+{
+    if constexpr (SPLIT) {   // q0 = p_h, q1 = p_(h + 2)
+        const double lo = q0 + pair_swap(q0), hi = q1 + pair_swap(q1);
+        return lo + hi;
+    } else {
+        return duo_sum(q0, q1);
+    }
+}
+// columns of one LDS chunk: two workgroups per CU have 80 KB each -- what the staged variates (16.5 KB)
+// and the logarithm table (2 KB) leave for two buffers of 64 dq bytes per column
+__host__ __device__ constexpr int duo1_chunk(int dq)
+{
+    int c = ((80 * 1024 - 16896 - 2048) / (2 * 64 * dq)) & ~3;
+    return c > 64 ? 64 : c;
+}
+
+template <int DQ, int NE, bool SPLIT, bool UNIT_T>
+__global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double2 smem2[];
+    constexpr int COLB = 4 * DQ, dpad = 4 * DQ;  // (v, u) pairs per column
+    constexpr int C = duo1_chunk(DQ);
+    constexpr int CHUNK = C * COLB;              // pairs per chunk
+    static_assert(SPLIT ? (NE == 2 * DQ || NE == 2 * DQ - 1) : NE == 2 * DQ, "dimensions per lane");
+    const StepArgs& s = a.s;
+    const int tid = threadIdx.x, h = tid & 1, wave = tid >> 6, lane = tid & 63;
+    const int W = s.W, d = a.d;
+    const int w = blockIdx.x * 128 + (tid >> 1);
+    const int g = __builtin_amdgcn_readfirstlane(w / s.group_size);
+    const int ncols = s.n_steps;
+    // (the launch's columns inside its direction set: see IncStepArgs::vu_cols)
+    const int set_cols = a.vu_cols > 0 ? a.vu_cols : ncols;
+    const double2* __restrict__ gVU = (const double2*)a.VU + ((size_t)g * set_cols + (size_t)a.col0) * COLB;
+    auto stage = [&](int k) {   // chunk k -> buffer k & 1, by DMA (as in step_inc_kernel)
+        const int first = k * C;
+        if (first >= ncols) return;
+        const int cols = ncols - first < C ? ncols - first : C;
+        const int bytes = cols * COLB * 16;
+        const char* src = (const char*)(gVU + (size_t)first * COLB);
+        char* dst = (char*)(smem2 + (k & 1) * CHUNK);
+        for (int kb = wave; kb * 1024 < bytes; kb += 4) {
+            if (kb * 1024 + lane * 16 < bytes)
+                __builtin_amdgcn_global_load_lds(
+                    (const __attribute__((address_space(1))) void*)(src + kb * 1024 + lane * 16),
+                    (__attribute__((address_space(3))) void*)(dst + kb * 1024), 16, 0, 0);
+        }
+    };
+    const bool refresh_y = (a.anchor & 2) != 0;   // wave-uniform
+    if (!refresh_y) stage(0);
+    const double blo = a.box_lo, bhi = a.box_hi;
+    const unsigned bhi_word = (unsigned)__double2hiint(bhi);   // (blo == +0, 0 < bhi < inf)
+    double x[NE], y[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int i = duo1_dim<SPLIT>(e, h);
+        const bool in = i < d;
+        // (a padded dimension rests at the middle of the box, inside for every step)
+        x[e] = in ? s.x[(size_t)i * W + w] : 0.5 * (blo + bhi);
+        y[e] = in ? a.y[(size_t)i * W + w] : 0.0;
+    }
+    double lpost = s.logpost[w], lpri = s.logprior[w], llik = s.loglike[w];
+    __shared__ pair_t sRE[kDuoStagedPairs];
+    if (refresh_y) {
+        // y = L^-1 (x - mu) from the walker's x, as step_inc_kernel does it: the deviations of the
+        // workgroup's 128 walkers in the chunk buffers ([walker][SD doubles], zero beyond d), L^-1 eight
+        // columns at a time through a [dpad][8] tile in sRE, one ascending fma chain per row from +0.0
+        constexpr int TW = 8, SD = (dpad + TW - 1) / TW * TW;
+        static_assert(128 * SD <= 4 * CHUNK, "the chunk buffers hold the deviations of the workgroup's walkers");
+        static_assert(sizeof(pair_t) * kDuoStagedPairs >= sizeof(double) * dpad * TW, "the tile fits sRE");
+        double* const sdev = (double*)smem2 + (size_t)(tid >> 1) * SD;
+        double* const tile = (double*)sRE;
+        for (int i = h; i < SD; i += 2) sdev[i] = 0.0;   // (a wave's LDS writes land in order)
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int i = duo1_dim<SPLIT>(e, h);
+            if (i < d) sdev[i] = x[e] - a.mean[i];
+            y[e] = 0.0;
+        }
+        for (int i0 = 0; i0 < d; i0 += TW) {
+            __syncthreads();   // (the previous tile has been used; the first: sdev is written)
+            for (int e = tid; e < dpad * TW; e += 256) {
+                const int j = e / TW, i = i0 + e % TW;
+                tile[e] = (j < d && i < d) ? a.Lrow[(size_t)j * d + i] : 0.0;
+            }
+            __syncthreads();
+            const lds_doubles pt = relaunder(tile + (SPLIT ? h : 2 * h) * TW), pd = relaunder(sdev + i0);
+#pragma unroll
+            for (int ii = 0; ii < TW; ++ii) {
+                const double dv = pd[ii];   // (beyond d: 0, and the tile's column is 0)
+#pragma unroll
+                for (int e = 0; e < NE; ++e) y[e] = fma(pt[duo1_off<SPLIT>(e) * TW + ii], dv, y[e]);
+            }
+        }
+        __syncthreads();   // every wave is done with its scratch: the first chunk may land
+        stage(0);
+    }
+    if (a.anchor) {   // (wave-uniform) y has just been refreshed from x: orc_anchor_loglike
+        double pa0 = 0.0, pa1 = 0.0;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            if (e & 1) pa1 = fma(y[e], y[e], pa1);
+            else pa0 = fma(y[e], y[e], pa0);
+        }
+        llik = -0.5 * (s.cnorm0 + duo1_sum<SPLIT>(pa0, pa1));
+        lpost = lpri + llik;
+    }
+    int wt = s.weight[w], prej = s.prior_rej[w], burn = s.burn_left[w];
+    const long long nacc0 = s.n_accept[w];
+    int nacc = 0;
+    const cdoubles gUU = (cdoubles)(unsigned long long)(a.UU + (size_t)g * set_cols + (size_t)a.col0);
+    const uint32_t gid = s.walker0 + (uint32_t)w;
+    const double mt10 = s.max_tries * 10.0;
+    const int lim1 = s.max_tries < 2.0e9 ? (int)floor(s.max_tries) : 0x7fffffff;
+    const int lim10 = mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff;
+    __shared__ dpair_t short_log_lds[SHORT_LOG_TABLE_SIZE];
+    const short_log_tab slog = short_log_load(short_log_lds);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    bool burning = lanes(burn > 0) != 0ull;   // wave-uniform
+    unsigned long long cur_oct = ~0ull;
+    DuoVariates sv;
+    sv.init(sRE, wave, lane);
+    const int hw_slot = hw_wave_slot();
+
+    for (int base = 0, k = 0; base < ncols; base += C, ++k) {
+        const double2* __restrict__ cur = smem2 + (k & 1) * CHUNK;
+        stage(k + 1);
+        const int cols = __builtin_amdgcn_readfirstlane(ncols - base < C ? ncols - base : C);
+        unsigned coff = lds_offset(cur + (SPLIT ? h : 2 * h));
+#pragma unroll 1
+        for (int sl = 0; sl < cols; ++sl, coff += COLB * 16) {
+            const unsigned long long S = s.step0 + (unsigned long long)(base + sl);
+            if ((S >> 3) != cur_oct) {   // wave-uniform: every eighth step
+                cur_oct = S >> 3;
+                rotate_priority<2>(hw_slot);
+#pragma unroll 1
+                for (int q = 0; q < 2; ++q) {   // (rolled: one Philox block's registers at a time)
+                    PairRng pr;
+                    pr.run(s.key0, s.key1, gid, (cur_oct << 2) + (unsigned long long)(2 * h + q), slog);
+                    sv.put(sRE, wave, lane, h, q, pr);
+                }
+                sv.seek(S);
+            }
+            double r, Ea;
+            sv.fetch(r, Ea);
+            sv.next();
+            const double uu = gUU[base + sl];   // (wave-uniform address: a scalar load)
+            // the step's pairs stay in registers from the trial to the commit (requesting the next
+            // step's behind the commit, over the bookkeeping, was measured slower: 1.24 against 1.02 ms)
+            pair_t pk[NE];
+            const lds_pairs col = (lds_pairs)(unsigned long long)coff;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) pk[e] = col[duo1_off<SPLIT>(e)];
+            // the support test on the high words of the trial coordinates (step_inc_kernel MODE 0)
+            unsigned hmx = 0u;
+            double pc0 = 0.0, pc1 = 0.0;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const double t = fma(r, pk[e].x, x[e]);
+                const unsigned hw = (unsigned)__double2hiint(t);
+                hmx = hmx > hw ? hmx : hw;
+                if (e & 1) pc1 = fma(y[e], pk[e].y, pc1);   // (y . u: the log-likelihood is carried)
+                else pc0 = fma(y[e], pk[e].y, pc0);
+            }
+            unsigned long long inside_m = lanes(pair_max_u32(hmx) < bhi_word);
+            if (inside_m != lanes(true)) {   // (wave-uniform, rare) the exact test
+                unsigned long long inb = ~0ull;
+#pragma unroll
+                for (int e = 0; e < NE; ++e) {
+                    const double t = fma(r, pk[e].x, x[e]);
+                    inb &= lanes(t <= bhi) & lanes(t >= blo);
+                }
+                inside_m = pair_all_mask(inb);
+            }
+            // chi2(y + r u) - chi2(y) = r (2 y.u + r |u|^2) (step_core_inc, `carry`)
+            const double yu = duo1_sum<SPLIT>(pc0, pc1);
+            const double mhr = -0.5 * r;
+            const double lp = s.uniform_logp;
+            const double ll = fma(mhr, fma(r, uu, yu + yu), llik);
+            const double lt = lp + ll;
+            const double delta = UNIT_T ? (lpost - lt) : (lpost - lt) / s.temperature;
+            const unsigned long long acc_m = inside_m & (lanes(lt > lpost) | lanes(Ea > delta));
+            const bool accept = __builtin_amdgcn_inverse_ballot_w64(acc_m);
+            llik = accept ? ll : llik;
+            int lim = lim1;
+            if (burning) {   // wave-uniform (see step_inc_kernel)
+                lim = burn > 0 ? lim10 : lim1;
+                burn -= (accept & (burn > 0)) ? 1 : 0;
+                burning = lanes(burn > 0) != 0ull;
+            }
+            const double ra = accept ? r : 0.0;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                x[e] = fma(ra, pk[e].x, x[e]);
+                y[e] = fma(ra, pk[e].y, y[e]);
+            }
+            lpost = accept ? lt : lpost;
+            {
+                const bool inside = __builtin_amdgcn_inverse_ballot_w64(inside_m);
+                prej = accept ? 0 : (prej + (inside ? 0 : 1));
+                wt = accept ? 1 : wt + 1;
+                nacc += accept ? 1 : 0;
+            }
+            if (wt - prej > lim && h == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next chunk has landed
+        __syncthreads();
+    }
+    // (the walker index passes through an empty asm: the store addresses are formed here, not kept
+    // alive from the prologue's loads)
+    int we = w, he = h;
+    asm volatile("" : "+v"(we), "+v"(he));
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        const int i = duo1_dim<SPLIT>(e, he);
+        if (i < d) {
+            s.x[(size_t)i * W + we] = x[e];
+            a.y[(size_t)i * W + we] = y[e];
+        }
+    }
+    if (h == 0) {
+        s.logpost[we] = lpost; s.logprior[we] = lpri; s.loglike[we] = llik;
+        s.weight[we] = wt; s.prior_rej[we] = prej; s.burn_left[we] = burn;
+        s.n_accept[we] = nacc0 + nacc;
+    }
+    wave_add_accepts(s.accept_total, (h == 0) ? nacc : 0);
+}
+
+template <int DQ, int NE, bool SPLIT>
+hipError_t launch_duo1(const IncStepArgs& a, hipStream_t st)
+{
+    constexpr int C = duo1_chunk(DQ);
+    const size_t lds = sizeof(double2) * 2 * C * 4 * DQ;
+    const bool unit_t = a.s.temperature == 1.0;
+    typedef void (*kern_t)(const IncStepArgs);
+    static const kern_t kerns[2] = {step_inc_duo_kernel<DQ, NE, SPLIT, false>,
+                                    step_inc_duo_kernel<DQ, NE, SPLIT, true>};
+    static const std::string names[2] = {"mcmc::step_inc_kernel<" + std::to_string(DQ) + ", 0, false, two lanes>",
+                                         "mcmc::step_inc_kernel<" + std::to_string(DQ) + ", 0, true, two lanes>"};
+    const int v = unit_t ? 1 : 0;
+    if (lds > 40 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)kerns[v],
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    mcmc_hip_note_step_kernel(names[v].c_str());
+    hipLaunchKernelGGL(kerns[v], dim3(a.s.W / 128), dim3(256), lds, st, a);
+    return hipGetLastError();
+}
+
+template <int DQ>
+hipError_t dispatch_duo1(const IncStepArgs& a, hipStream_t st)
+{
+    if constexpr (DQ > kDuo1MaxDq) {
+        return hipErrorInvalidValue;
+    } else {
+        if (a.dq != DQ) return dispatch_duo1<DQ + 1>(a, st);
+        constexpr bool SPLIT = MCMC_DUO1_SPLIT != 0;
+        if constexpr (SPLIT) {
+            if ((a.d + 1) / 2 == 2 * DQ - 1) return launch_duo1<DQ, 2 * DQ - 1, true>(a, st);
+            return launch_duo1<DQ, 2 * DQ, true>(a, st);
+        } else {
+            return launch_duo1<DQ, 2 * DQ, false>(a, st);
+        }
+    }
+}
+#endif  // MCMC_DUO_DQ_LO == 1
+
 }  // namespace
 }  // namespace mcmc
 
@@ -527,3 +823,17 @@ extern "C" hipError_t MCMC_CAT(mcmc_hip_launch_inc_duo_, MCMC_DUO_DQ_LO)(const m
     if (a->n_modes < 2 || !a->amode || a->vu_cols > 0) return hipErrorInvalidValue;
     return mcmc::dispatch_duo_mix<MCMC_DUO_DQ_LO>(*a, st);
 }
+
+#if MCMC_DUO_DQ_LO == 1
+// one mode (step_inc_duo_kernel): MODE 0 (one box [0, hi]), Metropolis steps, no periodic parameter, no
+// emitted rows, no block of one parameter, whole workgroups of 128 walkers inside one basis group
+extern "C" hipError_t mcmc_hip_launch_inc_duo1(const mcmc::IncStepArgs* a, hipStream_t st)
+{
+    if (a->dq < 1 || a->dq > mcmc::kDuo1MaxDq || a->n_modes != 1 || a->n_drag > 0 || a->colflag || a->s.rows ||
+        a->s.W % 128 != 0 || a->s.group_size % 128 != 0 || a->has_norm || !a->box || a->box_lo != 0.0 || !a->UU)
+        return hipErrorInvalidValue;
+    for (int q = 0; q < 4; ++q)
+        if (a->periodic_mask4[q]) return hipErrorInvalidValue;
+    return mcmc::dispatch_duo1<1>(*a, st);
+}
+#endif

@@ -249,6 +249,9 @@ __host__ __device__ constexpr bool duo_serves(int K, int dq)
 #endif
 __host__ __device__ constexpr bool duo_x_in_lds(int K, int dq) { return 2 * dq * (K + 1) > MCMC_DUO_XLDS_ABOVE; }
 
+// step_inc_duo_kernel (incremental_duo.hip, round 7): one mode, MODE 0, two lanes per walker up to d = 32
+constexpr int kDuo1MaxDq = 8;
+
 // periodic parameters step_inc_kernel<.., PER> serves (one mode, Metropolis steps, no emitted rows);
 // more: the general incremental kernels (incremental_any.hip)
 constexpr int kIncMaxPeriodic = 16;
