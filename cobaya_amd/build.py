@@ -132,8 +132,12 @@ def build(dims=None, jobs=None, verbose=True):
         tasks.append((duo, os.path.join(OBJ, f"incremental_duo_{lo_}.o"),
                       [f"-DMCMC_DUO_DQ_LO={lo_}", f"-DMCMC_DUO_DQ_HI={hi_}"],
                       _digest([duo, inc_hdr] + hdrs, extra=f"duo{lo_}-{hi_}|{' '.join(FLAGS)}")))
+    huge = os.path.join(CSRC, "huge_kernels.hip")   # 128 < d <= 256 (run-time d)
+    huge_hdr = os.path.join(CSRC, "huge_args.h")
+    tasks.append((huge, os.path.join(OBJ, "huge.o"), [],
+                  _digest([huge, huge_hdr] + hdrs, extra=" ".join(FLAGS))))
     tasks.append((capi, os.path.join(OBJ, "capi.o"), [],
-                  _digest([capi, root_hdr, pl_hdr, ck_hdr, comm_hdr] + hdrs, extra=" ".join(FLAGS))))
+                  _digest([capi, root_hdr, pl_hdr, ck_hdr, comm_hdr, huge_hdr] + hdrs, extra=" ".join(FLAGS))))
     jobs = jobs or min(len(tasks), os.cpu_count() or 4)
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         rebuilt = list(ex.map(lambda t: _compile(*t), tasks))

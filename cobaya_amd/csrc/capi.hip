@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "huge_args.h"
 #include "pliklite_args.h"
 #include "checkpoint_args.h"
 #include "comm.h"
@@ -292,6 +293,13 @@ extern "C" hipError_t mcmc_hip_launch_whiten_directions(const mcmc::IncDirArgs* 
                                                         hipStream_t st) __attribute__((weak));
 
 // checkpoint_kernels.hip
+// huge_kernels.hip: 128 < d <= 256 (run-time d; incremental evaluation, one block, up to four modes)
+extern "C" hipError_t mcmc_hip_launch_huge_basis(const mcmc::HugeBasisArgs*, int, int, hipStream_t);
+extern "C" hipError_t mcmc_hip_launch_huge_dirs(const mcmc::HugeDirArgs*, int, hipStream_t);
+extern "C" hipError_t mcmc_hip_launch_huge_step(const mcmc::HugeStepArgs*, hipStream_t);
+extern "C" hipError_t mcmc_hip_launch_huge_evaluate(const mcmc::HugeEvalArgs*, hipStream_t);
+extern "C" hipError_t mcmc_hip_launch_huge_moments(const mcmc::MomentArgs*, int, int, hipStream_t);
+
 extern "C" hipError_t mcmc_hip_launch_ckpt_window(const mcmc::CkptWindowArgs* a, hipStream_t st);
 extern "C" hipError_t mcmc_hip_launch_ckpt_payload(const mcmc::CkptPayloadArgs* a, hipStream_t st);
 extern "C" hipError_t mcmc_hip_launch_ckpt_solve(const mcmc::CkptSolveArgs* a, hipStream_t st);
@@ -315,6 +323,11 @@ struct mcmc_hip_ctx {
     const DimKernels* k = nullptr;    // d <= 32: lane-per-walker kernels of that dimension
     const BigKernels* kb = nullptr;   // 32 < d <= 128: column-sweep / matrix-core kernels
     const mcmc::PairKernels* kp = nullptr;   // 32 < d <= 56: the two-wave step kernel, if it fits
+    bool huge = false;                // 128 < d <= 256: huge_kernels.hip (incremental, one block, K <= 4)
+    // huge: the Haar columns of one cycle of every basis group ([BG][d][d]), the basis scratch, and
+    // the per-step direction columns of a launch ([BG][n][huge_col_stride])
+    DevBuf<double> hV, hScratch, hCols;
+    unsigned long long hV_cycle = ~0ull, hV_epoch = ~0ull;
     hipStream_t stream = nullptr;
     std::string err;
     int d = 0, W = 0, G = 0, gs = 0, K = -1;
@@ -618,9 +631,9 @@ int upload_constants(mcmc_hip_ctx* h)
         HIP_TRY(h, hipMemcpyAsync(h->dLcol.p, lcol.data(), sizeof(double) * lcol.size(),
                                   hipMemcpyHostToDevice, h->stream));
     }
-    if (h->incremental && K >= 1 && K <= mcmc::kMaxModes) {
+    if (h->incremental && (K >= 1 || h->huge) && K <= mcmc::kMaxModes) {
         const int dq = (d + 3) / 4, dpad = 4 * dq;
-        HIP_TRY(h, h->y.resize((size_t)K * d * h->W));
+        if (K > 0) HIP_TRY(h, h->y.resize((size_t)K * d * h->W));
         if (K > 1) HIP_TRY(h, h->amode.resize((size_t)K * h->W));
         h->amode_valid = false;
         std::vector<double> pr((size_t)5 * dpad, 0.0);
@@ -636,12 +649,14 @@ int upload_constants(mcmc_hip_ctx* h)
         HIP_TRY(h, h->inc_prior.resize(pr.size()));
         HIP_TRY(h, hipMemcpyAsync(h->inc_prior.p, pr.data(), sizeof(double) * pr.size(),
                                   hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, h->inc_Lrow.resize((size_t)K * d * d));
-        HIP_TRY(h, hipMemcpyAsync(h->inc_Lrow.p, h->Linv.data(), sizeof(double) * K * d * d,
-                                  hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, h->inc_mean.resize((size_t)K * d));
-        HIP_TRY(h, hipMemcpyAsync(h->inc_mean.p, h->mean.data(), sizeof(double) * K * d,
-                                  hipMemcpyHostToDevice, h->stream));
+        if (K > 0) {
+            HIP_TRY(h, h->inc_Lrow.resize((size_t)K * d * d));
+            HIP_TRY(h, hipMemcpyAsync(h->inc_Lrow.p, h->Linv.data(), sizeof(double) * K * d * d,
+                                      hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, h->inc_mean.resize((size_t)K * d));
+            HIP_TRY(h, hipMemcpyAsync(h->inc_mean.p, h->mean.data(), sizeof(double) * K * d,
+                                      hipMemcpyHostToDevice, h->stream));
+        }
         h->y_valid = false; h->amode_valid = false;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -652,7 +667,7 @@ int lds_check(mcmc_hip_ctx* h)
 {
     const ConstLayout cl{h->d, h->K};
     (void)cl;
-    if (h->kb) return MCMC_HIP_OK;  // the big step kernel's LDS does not depend on K
+    if (h->kb || h->huge) return MCMC_HIP_OK;  // the big / huge step kernels' LDS does not depend on K
     const size_t lds = sizeof(double) * ((h->K > 1 ? (size_t)h->K * 256 : 0) +
                                          2 * (size_t)(256 / h->gs) * mcmc::v_slab(h->d));
     if (lds > 160 * 1024)
@@ -668,6 +683,9 @@ int set_target_common(mcmc_hip_ctx* h, int K, const double* means, const double*
     const int d = h->d;
     if (K < 1 || K > mcmc::kMaxModes)
         return fail(h, MCMC_HIP_ERR_ARG, "n_modes must be in 1..%d, got %d", mcmc::kMaxModes, K);
+    if (h->huge && K > mcmc::kHugeMaxModes)
+        return fail(h, MCMC_HIP_ERR_ARG, "d=%d > %d serves at most %d mixture modes, got %d", d, kMaxDimBig,
+                    mcmc::kHugeMaxModes, K);
     std::vector<double> L((size_t)d * d), Li((size_t)d * d);
     h->mean.assign(means, means + (size_t)K * d);
     h->Linv.assign((size_t)K * d * d, 0.0);
@@ -894,6 +912,8 @@ int mcmc_hip_dim_supported(int d)
     return kernels_for_dim(d) != nullptr || big_for_dim(d) != nullptr;
 }
 
+int32_t mcmc_hip_max_dim(void) { return mcmc::kMaxDimHuge; }
+
 int mcmc_hip_incremental_supported(int32_t d, int32_t n_modes, int32_t n_periodic, int32_t n_drag,
                                    int32_t n_walkers, int32_t basis_group_size)
 {
@@ -920,7 +940,24 @@ int mcmc_hip_create(const mcmc_hip_config* cfg, mcmc_hip_ctx** out)
     if (cfg->d < 1) return fail(nullptr, MCMC_HIP_ERR_ARG, "d must be >= 1, got %d", cfg->d);
     const DimKernels* k = kernels_for_dim(cfg->d);
     const BigKernels* kb = k ? nullptr : big_for_dim(cfg->d);
-    if (!k && !kb)
+    const bool huge = cfg->d > kMaxDimBig;
+    if (huge) {   // 128 < d <= 256: huge_kernels.hip serves incremental evaluation with the shared basis
+        if (cfg->d > mcmc::kMaxDimHuge)
+            return fail(nullptr, MCMC_HIP_ERR_ARG, "d=%d is above the largest dimension served (%d)",
+                        cfg->d, mcmc::kMaxDimHuge);
+        if (!(cfg->flags & MCMC_HIP_FLAG_INCREMENTAL))
+            return fail(nullptr, MCMC_HIP_ERR_ARG,
+                        "d=%d > %d is served with incremental evaluation only (evaluation: full is not)",
+                        cfg->d, kMaxDimBig);
+        if (cfg->flags & MCMC_HIP_FLAG_OWN_BASIS)
+            return fail(nullptr, MCMC_HIP_ERR_ARG, "d=%d > %d needs the shared basis (shared_basis: False is not served)",
+                        cfg->d, kMaxDimBig);
+        if (cfg->emit_capacity > 0)
+            return fail(nullptr, MCMC_HIP_ERR_ARG,
+                        "d=%d > %d emits no rows on the device (emit: chains is not served; use emit: snapshots)",
+                        cfg->d, kMaxDimBig);
+    }
+    if (!k && !kb && !huge)
         return fail(nullptr, MCMC_HIP_ERR_ARG,
                     "no kernels compiled for d=%d (this build covers d = 1..32 lane-per-walker "
                     "and 33..%d column-sweep, as selected at build time)", cfg->d, kMaxDimBig);
@@ -977,6 +1014,7 @@ int mcmc_hip_create(const mcmc_hip_config* cfg, mcmc_hip_ctx** out)
     h->cfg = *cfg;
     h->k = k;
     h->kb = kb;
+    h->huge = huge;
     // MCMC_HIP_NO_PAIR_BIG (developer switch): keep 32 < d <= 56 on the matrix-core kernel
     h->kp = (kb && !getenv("MCMC_HIP_NO_PAIR_BIG")) ? pair_for_dim(cfg->d) : nullptr;
     h->d = cfg->d;
@@ -1069,6 +1107,7 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     if (h->T_event) (void)hipEventDestroy(h->T_event);
     if (h->stream2) (void)hipStreamDestroy(h->stream2);
     h->x.release(); h->logpost.release(); h->logprior.release(); h->loglike.release();
+    h->hV.release(); h->hScratch.release(); h->hCols.release();
     h->cblock.release(); h->dT.release(); h->V.release(); h->rows.release(); h->gsum.release();
     h->Sg.release(); h->pooled.p = nullptr; /* (a view into gsum) */ h->dshift.release(); h->ex.release(); h->elp.release();
     h->ell.release(); h->eder.release(); h->escratch.release(); h->dLrow.release();
@@ -1125,6 +1164,9 @@ int mcmc_hip_set_prior(mcmc_hip_ctx* h, const int32_t* kind, const double* a, co
             h->lo[i] = a[i]; h->hi[i] = b[i];
             ulp += std::log(b[i] - a[i]);
             if (periodic && periodic[i]) {
+                if (h->huge)
+                    return fail(h, MCMC_HIP_ERR_ARG, "d=%d > %d: periodic parameters are not served (prior %d)",
+                                d, kMaxDimBig, i);
                 h->periodic[i] = 1;
                 h->any_periodic = true;
                 if (i < 32) h->periodic_mask |= 1u << i;
@@ -1137,7 +1179,7 @@ int mcmc_hip_set_prior(mcmc_hip_ctx* h, const int32_t* kind, const double* a, co
                             "parameter %d cannot be periodic if it is not bounded", i);
             h->loc[i] = a[i]; h->scale[i] = b[i];
             h->mls[i] = -std::log(b[i]) - std::log(2.0 * M_PI) / 2.0;  // tools.py:723
-            h->norm_mask4[i >> 5] |= 1u << (i & 31);
+            if (i < 128) h->norm_mask4[i >> 5] |= 1u << (i & 31);   // (d > 128: h->kind)
             if (i < 32) h->norm_mask |= 1u << i;
         } else {
             return fail(h, MCMC_HIP_ERR_ARG,
@@ -1186,6 +1228,8 @@ int mcmc_hip_set_target_binned_gaussian(mcmc_hip_ctx* h, int32_t n_bins, const i
                                         const double* D0, const double* J, int32_t calib_index)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
+    if (h->huge)
+        return fail(h, MCMC_HIP_ERR_ARG, "d=%d > %d: the binned Gaussian target is not served", h->d, kMaxDimBig);
     if (!bins || !weights || !X || !cov || !theta0 || !D0 || !J)
         return fail(h, MCMC_HIP_ERR_ARG, "null argument");
     const int d = h->d;
@@ -1409,6 +1453,10 @@ int mcmc_hip_set_blocking(mcmc_hip_ctx* h, int32_t n_blocks, const int32_t* bloc
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     if (!block_size || !oversampling || !i_of_j) return fail(h, MCMC_HIP_ERR_ARG, "null argument");
+    if (h->huge && (n_blocks != 1 || drag_last_slow >= 0))
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "d=%d > %d samples one parameter block (blocking / oversampling / drag are not served)",
+                    h->d, kMaxDimBig);
     const int d = h->d;
     // (d > 32 from scratch: the general kernels -- step_general_kernel, drag_general_kernel)
     if (n_blocks < 1 || n_blocks > 32)
@@ -1578,7 +1626,17 @@ int mcmc_hip_evaluate(mcmc_hip_ctx* h, int32_t n, const double* x, double* logpr
     a.norm_mask = h->norm_mask; a.periodic_mask = h->periodic_mask;
     a.uniform_logp = h->uniform_logp;
     for (int q = 0; q < 4; ++q) a.norm_mask4[q] = h->norm_mask4[q];
-    if (h->kb) {
+    if (h->huge) {
+        const ConstLayout cl{h->d, std::max(h->K, 0)};
+        mcmc::HugeEvalArgs e{};
+        e.x = h->ex.p; e.logprior = h->elp.p; e.loglike = h->ell.p; e.derived = a.derived;
+        e.prior = h->inc_prior.p; e.scale = h->cblock.p + cl.scale();
+        e.Lrow = h->inc_Lrow.p; e.mean = h->inc_mean.p;
+        e.cnorm = h->cblock.p + cl.cnorm(); e.mweight = h->cblock.p + cl.weight();
+        e.n = n; e.d = h->d; e.dpad = 4 * ((h->d + 3) / 4); e.K = std::max(h->K, 0);
+        e.uniform_logp = h->uniform_logp;
+        HIP_TRY(h, mcmc_hip_launch_huge_evaluate(&e, h->stream));
+    } else if (h->kb) {
         HIP_TRY(h, h->escratch.resize((size_t)n * std::max(h->K, 1)));
         HIP_TRY(h, h->kb->evaluate(a, h->dLrow.p, h->d, h->escratch.p, h->stream));
     } else {
@@ -1922,6 +1980,89 @@ int make_directions(mcmc_hip_ctx* h, const IncPlan& P, const IncSeg& s, mcmc_hip
     return MCMC_HIP_OK;
 }
 
+// mcmc_hip_step at 128 < d <= 256 (huge_kernels.hip): one parameter block, Metropolis steps, 1..4
+// Gaussian modes, no periodic parameter, no emitted rows.  A launch stays inside one cycle of the
+// basis: the Haar columns of that cycle are formed for every basis group (kept while the cycle and
+// the transform stay), then the directions of the launch's steps, then the step kernel -- which
+// refreshes y from x itself at the multiples of refresh_every = 40 d (oracle: orc_run).
+int step_huge(mcmc_hip_ctx* h, int n_steps)
+{
+    const int d = h->d, K = h->K;
+    if (K < 0 || K > mcmc::kHugeMaxModes || h->bg.on)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "d=%d > %d steps the `one` likelihood and Gaussian targets of 1..%d modes (K=%d is not served)",
+                    d, kMaxDimBig, mcmc::kHugeMaxModes, K);
+    if (h->any_periodic || h->blocked || h->drag_last_slow >= 0 || h->cfg.emit_capacity > 0 || h->emit_thin > 1)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "d=%d > %d serves one parameter block without periodic parameters or emitted rows",
+                    d, kMaxDimBig);
+    bool any_normal = false;
+    for (int i = 0; i < d; ++i) any_normal = any_normal || h->kind[i] == 1;
+    const int dpad = 4 * ((d + 3) / 4);
+    const int stride = mcmc::huge_col_stride(d, K);
+    const size_t BG = (size_t)h->BG;
+    const unsigned long long ud = (unsigned long long)d, R = 40ull * ud;
+    // steps per launch: at most what is left of the cycle, and a direction set of <= 256 MiB
+    const int max_n = (int)std::max<size_t>(1, std::min<size_t>(64, ((size_t)32 << 20) / (BG * stride)));
+    int left = n_steps;
+    while (left > 0) {
+        const unsigned long long cyc = h->step / ud;
+        const int n = (int)std::min<unsigned long long>(
+            (unsigned long long)std::min(left, max_n), ud - h->step % ud);
+        if (h->hV_cycle != cyc || h->hV_epoch != h->dir_epoch) {
+            Timed t(h, 1);
+            const long long per = mcmc::huge_basis_scratch(d);
+            const int slabs = (int)std::max<long long>(1, std::min<long long>((long long)BG, (32ll << 20) / per));
+            HIP_TRY(h, h->hV.resize(BG * (size_t)d * d));
+            HIP_TRY(h, h->hScratch.resize((size_t)slabs * (size_t)per));
+            mcmc::HugeBasisArgs b{};
+            b.T = h->dT.p; b.V = h->hV.p; b.scratch = h->hScratch.p; b.d = d; b.ncyc = 1;
+            b.group0 = h->cfg.walker_offset / (uint32_t)h->bgs; b.cycle0 = (uint32_t)cyc;
+            b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
+            HIP_TRY(h, mcmc_hip_launch_huge_basis(&b, (int)BG, slabs, h->stream));
+            h->hV_cycle = cyc; h->hV_epoch = h->dir_epoch;
+        }
+        {
+            Timed t(h, 1);
+            HIP_TRY(h, h->hCols.resize(BG * (size_t)n * stride));
+            mcmc::HugeDirArgs w{};
+            w.V = h->hV.p; w.Lrow = h->inc_Lrow.p; w.prior = h->inc_prior.p; w.out = h->hCols.p;
+            w.step0 = h->step; w.cycle0 = cyc; w.n_steps = n; w.ncyc = 1; w.d = d; w.dpad = dpad; w.K = K;
+            w.carry_prior = (K == 1 && any_normal) ? 1 : 0;
+            HIP_TRY(h, mcmc_hip_launch_huge_dirs(&w, (int)BG, h->stream));
+        }
+        {
+            Timed t(h, 0);
+            const ConstLayout cl{d, K};
+            mcmc::HugeStepArgs a{};
+            a.x = h->x.p; a.y = h->y.p; a.logpost = h->logpost.p; a.logprior = h->logprior.p;
+            a.loglike = h->loglike.p; a.weight = h->weight_i.p; a.prior_rej = h->prej.p;
+            a.burn_left = h->burn.p; a.n_accept = h->nacc.p; a.accept_total = h->acc_total.p;
+            a.stuck = h->stuck.p; a.cols = h->hCols.p; a.prior = h->inc_prior.p;
+            a.Lrow = h->inc_Lrow.p; a.mean = h->inc_mean.p; a.scale = h->cblock.p + cl.scale();
+            a.cnorm = h->cblock.p + cl.cnorm(); a.mweight = h->cblock.p + cl.weight();
+            a.d = d; a.dpad = dpad; a.K = K; a.W = h->W; a.bgs = h->bgs;
+            a.walker0 = h->cfg.walker_offset;
+            a.key0 = (uint32_t)h->cfg.seed; a.key1 = (uint32_t)(h->cfg.seed >> 32);
+            a.step0 = h->step; a.refresh = R; a.n_steps = n;
+            a.anchor = h->y_valid ? 0 : 1;
+            a.carry_prior = (K == 1 && any_normal) ? 1 : 0;
+            a.uniform_logp = h->uniform_logp; a.temperature = h->cfg.temperature;
+            a.max_tries = h->cfg.max_tries;
+            HIP_TRY(h, mcmc_hip_launch_huge_step(&a, h->stream));
+            h->y_valid = true;
+            h->n_step_launches += 1;
+            if (g_noted_kernel) {
+                h->last_step_kernel = std::string(g_noted_kernel) + " (d=" + std::to_string(d) + ")";
+                g_noted_kernel = nullptr;
+            }
+        }
+        h->step += (unsigned long long)n;
+        left -= n;
+    }
+    return MCMC_HIP_OK;
+}
+
 int step_incremental(mcmc_hip_ctx* h, int n_steps)
 {
     const int d = h->d, dq = (d + 3) / 4;
@@ -2226,6 +2367,7 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
     if (n_steps <= 0) return fail(h, MCMC_HIP_ERR_ARG, "n_steps must be > 0");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (h->bg.on) return step_binned(h, n_steps);
+    if (h->incremental && h->huge) return step_huge(h, n_steps);
     if (h->incremental) return step_incremental(h, n_steps);
     if (h->emit_thin > 1)
         return fail(h, MCMC_HIP_ERR_ARG, "emit_thin needs incremental evaluation; thin on the host");
@@ -2590,7 +2732,8 @@ int mcmc_hip_accumulate_moments(mcmc_hip_ctx* h)
     mcmc::MomentArgs a{};
     a.x = h->x.p; a.shift = h->dshift.p; a.group_sum = h->gsum.p; a.Sg = h->Sg.p;
     a.pooled = h->pooled.p; a.W = h->W; a.G = h->G;
-    if (h->kb) HIP_TRY(h, h->kb->moments(a, h->gs, h->d, h->stream));
+    if (h->huge) HIP_TRY(h, mcmc_hip_launch_huge_moments(&a, h->gs, h->d, h->stream));
+    else if (h->kb) HIP_TRY(h, h->kb->moments(a, h->gs, h->d, h->stream));
     else HIP_TRY(h, h->k->moments(a, h->gs, h->stream));
     h->n_snapshots += 1;
     return MCMC_HIP_OK;

@@ -51,6 +51,7 @@ SYMBOLS = [
     ("mcmc_hip_version", C.c_char_p, []),
     ("mcmc_hip_last_error", C.c_char_p, [_H]),
     ("mcmc_hip_dim_supported", C.c_int, [C.c_int]),
+    ("mcmc_hip_max_dim", C.c_int32, []),
     ("mcmc_hip_incremental_supported", C.c_int, [C.c_int32] * 6),
     ("mcmc_hip_create", C.c_int, [C.POINTER(Config), C.POINTER(_H)]),
     ("mcmc_hip_destroy", None, [_H]),
@@ -191,6 +192,11 @@ def _f64(a, shape=None):
     return a
 
 
+def max_dim():
+    """The largest number of sampled parameters the library serves (mcmc_hip_max_dim)."""
+    return int(load_library().mcmc_hip_max_dim())
+
+
 def incremental_supported(d, n_modes, n_periodic, n_drag, n_walkers, basis_group_size):
     """Does incremental evaluation (O(d) steps on carried whitened residuals) serve this model
     shape?  (mcmc_hip_incremental_supported: a pure function of the library, no device.)"""
@@ -290,6 +296,11 @@ class Communicator:
 
 class Engine:
     """One walker ensemble on one MI355X (one handle of the C ABI)."""
+
+    @staticmethod
+    def max_dim():
+        """The largest number of sampled parameters the library serves (mcmc_hip_max_dim)."""
+        return max_dim()
 
     def __init__(self, d, n_walkers, group_size=64, device=0, seed=0, walker_offset=0,
                  burn_in=0, temperature=1.0, proposal_scale=2.4, max_tries=None,

@@ -209,7 +209,14 @@ class EnsembleMCMC:
     fallback_covmat_scale = 4.0  # sampler.py:474
     _LoggedError = LoggedError   # the hosted class raises cobaya.log.LoggedError instead
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
-    MAX_DIM = 128    # capi.hip: kMaxDimBig (mixtures: at most 64 modes, model.py)
+    MAX_DIM = 128    # capi.hip: kMaxDimBig, every path (mixtures: at most 64 modes, model.py)
+    HUGE_MAX_MODES = 4   # 128 < d <= max_dim(): huge_kernels.hip (huge_args.h: kHugeMaxModes)
+
+    def _max_dim(self):
+        """The cap of the engine behind the seam: its max_dim() where it has one, else 128 (the
+        CPU oracle's step functions hold 128-element arrays)."""
+        f = getattr(self._engine_factory, "max_dim", None)
+        return int(f()) if callable(f) else self.MAX_DIM
 
     # ------------------------------------------------------------------ host seams
     def _fail(self, msg, *args, cause=None):
@@ -267,13 +274,14 @@ class EnsembleMCMC:
             self.Rminus1_last = np.inf
         spec = self.spec
         d = spec.d
-        if d > self.MAX_DIM:
-            # (fails here, with the reason, instead of at mcmc_hip_create's "no kernels compiled":
-            # the reference has no cap, proposal.py:96-201)
-            self._fail("mcmc_hip samples at most %d parameters (this model has %d): a walker group's "
-                       "Haar basis of d x d doubles is built in the 160 KiB of LDS of one compute "
-                       "unit.  Fix or marginalise parameters, or use the reference sampler `mcmc` "
-                       "for this model.", self.MAX_DIM, d)
+        max_dim = self._max_dim()
+        if d > max_dim:
+            # (fails here, with the reason, instead of at mcmc_hip_create: the reference has no
+            # cap, proposal.py:96-201)
+            self._fail("mcmc_hip samples at most %d parameters (this model has %d).  Fix or "
+                       "marginalise parameters, or use the reference sampler `mcmc` for this "
+                       "model.", max_dim, d)
+        self._huge = d > self.MAX_DIM
         if self.temperature is None:
             self.temperature = 1
         if self.temperature < 1:
@@ -373,6 +381,11 @@ class EnsembleMCMC:
         if not self.shared_basis and (len(self.blocks) > 1 or self.oversampling_factors[0] != 1):
             self._fail("shared_basis: False serves a single parameter block without "
                        "oversampling or dragging")
+        if self._huge:
+            # (mcmc_hip_incremental_supported answers for d <= 128; above, huge_kernels.hip serves
+            # the shapes _check_huge lets through, and nothing else)
+            self._check_huge(spec, d)
+            can_inc = int(self.group_size) % 64 == 0 and W % int(self.group_size) == 0
         if self.evaluation == "incremental" and not can_inc:
             self._fail("evaluation: incremental serves Gaussian mixtures whose whitened residuals "
                        "(n_modes * d doubles per walker) fit the LDS, with Metropolis steps; "
@@ -428,6 +441,9 @@ class EnsembleMCMC:
                     self.drag_interp_steps if self.drag else 0)
                 assert self.engine.cycle_length() == self.cycle_length
         except EngineError as e:
+            if self._huge:   # (d > 128 is the HIP engine's huge_kernels.hip path alone)
+                self._fail("mcmc_hip samples at most 128 parameters unless the HIP engine can serve "
+                           "d = %d (up to %d): %s", d, max_dim, str(e), cause=e)
             self._fail("%s", str(e), cause=e)
         # thinned output: on the device where the engine's emitting kernel does it (PCIe then
         # carries output_thin times fewer rows), else on the host (`_thin_rows`)
@@ -519,6 +535,35 @@ class EnsembleMCMC:
         k = min(free, key=lambda k_: self._bslots[k_])
         self._bslots[k] = i
         self.engine.bounds_snapshot(k)
+
+    def _check_huge(self, spec, d):
+        """128 < d <= 256 (huge_kernels.hip) serves incremental evaluation of one parameter block
+        with Metropolis steps: the `one` likelihood or Gaussian targets of 1..4 modes, uniform / normal priors, the shared
+        basis, emit: snapshots.  Everything else is refused here, by the option to change."""
+        why = None
+        if spec.n_modes < 1 and spec.like_kind != "one":
+            why = "likelihood %r: only `one` and Gaussian targets (gaussian, gaussian_mixture) are served" % (
+                spec.like_kind,)
+        elif spec.n_modes > self.HUGE_MAX_MODES:
+            why = "the target has %d mixture modes (at most %d)" % (spec.n_modes, self.HUGE_MAX_MODES)
+        elif np.any(spec.periodic):
+            why = "periodic parameters are not served"
+        elif self.drag:
+            why = "drag: True is not served"
+        elif len(self.blocks) > 1 or any(int(f) != 1 for f in self.oversampling_factors):
+            why = "parameter blocks / oversample_power / blocking are not served (one block only)"
+        elif self.evaluation == "full":
+            why = "evaluation: full is not served (use evaluation: incremental or auto)"
+        elif not self.shared_basis:
+            why = "shared_basis: False is not served"
+        elif self.emit != "snapshots":
+            why = "emit: %s is not served (use emit: snapshots)" % self.emit
+        elif self.device_checkpoint in (True, "solve"):
+            why = "device_checkpoint: %r is not served (the solve runs on the host: None or False)" % (
+                self.device_checkpoint,)
+        if why:
+            self._fail("mcmc_hip samples d = %d > %d parameters with incremental evaluation of one "
+                       "parameter block only: %s", d, self.MAX_DIM, why)
 
     def _init_device_checkpoint(self):
         """`device_checkpoint`: which part of the checkpoint runs on the device -- nothing (False),

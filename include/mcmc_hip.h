@@ -43,7 +43,7 @@ enum {
 /* Options fixed at creation.  Mirrors the attributes cobaya/samplers/mcmc/mcmc.py:111-271
  * (MCMC.initialize) reads from mcmc.yaml, plus the ensemble geometry. */
 typedef struct mcmc_hip_config {
-    int32_t d;               /* number of sampled parameters, 1..128 (mcmc_hip_dim_supported) */
+    int32_t d;               /* number of sampled parameters, 1..256 (mcmc_hip_max_dim) */
     int32_t n_walkers;       /* walkers on this device; multiple of group_size */
     int32_t group_size;      /* walkers sharing one Haar basis: 64, 128 or 256 */
     int32_t device;          /* HIP device ordinal */
@@ -82,6 +82,10 @@ MCMC_HIP_API const char* mcmc_hip_version(void);
 MCMC_HIP_API const char* mcmc_hip_last_error(const mcmc_hip_ctx* h);
 /* 1 if the lane-per-walker kernels for dimension d were compiled into this library */
 MCMC_HIP_API int mcmc_hip_dim_supported(int d);
+/* the largest number of sampled parameters any configuration serves (256): d <= 128 on every path,
+ * 128 < d <= 256 with incremental evaluation of one parameter block (Metropolis steps, the `one` likelihood or 1..4
+ * Gaussian modes, no periodic parameter, no emitted rows; huge_kernels.hip) */
+MCMC_HIP_API int32_t mcmc_hip_max_dim(void);
 /* 1 if MCMC_HIP_FLAG_INCREMENTAL serves a Gaussian mixture of n_modes (>= 1) modes in d dimensions
  * of which n_periodic are periodic (prior.py:658-676), with n_drag interpolation steps per dragging
  * step (0: Metropolis steps), for n_walkers walkers of which basis_group_size share a proposal

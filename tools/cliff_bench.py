@@ -13,7 +13,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from cobaya_amd.engine import Engine, incremental_supported  # noqa: E402
+from cobaya_amd.engine import Engine, incremental_supported, max_dim  # noqa: E402
 
 DEFAULT = ["30:1:0", "30:1:1", "30:1:12", "30:2:0", "30:4:0", "30:5:0", "30:8:0", "30:16:0",
            "30:2:1", "30:5:3", "64:4:0", "64:8:0", "80:2:0", "100:1:12", "100:2:0", "100:4:0",
@@ -36,7 +36,9 @@ def run(d, K, n_per, W=65536, gs=256, launches=2):
     hi = [0.5 + ns * sd[i] if per[i] else 1.0 for i in range(d)]
     if differ:
         lo[0] = -0.125
-    if not incremental_supported(d, K, n_per, 0, W, 4096):
+    # (d > 128: huge_kernels.hip, one to four modes without periodic parameters)
+    huge = 128 < d <= max_dim() and 1 <= K <= 4 and n_per == 0
+    if not huge and not incremental_supported(d, K, n_per, 0, W, 4096):
         print(f"d={d} K={K} periodic={n_per}: not served incrementally", flush=True)
         return
     # (CLIFF_MAX_TRIES: timing experiments on builds whose chains do not move)
