@@ -136,8 +136,12 @@ def build(dims=None, jobs=None, verbose=True):
     huge_hdr = os.path.join(CSRC, "huge_args.h")
     tasks.append((huge, os.path.join(OBJ, "huge.o"), [],
                   _digest([huge, huge_hdr] + hdrs, extra=" ".join(FLAGS))))
+    fnk = os.path.join(CSRC, "function_kernels.hip")   # function targets (the user's batched device function)
+    fn_hdr = os.path.join(CSRC, "function_args.h")
+    tasks.append((fnk, os.path.join(OBJ, "function.o"), [],
+                  _digest([fnk, fn_hdr] + hdrs, extra=" ".join(FLAGS))))
     tasks.append((capi, os.path.join(OBJ, "capi.o"), [],
-                  _digest([capi, root_hdr, pl_hdr, ck_hdr, comm_hdr, huge_hdr] + hdrs, extra=" ".join(FLAGS))))
+                  _digest([capi, root_hdr, pl_hdr, ck_hdr, comm_hdr, huge_hdr, fn_hdr] + hdrs, extra=" ".join(FLAGS))))
     jobs = jobs or min(len(tasks), os.cpu_count() or 4)
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         rebuilt = list(ex.map(lambda t: _compile(*t), tasks))

@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "huge_args.h"
 #include "pliklite_args.h"
+#include "function_args.h"
 #include "checkpoint_args.h"
 #include "comm.h"
 
@@ -317,6 +318,9 @@ extern "C" hipError_t mcmc_hip_launch_pl_residual_mfma(const mcmc::PlResidualMfm
 extern "C" hipError_t mcmc_hip_launch_pl_fused(const mcmc::PlFusedArgs* a, hipStream_t st);
 extern "C" hipError_t mcmc_hip_launch_pl_chi2(const mcmc::PlChi2Args* a, hipStream_t st);
 extern "C" hipError_t mcmc_hip_launch_pl_combine(const double* psum, double* chi2, int n, hipStream_t st);
+// function_kernels.hip
+extern "C" hipError_t mcmc_hip_launch_fn_walker(const mcmc::FnWalkerArgs* a, int accept, int propose,
+                                                hipStream_t st);
 
 struct mcmc_hip_ctx {
     mcmc_hip_config cfg{};
@@ -406,6 +410,7 @@ struct mcmc_hip_ctx {
     hipEvent_t pin_T_done[4] = {nullptr, nullptr, nullptr, nullptr};   // the copy out of slot k has run
     hipEvent_t mom_event = nullptr;
     bool mom_pending = false;
+    bool mom_fn = false;                            // the pending read-out carries a function target's error flag
     int64_t mom_n = 0;
     unsigned long long mom_step = 0;
     // drain_samples_pinned: ring of pinned host slots the packed rows are copied into (PCIe at
@@ -473,6 +478,15 @@ struct mcmc_hip_ctx {
         unsigned long long tile_off[8][5];
         int nk[8][5];
     } bg;
+    // function target (mcmc_hip_set_target_function; function_kernels.hip): the user's batched
+    // device function stands where the likelihood kernels of the other targets do
+    struct Function {
+        bool on = false;
+        mcmc_hip_loglike_fn fn = nullptr;
+        void* user = nullptr;
+        DevBuf<double> points, lp_t, Ea, ll_t;   // step scratch: trial [W][d], its log-prior, E_a, the function's values
+        DevBuf<int> bad;                         // [1] 1 + global id of the first walker with NaN / +inf inside the support
+    } fnt;
 };
 
 namespace {
@@ -715,6 +729,7 @@ int set_target_common(mcmc_hip_ctx* h, int K, const double* means, const double*
     }
     h->K = K;
     h->bg.on = false;
+    h->fnt.on = false;
     h->have_target = true;
     ++h->dir_epoch;
     h->have_state = false;
@@ -894,6 +909,115 @@ int step_binned(mcmc_hip_ctx* h, int n_steps)
         g_noted_kernel = nullptr;
     }
     return MCMC_HIP_OK;
+}
+
+// ------------------------------------------------------------------ function target
+// what may be set before or after the target: checked by mcmc_hip_set_target_function and again by
+// every mcmc_hip_step
+int function_refusals(mcmc_hip_ctx* h)
+{
+    if (h->blocked || h->drag_last_slow >= 0)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target serves one parameter block with Metropolis steps (parameter "
+                    "blocks, oversampling and dragging are not served)");
+    if (h->any_periodic)
+        return fail(h, MCMC_HIP_ERR_ARG, "a function target does not serve periodic parameters");
+    return MCMC_HIP_OK;
+}
+
+int function_call(mcmc_hip_ctx* h, int n, const double* points, double* loglike)
+{
+    const int rc = h->fnt.fn(h->fnt.user, n, h->d, points, loglike, (void*)h->stream);
+    if (rc)
+        return fail(h, MCMC_HIP_ERR_CALLBACK, "the callback of the function target returned %d", rc);
+    return MCMC_HIP_OK;
+}
+
+// mcmc_hip_step on a function target: per step  [accept of the previous trial +] proposal ->
+// the user's function on the trial points; a call ends with the accept of its last trial, so the
+// state is complete between calls.  Nothing here waits for the device.
+int step_function(mcmc_hip_ctx* h, int n_steps)
+{
+    auto& F = h->fnt;
+    const int d = h->d, W = h->W;
+    int rc = function_refusals(h);
+    if (rc) return rc;
+    HIP_TRY(h, F.points.resize((size_t)d * W));
+    HIP_TRY(h, F.lp_t.resize(W));
+    HIP_TRY(h, F.Ea.resize(W));
+    HIP_TRY(h, F.ll_t.resize(W));
+    const size_t dd = h->kb ? (size_t)mcmc::v_slab_big(d) : (size_t)mcmc::v_slab(d);
+    const int max_cyc = (int)std::max<size_t>(1, (64u << 20) / (sizeof(double) * dd * (size_t)h->G));
+    mcmc::FnWalkerArgs a{};
+    a.s.x = h->x.p; a.s.logpost = h->logpost.p; a.s.logprior = h->logprior.p;
+    a.s.loglike = h->loglike.p; a.s.weight = h->weight_i.p; a.s.prior_rej = h->prej.p;
+    a.s.burn_left = h->burn.p; a.s.n_accept = h->nacc.p; a.s.stuck = h->stuck.p;
+    a.s.accept_total = h->acc_total.p;
+    a.s.cblock = h->cblock.p; a.s.W = W; a.s.group_size = h->gs; a.s.n_modes = 0;
+    a.s.norm_mask = h->norm_mask; a.s.walker0 = h->cfg.walker_offset;
+    a.s.key0 = (uint32_t)h->cfg.seed; a.s.key1 = (uint32_t)(h->cfg.seed >> 32);
+    a.s.uniform_logp = h->uniform_logp; a.s.temperature = h->cfg.temperature;
+    a.s.max_tries = h->cfg.max_tries; a.s.cps = d; a.s.slab = (int)dd;
+    a.d = d; a.ld = h->kb ? mcmc::v_ld(d) : d;
+    for (int q = 0; q < 4; ++q) a.norm_mask4[q] = h->norm_mask4[q];
+    a.points = F.points.p; a.lp_t = F.lp_t.p; a.Ea = F.Ea.p; a.ll_t = F.ll_t.p; a.bad = F.bad.p;
+    int left = n_steps;
+    bool pending = false;   // a trial has been proposed and evaluated, not yet accepted / rejected
+    rc = MCMC_HIP_OK;
+    while (left > 0 && rc == MCMC_HIP_OK) {
+        const unsigned long long c0 = h->step / (unsigned long long)d;
+        const unsigned long long room = (c0 + (unsigned long long)max_cyc) * d - h->step;
+        const int n = (int)std::min<unsigned long long>((unsigned long long)left, room);
+        const int ncyc = (int)((h->step + (unsigned long long)n - 1) / d - c0 + 1);
+        {
+            Timed t(h, 1);
+            HIP_TRY(h, h->V.resize((size_t)h->G * ncyc * dd));
+            mcmc::BasisArgs b{};
+            b.T = h->dT.p; b.V = h->V.p;
+            b.group0 = h->cfg.walker_offset / (uint32_t)h->gs;
+            b.cycle0 = (uint32_t)c0;
+            b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
+            b.ncyc = ncyc;
+            if (h->kb) HIP_TRY(h, h->kb->basis(b, h->G, d, h->stream));
+            else HIP_TRY(h, h->k->basis(b, h->G, h->stream));
+        }
+        a.s.V = h->V.p; a.s.ncyc = ncyc;
+        for (int s = 0; s < n; ++s) {
+            a.s.step0 = h->step;
+            a.cyc = (int)(h->step / (unsigned long long)d - c0);
+            a.col = (int)(h->step % (unsigned long long)d);
+            {
+                Timed t(h, 0);
+                HIP_TRY(h, mcmc_hip_launch_fn_walker(&a, pending ? 1 : 0, 1, h->stream));
+            }
+            h->n_step_launches += 1;
+            // (the launch has settled the previous trial; a callback that fails drops THIS one:
+            // state and step counter stay as of the last completed step)
+            pending = false;
+            rc = function_call(h, W, F.points.p, F.ll_t.p);
+            if (rc) break;
+            pending = true;
+            h->step += 1;
+        }
+        left -= n;
+    }
+    if (pending) {
+        Timed t(h, 0);
+        HIP_TRY(h, mcmc_hip_launch_fn_walker(&a, 1, 0, h->stream));
+    }
+    if (g_noted_kernel) {
+        h->last_step_kernel = std::string(g_noted_kernel) + " (d=" + std::to_string(d) + ")";
+        g_noted_kernel = nullptr;
+    }
+    return rc;
+}
+
+// the flag of a function target that returned NaN or +inf inside the support (1 + walker, 0: none)
+int function_target_error(mcmc_hip_ctx* h, int bad)
+{
+    return fail(h, MCMC_HIP_ERR_TARGET,
+                "the function target returned NaN or +inf inside the prior support (walker %d): a "
+                "log-likelihood there must be finite or -inf", bad - 1);
 }
 
 }  // namespace
@@ -1138,6 +1262,8 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
         B.Ea.release(); B.psum.release(); B.epsum.release(); B.edelta.release(); B.etrial.release(); B.elp.release();
         B.echi2.release(); B.ecl.release(); B.eA.release();
     }
+    h->fnt.points.release(); h->fnt.lp_t.release(); h->fnt.Ea.release(); h->fnt.ll_t.release();
+    h->fnt.bad.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1213,6 +1339,42 @@ int mcmc_hip_set_target_gaussian(mcmc_hip_ctx* h, const double* mean, const doub
 int mcmc_hip_set_target_one(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
+    h->K = 0;
+    h->bg.on = false;
+    h->fnt.on = false;
+    h->mean.clear(); h->Linv.clear(); h->cnorm.clear(); h->weight.clear();
+    h->have_target = true;
+    ++h->dir_epoch;
+    h->have_state = false;
+    return upload_constants(h);
+}
+
+int mcmc_hip_set_target_function(mcmc_hip_ctx* h, mcmc_hip_loglike_fn fn, void* user)
+{
+    if (!h) return MCMC_HIP_ERR_ARG;
+    if (!fn) return fail(h, MCMC_HIP_ERR_ARG, "null argument");
+    if (h->d > kMaxDimBig)
+        return fail(h, MCMC_HIP_ERR_ARG, "a function target serves d <= %d, got d=%d", kMaxDimBig, h->d);
+    if (h->cfg.flags & MCMC_HIP_FLAG_INCREMENTAL)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target is evaluated from scratch (incremental evaluation, "
+                    "MCMC_HIP_FLAG_INCREMENTAL, is not served)");
+    if (h->cfg.flags & MCMC_HIP_FLAG_OWN_BASIS)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target needs the shared basis (own basis, MCMC_HIP_FLAG_OWN_BASIS / "
+                    "shared_basis: False, is not served)");
+    if (h->cfg.emit_capacity > 0)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target emits no rows on the device (emit_capacity > 0 / emit: chains is "
+                    "not served; use emit: snapshots)");
+    const int rc = function_refusals(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, h->fnt.bad.resize(1));
+    HIP_TRY(h, hipMemsetAsync(h->fnt.bad.p, 0, sizeof(int), h->stream));
+    h->fnt.fn = fn;
+    h->fnt.user = user;
+    h->fnt.on = true;
     h->K = 0;
     h->bg.on = false;
     h->mean.clear(); h->Linv.clear(); h->cnorm.clear(); h->weight.clear();
@@ -1381,6 +1543,7 @@ int mcmc_hip_set_target_binned_gaussian(mcmc_hip_ctx* h, int32_t n_bins, const i
     HIP_TRY(h, hipMemcpy(B.X.p, X, sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(B.dbins.p, bins, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice));
     B.on = true;
+    h->fnt.on = false;
     h->K = 0;
     h->mean.clear(); h->Linv.clear(); h->cnorm.clear(); h->weight.clear();
     h->have_target = true;
@@ -1642,12 +1805,26 @@ int mcmc_hip_evaluate(mcmc_hip_ctx* h, int32_t n, const double* x, double* logpr
     } else {
         HIP_TRY(h, h->k->evaluate(a, h->stream));
     }
+    if (h->fnt.on) {   // the log-prior is the `one` target's; the log-likelihood is the function's
+        const int rc = function_call(h, n, h->ex.p, h->ell.p);
+        if (rc) return rc;
+    }
     HIP_TRY(h, hipMemcpyAsync(logprior, h->elp.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(loglike, h->ell.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     if (a.derived)
         HIP_TRY(h, hipMemcpyAsync(derived, h->eder.p, sizeof(double) * n * Kd, hipMemcpyDeviceToHost,
                                   h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->fnt.on)
+        for (int w = 0; w < n; ++w) {
+            // (the likelihood is skipped outside the prior support, model.py:650-653: what the
+            // batched function returned there is ignored)
+            if (std::isinf(logprior[w])) loglike[w] = -INFINITY;
+            else if (std::isnan(loglike[w]) || loglike[w] == INFINITY)
+                return fail(h, MCMC_HIP_ERR_TARGET,
+                            "the function target returned NaN or +inf inside the prior support (point "
+                            "%d): a log-likelihood there must be finite or -inf", w);
+        }
     return MCMC_HIP_OK;
 }
 
@@ -1684,6 +1861,7 @@ int mcmc_hip_set_state(mcmc_hip_ctx* h, const double* x, int32_t* n_bad)
     if (h->nrows.p)
         HIP_TRY(h, hipMemcpyAsync(h->nrows.p, zeros.data(), sizeof(int) * W, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemsetAsync(h->stuck.p, 0, sizeof(int), s));
+    if (h->fnt.bad.p) HIP_TRY(h, hipMemsetAsync(h->fnt.bad.p, 0, sizeof(int), s));
     HIP_TRY(h, hipMemsetAsync(h->acc_total.p, 0, sizeof(unsigned long long), s));
     // a fresh start: no thinning remainders from an earlier run (the oracle's State starts at zero;
     // mcmc_hip_set_full_state leaves them alone -- mcmc_hip_set_thin_carry follows it)
@@ -1766,6 +1944,7 @@ int mcmc_hip_set_full_state(mcmc_hip_ctx* h, const double* x, const double* logp
     HIP_TRY(h, hipMemcpy(h->nacc.p, n_accept, sizeof(int64_t) * W, hipMemcpyHostToDevice));
     if (h->nrows.p) HIP_TRY(h, hipMemset(h->nrows.p, 0, sizeof(int) * W));
     HIP_TRY(h, hipMemset(h->stuck.p, 0, sizeof(int)));
+    if (h->fnt.bad.p) HIP_TRY(h, hipMemset(h->fnt.bad.p, 0, sizeof(int)));
     {
         unsigned long long tot = 0;
         for (size_t w = 0; w < W; ++w) tot += (unsigned long long)n_accept[w];
@@ -2367,6 +2546,7 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
     if (n_steps <= 0) return fail(h, MCMC_HIP_ERR_ARG, "n_steps must be > 0");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (h->bg.on) return step_binned(h, n_steps);
+    if (h->fnt.on) return step_function(h, n_steps);
     if (h->incremental && h->huge) return step_huge(h, n_steps);
     if (h->incremental) return step_incremental(h, n_steps);
     if (h->emit_thin > 1)
@@ -2533,6 +2713,11 @@ int mcmc_hip_sync(mcmc_hip_ctx* h)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->stream2) HIP_TRY(h, hipStreamSynchronize(h->stream2));   // directions computed ahead
     resolve_timing(h);
+    if (h->fnt.on) {
+        int bad = 0;
+        HIP_TRY(h, hipMemcpy(&bad, h->fnt.bad.p, sizeof(int), hipMemcpyDeviceToHost));
+        if (bad) return function_target_error(h, bad);
+    }
     int stuck = 0;
     HIP_TRY(h, hipMemcpy(&stuck, h->stuck.p, sizeof(int), hipMemcpyDeviceToHost));
     if (stuck)
@@ -2798,6 +2983,11 @@ int mcmc_hip_request_moments(mcmc_hip_ctx* h)
     // (mcmc.py:717-743 stops at once)
     HIP_TRY(h, hipMemcpyAsync(h->pin_mom + G * d + np + 1, h->stuck.p, sizeof(int),
                               hipMemcpyDeviceToHost, s));
+    // (a function target: its error flag in the other half of that word)
+    if (h->fnt.on)
+        HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<int*>(h->pin_mom + G * d + np + 1) + 1, h->fnt.bad.p,
+                                  sizeof(int), hipMemcpyDeviceToHost, s));
+    h->mom_fn = h->fnt.on;
     // (with the device-side checkpoint the accumulators are reset by ckpt_window_kernel, which
     // first files them in the ring: mcmc_hip_checkpoint_begin must follow)
     if (!h->ck.ring.p) HIP_TRY(h, hipMemsetAsync(h->gsum.p, 0, sizeof(double) * (G * d + np), s));
@@ -2831,6 +3021,11 @@ int mcmc_hip_fetch_moments(mcmc_hip_ctx* h, int64_t* n_snapshots, double* group_
         std::memcpy(&tot, h->pin_mom + G * d + np, sizeof tot);
         counters[0] = (int64_t)h->mom_step;
         counters[1] = (int64_t)tot;
+    }
+    if (h->mom_fn) {
+        int bad = 0;
+        std::memcpy(&bad, reinterpret_cast<const int*>(h->pin_mom + G * d + np + 1) + 1, sizeof bad);
+        if (bad) return function_target_error(h, bad);
     }
     int stuck = 0;
     std::memcpy(&stuck, h->pin_mom + G * d + np + 1, sizeof stuck);

@@ -18,6 +18,7 @@ c_int32_p = C.POINTER(C.c_int32)
 c_int64_p = C.POINTER(C.c_int64)
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOT_PD, ERR_STATE, ERR_STUCK = 0, -1, -2, -3, -4, -5
+ERR_TARGET, ERR_CALLBACK = -6, -7
 
 
 class EngineError(RuntimeError):
@@ -34,6 +35,16 @@ class NotPositiveDefinite(EngineError):
 
 class ChainStuck(EngineError):
     pass
+
+
+class TargetError(EngineError):
+    """A function target returned NaN or +inf inside the prior support (MCMC_HIP_ERR_TARGET)."""
+
+
+# mcmc_hip_loglike_fn: int fn(void* user, int32 n, int32 d, const double* points, double* loglike,
+# void* stream) -- the pointers as integers (the wrapper turns them into tensor views)
+LOGLIKE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                         C.c_void_p)
 
 
 class Config(C.Structure):
@@ -60,6 +71,7 @@ SYMBOLS = [
      [_H, C.c_int32, c_double_p, c_double_p, c_double_p]),
     ("mcmc_hip_set_target_gaussian", C.c_int, [_H, c_double_p, c_double_p, C.c_int32]),
     ("mcmc_hip_set_target_one", C.c_int, [_H]),
+    ("mcmc_hip_set_target_function", C.c_int, [_H, LOGLIKE_FN, C.c_void_p]),
     ("mcmc_hip_checkpoint_set_ring", C.c_int, [_H, C.c_int32, c_double_p, c_double_p, C.c_int32]),
     ("mcmc_hip_checkpoint_set_accepted", C.c_int, [_H, C.c_int64]),
     ("mcmc_hip_checkpoint_begin", C.c_int, [_H, C.c_int32, C.c_int64, C.c_double,
@@ -336,8 +348,19 @@ class Engine:
         if rc == OK:
             return
         msg = self._lib.mcmc_hip_last_error(self._h).decode()
-        cls = {ERR_NOT_PD: NotPositiveDefinite, ERR_STUCK: ChainStuck}.get(rc, EngineError)
+        cls = {ERR_NOT_PD: NotPositiveDefinite, ERR_STUCK: ChainStuck,
+               ERR_TARGET: TargetError}.get(rc, EngineError)
+        if rc == ERR_CALLBACK and self._fn_exc is not None:
+            # an exception cannot cross the C callback: the wrapper kept it, and it is the cause
+            exc, self._fn_exc = self._fn_exc, None
+            if not isinstance(exc, Exception):   # KeyboardInterrupt, SystemExit: not ours to wrap
+                raise exc
+            raise EngineError(rc, f"{msg}: the target function raised "
+                                  f"{type(exc).__name__}: {exc}") from exc
         raise cls(rc, msg)
+
+    _fn_exc = None
+    _fn_callback = None
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -423,6 +446,88 @@ class Engine:
 
     def set_target_one(self):
         self._check(self._lib.mcmc_hip_set_target_one(self._h))
+        self.K = 0
+
+    def set_target_function(self, fn, pass_out=False):
+        """Target kind `function` (mcmc_hip_set_target_function): the log-likelihood of a point is
+        what `fn` returns for it.
+
+        `fn(points)` receives a torch.float64 tensor (n, d) on the engine's device -- a VIEW of
+        the engine's buffer of trial points, sampled parameters in sampled order -- and returns
+        (n,) float64 log-likelihoods on that device.  It is called once per step with the trials
+        of all walkers, under the engine's stream (`torch.cuda.ExternalStream`): its operations
+        are stream-ordered with the step kernels and nothing synchronises with the host.
+
+        Rows outside the prior support are included; what it returns for them is ignored (NaN is
+        allowed there).  Inside the support -inf rejects the trial; NaN or +inf raise
+        `TargetError` at the next `sync` / `fetch_moments`.  An exception inside `fn` is re-raised
+        as the cause of the `EngineError` of the `step` / `evaluate` that called it; the engine
+        stays usable.
+
+        `pass_out=True`: `fn` is called as `fn(points, out)` with the engine's (n,) result buffer
+        as a second argument; a result returned from there is not copied.
+
+        `import torch` before the first Engine is created: PyTorch brings its own copy of the HIP
+        runtime, which the process must load first."""
+        if not callable(fn):
+            raise EngineError(ERR_ARG, f"set_target_function needs a callable, got {fn!r}")
+        import torch   # (only function targets need it)
+        dev = torch.device("cuda", int(self.cfg.device))
+        try:
+            stream = torch.cuda.ExternalStream(self.stream_handle(), device=dev)
+        except RuntimeError as e:
+            # PyTorch ships its own copy of the HIP runtime: loaded after libmcmc_hip.so has bound
+            # to the system's, the process holds two runtimes and PyTorch's finds no device
+            raise EngineError(ERR_DEVICE,
+                              f"PyTorch cannot use device {dev} in this process ({e}): `import torch` "
+                              "before the first Engine is created (before libmcmc_hip.so is loaded), so "
+                              "that both use one HIP runtime") from e
+        views = {}
+        pass_out = bool(pass_out)
+
+        class _View:   # __cuda_array_interface__ of n float64 at a device pointer: no copy
+            def __init__(self, ptr, shape):
+                self.__cuda_array_interface__ = {"shape": shape, "typestr": "<f8", "data": (ptr, False),
+                                                 "version": 2, "strides": None}
+
+        def view(ptr, shape):
+            key = (ptr, shape)
+            t = views.get(key)
+            if t is None:
+                if len(views) > 64:
+                    views.clear()
+                t = views[key] = torch.as_tensor(_View(ptr, shape), device=dev)
+            return t
+
+        def callback(_user, n, d, points, loglike, _stream):
+            try:
+                with torch.cuda.stream(stream):
+                    out_buf = view(loglike, (n,))
+                    pts = view(points, (n, d))
+                    out = fn(pts, out_buf) if pass_out else fn(pts)
+                    if not isinstance(out, torch.Tensor):
+                        raise TypeError("the target function must return a torch.Tensor, got "
+                                        f"{type(out).__name__}")
+                    if tuple(out.shape) != (n,):
+                        raise ValueError(f"the target function must return shape ({n},), got shape "
+                                         f"{tuple(out.shape)}")
+                    if out.dtype != torch.float64:
+                        raise TypeError("the target function must return dtype torch.float64, got "
+                                        f"dtype {out.dtype}")
+                    if out.device != dev:
+                        raise ValueError(f"the target function must return a tensor on device {dev}, "
+                                         f"got device {out.device}")
+                    if out.data_ptr() != loglike or not out.is_contiguous():
+                        out_buf.copy_(out)
+                return 0
+            except BaseException as e:   # (cannot cross ctypes: kept for _check, which re-raises
+                # a KeyboardInterrupt / SystemExit as it is)
+                self._fn_exc = e
+                return 1
+
+        cb = LOGLIKE_FN(callback)
+        self._check(self._lib.mcmc_hip_set_target_function(self._h, cb, None))
+        self._fn_callback = (cb, fn, stream)   # alive as long as the engine
         self.K = 0
 
     def derived_constants(self):

@@ -14,6 +14,8 @@ Reference behaviour mirrored here (paths relative to the reference checkout):
   reference pdf            cobaya/prior.py:866-961 (initial points), 963-985 (variances)
   gaussian_mixture         cobaya/likelihoods/gaussian_mixture/gaussian_mixture.py:45-163
   gaussian / one           cobaya/likelihoods/gaussian/gaussian.py:30-112 ; likelihoods/one/one.py
+  device_function          cobaya/likelihood.py:150-255 (LikelihoodExternalFunction), batched: the
+                           function maps an (n, d) device tensor of points to n log-likelihoods
 """
 from __future__ import annotations
 
@@ -119,7 +121,7 @@ class ProblemSpec:
     refs: list  # RefPdf per sampled parameter
     proposal: list  # `proposal` width or None
     like_name: str = "one"
-    like_kind: str = "one"  # one | gaussian_mixture | gaussian | planck_pliklite
+    like_kind: str = "one"  # one | gaussian_mixture | gaussian | planck_pliklite | device_function
     means: np.ndarray | None = None
     covs: np.ndarray | None = None
     weights: np.ndarray | None = None
@@ -132,6 +134,8 @@ class ProblemSpec:
     binned: object = None
     emulator: object = None
     calib_index: int = -1
+    # device_function: the batched callable (points (n, d) on the device -> (n,) log-likelihoods)
+    function: object = None
 
     @property
     def d(self):
@@ -139,7 +143,7 @@ class ProblemSpec:
 
     @property
     def n_modes(self):
-        return 0 if self.like_kind in ("one", "planck_pliklite") else len(self.means)
+        return 0 if self.like_kind in ("one", "planck_pliklite", "device_function") else len(self.means)
 
     # ----------------------------------------------------------------- prior facts
     def prior_variances(self):
@@ -275,6 +279,8 @@ class ProblemSpec:
             if c["kind"] == "planck_pliklite":
                 spec.binned, spec.emulator = c["binned"], c["emulator"]
                 spec.calib_index = c["calib_index"]
+            if c["kind"] == "device_function":
+                spec.function = c["function"]
             return spec
         # several likelihoods over disjoint parameter sets: the posterior is the product, i.e.
         # ONE mixture whose modes are all combinations of the components' modes, with
@@ -289,6 +295,10 @@ class ProblemSpec:
             if c["kind"] == "planck_pliklite":
                 raise UnsupportedModel(
                     f"likelihood '{c['name']}' (planck_pliklite) cannot be combined with others")
+            if c["kind"] == "device_function":
+                raise UnsupportedModel(
+                    f"likelihood '{c['name']}' (device_function) must be the only likelihood: it "
+                    "cannot be combined with others")
             if c["kind"] == "one" or not c["normalized"] or c["has_derived"]:
                 raise UnsupportedModel(
                     f"likelihood '{c['name']}': only normalized gaussian / gaussian_mixture "
@@ -336,6 +346,9 @@ class ProblemSpec:
             return cls._component(lname, "one", [], [], sampled, derived, single, speed=speed)
         if lclass in ("planckpliklite", "ttteeelitenative", "ttlitenative"):
             return cls._pliklite_component(lname, linfo, sampled, derived, speed)
+        if lclass == "devicefunction":
+            return cls._function_component(lname, linfo, inputs, in_prefix, sampled, derived,
+                                           single, speed)
         if lclass not in ("gaussianmixture", "gaussian"):
             raise UnsupportedModel(f"likelihood '{lname}' is not one of gaussian_mixture, "
                                    "gaussian, one, planck_pliklite")
@@ -357,6 +370,61 @@ class ProblemSpec:
                                    f"{sorted(linfo)}")
         return cls._component(lname, kind, list(inputs), list(outputs), sampled, derived,
                               single, speed=speed, **kw)
+
+    @staticmethod
+    def _function_component(lname, linfo, inputs, in_prefix, sampled, derived, single, speed):
+        """`device_function`: the batched counterpart of an external likelihood function
+        (likelihood.py:150-255).  `function` is a callable that maps a float64 device tensor of
+        points (n, d) -- the sampled parameters in sampled order -- to (n,) log-likelihoods on the
+        same device, or a "package.module:name" string resolved with importlib (YAML inputs,
+        resumed runs).  It is called with every trial point, the ones outside the prior support
+        included (their values are ignored).  It has no derived parameters and is the only
+        likelihood."""
+        linfo = dict(linfo)
+        fn = linfo.pop("function", None)
+        if isinstance(fn, str):
+            import importlib
+            mod, sep, attr = fn.partition(":")
+            if not sep or not mod or not attr:
+                raise UnsupportedModel(f"likelihood '{lname}': `function` given as a string must "
+                                       f"be 'package.module:name', got {fn!r}")
+            try:
+                obj = importlib.import_module(mod)
+                for part in attr.split("."):
+                    obj = getattr(obj, part)
+            except (ImportError, AttributeError) as e:
+                raise UnsupportedModel(f"likelihood '{lname}': `function` {fn!r} could not be "
+                                       f"resolved ({e})") from e
+            fn = obj
+        if not callable(fn):
+            raise UnsupportedModel(f"likelihood '{lname}': `function` must be a callable (or a "
+                                   f"'package.module:name' string), got {fn!r}")
+        if linfo:
+            raise UnsupportedModel(f"unknown options for likelihood '{lname}': {sorted(linfo)}")
+        # PyTorch now, before any engine exists: it ships its own copy of the HIP runtime, and the
+        # process must load that copy BEFORE libmcmc_hip.so binds to one -- the other way round
+        # the process holds two runtimes and PyTorch's finds no device
+        try:
+            import torch  # noqa: F401
+        except ImportError as e:
+            raise UnsupportedModel(f"likelihood '{lname}' (device_function) needs PyTorch: the "
+                                   f"function receives and returns torch tensors ({e})") from e
+        if derived:
+            raise UnsupportedModel(f"likelihood '{lname}' (device_function) has no derived "
+                                   f"parameters, but {list(derived)} were requested")
+        if not single:
+            raise UnsupportedModel(f"likelihood '{lname}' (device_function) must be the only "
+                                   "likelihood: it cannot be combined with others")
+        if not isinstance(inputs, (list, tuple)):
+            inputs = [p for p in sampled if p.startswith(in_prefix)]  # model.py:1169-1172
+        if list(inputs) != list(sampled):
+            raise UnsupportedModel(
+                f"likelihood '{lname}' takes {list(inputs)} but all sampled parameters "
+                f"{list(sampled)} must feed the likelihood, in sampled order")
+        return {"name": lname, "kind": "device_function", "idx": list(range(len(sampled))),
+                "means": None, "covs": None, "weights": None, "normalized": True,
+                "has_derived": False, "speed": float(speed if speed is not None else -1),
+                "function": fn}
 
     @staticmethod
     def _pliklite_component(lname, linfo, sampled, derived, speed):
@@ -631,7 +699,10 @@ class ProblemSpec:
             else:
                 raise UnsupportedModel(
                     f"likelihood '{lname}' ({type(like).__name__}) is not one of "
-                    "gaussian_mixture, gaussian, one")
+                    "gaussian_mixture, gaussian, one" +
+                    (" (an external likelihood function is served as a batched `device_function` "
+                     "through cobaya_amd.run, not hosted under cobaya.run)"
+                     if "LikelihoodExternalFunction" in mro else ""))
         if not comps:
             raise UnsupportedModel("no likelihood given (use `one` for prior-only sampling)")
         return spec._with_components(comps)
@@ -643,6 +714,8 @@ class ProblemSpec:
             engine.set_target_one()
         elif self.like_kind == "planck_pliklite":
             engine.set_target_binned_gaussian(self.binned, self.emulator, self.calib_index)
+        elif self.like_kind == "device_function":
+            engine.set_target_function(self.function)
         elif self.like_kind == "gaussian":
             engine.set_target_gaussian(self.means[0], self.covs[0], self.normalized)
         else:

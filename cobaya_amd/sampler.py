@@ -378,6 +378,11 @@ class EnsembleMCMC:
                     or self.emit != "snapshots" or not self.shared_basis or np.any(spec.periodic)):
                 self._fail("the planck_pliklite likelihood is sampled with one parameter block, "
                            "the shared basis, non-periodic priors and emit: snapshots")
+        if spec.like_kind == "device_function":
+            # the user's batched device function: every trial is evaluated from scratch, by it
+            # (function_kernels.hip: propose -> function -> accept)
+            can_inc = False
+            self._check_function(spec, d)
         if not self.shared_basis and (len(self.blocks) > 1 or self.oversampling_factors[0] != 1):
             self._fail("shared_basis: False serves a single parameter block without "
                        "oversampling or dragging")
@@ -564,6 +569,30 @@ class EnsembleMCMC:
         if why:
             self._fail("mcmc_hip samples d = %d > %d parameters with incremental evaluation of one "
                        "parameter block only: %s", d, self.MAX_DIM, why)
+
+    def _check_function(self, spec, d):
+        """A `device_function` likelihood is sampled from scratch with Metropolis steps of one
+        parameter block, the shared basis, non-periodic priors and emit: snapshots, up to d = 128.
+        Everything else is refused here, by the option to change, before the engine is created."""
+        why = None
+        if d > self.MAX_DIM:
+            why = "d = %d > %d parameters are not served" % (d, self.MAX_DIM)
+        elif self.drag:
+            why = "drag: True is not served"
+        elif len(self.blocks) > 1 or any(int(f) != 1 for f in self.oversampling_factors):
+            why = "parameter blocks / oversample_power / blocking are not served (one block only)"
+        elif np.any(spec.periodic):
+            why = "periodic parameters are not served (periodic: True of %s)" % (
+                [p for p, per in zip(spec.sampled, spec.periodic) if per],)
+        elif self.emit != "snapshots":
+            why = "emit: %s is not served (use emit: snapshots)" % self.emit
+        elif not self.shared_basis:
+            why = "shared_basis: False is not served"
+        elif self.evaluation == "incremental":
+            why = "evaluation: incremental is not served (use evaluation: full or auto)"
+        if why:
+            self._fail("mcmc_hip samples a device_function likelihood from scratch with Metropolis "
+                       "steps of one parameter block only: %s", why)
 
     def _init_device_checkpoint(self):
         """`device_checkpoint`: which part of the checkpoint runs on the device -- nothing (False),

@@ -37,7 +37,9 @@ enum {
     MCMC_HIP_ERR_DEVICE = -2,    /* HIP runtime error or no usable gfx950 device */
     MCMC_HIP_ERR_NOT_PD = -3,    /* matrix not symmetric positive definite */
     MCMC_HIP_ERR_STATE = -4,     /* call order violated (e.g. step before set_state) */
-    MCMC_HIP_ERR_STUCK = -5      /* a walker exceeded max_tries (mcmc.py:717-743) */
+    MCMC_HIP_ERR_STUCK = -5,     /* a walker exceeded max_tries (mcmc.py:717-743) */
+    MCMC_HIP_ERR_TARGET = -6,    /* a function target returned NaN or +inf inside the prior support */
+    MCMC_HIP_ERR_CALLBACK = -7   /* the callback of a function target returned non-zero */
 };
 
 /* Options fixed at creation.  Mirrors the attributes cobaya/samplers/mcmc/mcmc.py:111-271
@@ -114,6 +116,36 @@ MCMC_HIP_API int mcmc_hip_set_target_gaussian(mcmc_hip_ctx* h, const double* mea
                                  int32_t normalized);
 /* likelihoods/one/one.py:27-29: loglike = 0 (prior-only sampling) */
 MCMC_HIP_API int mcmc_hip_set_target_one(mcmc_hip_ctx* h);
+
+/* Target kind `function` (the batched counterpart of LikelihoodExternalFunction,
+ * cobaya/likelihood.py:150-255): the log-likelihood of a point is whatever `fn` computes for it.
+ *   points   device memory, [n][d] row-major (point-major, as mcmc_hip_evaluate's x)
+ *   loglike  device memory, [n]: fn leaves the log-likelihood of point k in loglike[k]
+ *   stream   the engine's hipStream_t (mcmc_hip_stream_handle)
+ * fn must only QUEUE work -- kernels, copies -- on `stream`, or on streams it orders against
+ * `stream` with events on both sides; it must not synchronise the device and returns 0 on success.
+ * It is called once per Metropolis step with the trial points of ALL n_walkers walkers, the rows
+ * outside the prior support included: what it returns for those is ignored (NaN is allowed there;
+ * the reference skips the likelihood outside the support, model.py:650-653 -- a batched call
+ * cannot).  Inside the support -inf is an ordinary rejection; NaN or +inf is an error of the
+ * target: the id of the first such walker is kept and the next mcmc_hip_sync or
+ * mcmc_hip_fetch_moments returns MCMC_HIP_ERR_TARGET (mcmc_hip_evaluate returns it at once).
+ * If fn returns non-zero, mcmc_hip_step / mcmc_hip_evaluate return MCMC_HIP_ERR_CALLBACK: the
+ * pending trial is dropped, state and step counter stay as of the last completed step, and the
+ * context stays usable.
+ * Per step ("Function targets"): variates of the un-paired stream, trial
+ * t = fma(r, v, x) along the group's shared direction, support test and log-prior as under
+ * mcmc_hip_set_target_one, loglike = fn(t), the Metropolis rule and bookkeeping of every other
+ * target; one launch accepts step s and proposes step s + 1 (function_kernels.hip).
+ * Served: 1 <= d <= 128, evaluation from scratch, the shared basis, one parameter block, Metropolis
+ * steps, non-periodic priors, emit_capacity 0.  Refused with MCMC_HIP_ERR_ARG here or by
+ * mcmc_hip_step: MCMC_HIP_FLAG_INCREMENTAL, MCMC_HIP_FLAG_OWN_BASIS, parameter blocks /
+ * oversampling / dragging (mcmc_hip_set_blocking), periodic parameters, emit_capacity > 0, d > 128.
+ * Moments, checkpoints, the bounds ring, get / set_full_state, walker_offset, temperature, burn-in
+ * and timing work as for every target. */
+typedef int (*mcmc_hip_loglike_fn)(void* user, int32_t n, int32_t d, const double* points,
+                                   double* loglike, void* stream);
+MCMC_HIP_API int mcmc_hip_set_target_function(mcmc_hip_ctx* h, mcmc_hip_loglike_fn fn, void* user);
 
 /* PlanckPlikLite.init_params (cobaya/likelihoods/base_classes/planck_pliklite.py:32-141) for the
  * used bins, + the Cl provider of `logp` (planck_pliklite.py:170-178) as a LINEAR emulator:
@@ -200,7 +232,8 @@ MCMC_HIP_API int mcmc_hip_set_full_state(mcmc_hip_ctx* h, const double* x, const
 /* n_steps iterations of MCMC.get_new_sample_metropolis (mcmc.py:545-562) for every walker,
  * asynchronously on the engine's stream; generates the Haar bases the steps need. */
 MCMC_HIP_API int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps);
-/* wait for queued work; returns MCMC_HIP_ERR_STUCK if a walker tripped max_tries */
+/* wait for queued work; returns MCMC_HIP_ERR_STUCK if a walker tripped max_tries, and
+ * MCMC_HIP_ERR_TARGET if a function target returned NaN or +inf inside the prior support */
 MCMC_HIP_API int mcmc_hip_sync(mcmc_hip_ctx* h);
 
 /* counters[0] steps per walker so far, [1] accepted steps summed over walkers (n_steps_raw /
