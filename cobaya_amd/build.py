@@ -1,8 +1,10 @@
 """Builds libmcmc_hip.so (hipcc, gfx950 only) in-tree under cobaya_amd/csrc/.
 
-One object per compiled dimension (walker_kernels.hip with -DMCMC_D=<d>), compiled in
-parallel, plus capi.hip; linked into cobaya_amd/csrc/libmcmc_hip.so.  hipcc cross-compiles
-without a GPU, so this runs in the CPU-only build container.
+One object per compiled dimension (walker_kernels.hip with -DMCMC_D=<d>) and per entry of
+translation_units(), compiled in parallel; linked into cobaya_amd/csrc/libmcmc_hip.so.  An object
+is rebuilt when a file the compiler read for it last time (its -MD dependency list), the flags or
+its defines change.  hipcc cross-compiles without a GPU, so this runs in the CPU-only build
+container.
 
     python -m cobaya_amd.build            # all dimensions 1..32
     MCMC_HIP_DIMS=2,3,30 python -m cobaya_amd.build   # quick developer build
@@ -42,27 +44,86 @@ def hipcc() -> str:
     return exe
 
 
+_file_digests = {}
+
+
+def _file_digest(path):
+    """sha256 of a file's contents (None if it is gone), read once per build."""
+    if path not in _file_digests:
+        try:
+            with open(path, "rb") as f:
+                _file_digests[path] = hashlib.sha256(f.read()).hexdigest()
+        except OSError:
+            _file_digests[path] = None
+    return _file_digests[path]
+
+
 def _digest(paths, extra=""):
     h = hashlib.sha256(extra.encode())
     for p in paths:
-        with open(p, "rb") as f:
-            h.update(f.read())
+        h.update(str(_file_digest(p)).encode())
     return h.hexdigest()[:16]
 
 
-def _compile(src, obj, defines, stamp):
-    stamp_file = obj + ".stamp"
-    if os.path.exists(obj) and os.path.exists(stamp_file):
+def _dependencies(depfile):
+    """The files the compiler read for an object: the prerequisites its -MD file lists."""
+    with open(depfile) as f:
+        text = f.read().replace("\\\n", " ")
+    return [w for w in text.split(":", 1)[1].split() if w]
+
+
+def _compile(src, obj, defines):
+    """Compiles src -> obj unless the last successful compile saw the same inputs: the source
+    and every header the compiler itself listed then (obj.d), the flags and the defines.  No
+    dependency list (never built, or cleaned): compile."""
+    stamp_file, depfile = obj + ".stamp", obj + ".d"
+    extra = " ".join([*FLAGS, *defines])
+    if os.path.exists(obj) and os.path.exists(stamp_file) and os.path.exists(depfile):
         with open(stamp_file) as f:
-            if f.read() == stamp:
+            if f.read() == _digest(_dependencies(depfile), extra):
                 return False
-    cmd = [hipcc(), *FLAGS, *defines, "-c", src, "-o", obj]
+    for stale in (stamp_file, depfile):
+        if os.path.exists(stale):
+            os.remove(stale)
+    cmd = [hipcc(), *FLAGS, *defines, "-MD", "-MF", depfile, "-c", src, "-o", obj]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError(f"hipcc failed: {' '.join(cmd)}\n{res.stdout}\n{res.stderr}")
     with open(stamp_file, "w") as f:
-        f.write(stamp)
+        f.write(_digest(_dependencies(depfile), extra))
     return True
+
+
+def translation_units(dims, big=True):
+    """(source, object name, defines) of every object of the library, in link order."""
+    tus = [("walker_kernels.hip", f"walker_d{d}", [f"-DMCMC_D={d}"]) for d in dims]
+    if big:   # 32 < d <= 56: the two-wave step kernel; the padded sizes of the d > 32 kernels
+        tus += [("walker_kernels.hip", f"walker_d{d}", [f"-DMCMC_D={d}"]) for d in PAIR_DIMS]
+        tus += [("walker_kernels_big.hip", f"walker_big{dp}", [f"-DMCMC_DP={dp}"]) for dp in BIG_DPS]
+    tus += [("blocked_kernels.hip", "blocked", []),
+            ("general_kernels.hip", "general", []),
+            ("pliklite_kernels.hip", "pliklite", []),
+            ("checkpoint_kernels.hip", "checkpoint", []),
+            ("comm.hip", "comm", [])]   # the RCCL communicator (bound at run time)
+    tus += [("incremental_kernels.hip", f"incremental_{lo}", [f"-DMCMC_DQ_LO={lo}", f"-DMCMC_DQ_HI={hi}"])
+            for lo, hi in INC_DQ_RANGES]
+    # the EMIT instantiations of step_inc_kernel (emit: chains)
+    tus += [("incremental_kernels.hip", f"incremental_emit_{lo}",
+             ["-DMCMC_INC_EMIT_TU", f"-DMCMC_DQ_LO={lo}", f"-DMCMC_DQ_HI={hi}"]) for lo, hi in INC_DQ_RANGES]
+    # the general incremental kernel: the LDS kernel + KM = 4 | KM = 8 | KM = 16 register planes
+    tus += [("incremental_any.hip", f"incremental_any_{part}", [f"-DANY_PART={part}"]) for part in (0, 1, 2)]
+    # two lanes per walker (round 6)
+    tus += [("incremental_duo.hip", f"incremental_duo_{lo}", [f"-DMCMC_DUO_DQ_LO={lo}", f"-DMCMC_DUO_DQ_HI={hi}"])
+            for lo, hi in DUO_DQ_RANGES]
+    tus += [("huge_kernels.hip", "huge", []),        # 128 < d <= 256 (run-time d)
+            ("function_kernels.hip", "function", []),   # function targets (the user's batched device function)
+            ("host_linalg.cpp", "host_linalg", []),  # the host side: the C ABI, split by job
+            ("capi.hip", "capi", []),
+            ("capi_targets.hip", "capi_targets", []),
+            ("capi_incremental.hip", "capi_incremental", []),
+            ("capi_rows.hip", "capi_rows", []),
+            ("capi_checkpoint.hip", "capi_checkpoint", [])]
+    return tus
 
 
 def selected_dims():
@@ -79,69 +140,9 @@ def build(dims=None, jobs=None, verbose=True):
     if extra:
         FLAGS.extend(f for f in extra if f not in FLAGS)
     os.makedirs(OBJ, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in ("det_math.h", "kernels.h", "short_log_table.h")]
-    root_hdr = os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "mcmc_hip.h")
-    wk = os.path.join(CSRC, "walker_kernels.hip")
-    capi = os.path.join(CSRC, "capi.hip")
-    tasks = []
-    for d in dims:
-        stamp = _digest([wk] + hdrs, extra=f"{d}|{' '.join(FLAGS)}")
-        tasks.append((wk, os.path.join(OBJ, f"walker_d{d}.o"), [f"-DMCMC_D={d}"], stamp))
-    big = os.path.join(CSRC, "walker_kernels_big.hip")
-    big_dps = [] if os.environ.get("MCMC_HIP_NO_BIG") else BIG_DPS
-    for d in ([] if os.environ.get("MCMC_HIP_NO_BIG") else PAIR_DIMS):
-        stamp = _digest([wk] + hdrs, extra=f"{d}|{' '.join(FLAGS)}")
-        tasks.append((wk, os.path.join(OBJ, f"walker_d{d}.o"), [f"-DMCMC_D={d}"], stamp))
-    for dp in big_dps:
-        stamp = _digest([big] + hdrs, extra=f"big{dp}|{' '.join(FLAGS)}")
-        tasks.append((big, os.path.join(OBJ, f"walker_big{dp}.o"), [f"-DMCMC_DP={dp}"], stamp))
-    blocked = os.path.join(CSRC, "blocked_kernels.hip")
-    tasks.append((blocked, os.path.join(OBJ, "blocked.o"), [],
-                  _digest([blocked] + hdrs, extra=" ".join(FLAGS))))
-    general = os.path.join(CSRC, "general_kernels.hip")
-    tasks.append((general, os.path.join(OBJ, "general.o"), [],
-                  _digest([general] + hdrs, extra=" ".join(FLAGS))))
-    pl = os.path.join(CSRC, "pliklite_kernels.hip")
-    pl_hdr = os.path.join(CSRC, "pliklite_args.h")
-    tasks.append((pl, os.path.join(OBJ, "pliklite.o"), [],
-                  _digest([pl, pl_hdr] + hdrs, extra=" ".join(FLAGS))))
-    ck = os.path.join(CSRC, "checkpoint_kernels.hip")
-    ck_hdr = os.path.join(CSRC, "checkpoint_args.h")
-    tasks.append((ck, os.path.join(OBJ, "checkpoint.o"), [],
-                  _digest([ck, ck_hdr], extra=" ".join(FLAGS))))
-    comm = os.path.join(CSRC, "comm.hip")   # the RCCL communicator (bound at run time)
-    comm_hdr = os.path.join(CSRC, "comm.h")
-    tasks.append((comm, os.path.join(OBJ, "comm.o"), [],
-                  _digest([comm, comm_hdr, root_hdr], extra=" ".join(FLAGS))))
-    inc = os.path.join(CSRC, "incremental_kernels.hip")
-    inc_hdr = os.path.join(CSRC, "incremental_common.h")
-    for lo_, hi_ in INC_DQ_RANGES:
-        tasks.append((inc, os.path.join(OBJ, f"incremental_{lo_}.o"),
-                      [f"-DMCMC_DQ_LO={lo_}", f"-DMCMC_DQ_HI={hi_}"],
-                      _digest([inc, inc_hdr] + hdrs, extra=f"inc{lo_}-{hi_}|{' '.join(FLAGS)}")))
-    for lo_, hi_ in INC_DQ_RANGES:   # the EMIT instantiations of step_inc_kernel (emit: chains)
-        tasks.append((inc, os.path.join(OBJ, f"incremental_emit_{lo_}.o"),
-                      ["-DMCMC_INC_EMIT_TU", f"-DMCMC_DQ_LO={lo_}", f"-DMCMC_DQ_HI={hi_}"],
-                      _digest([inc, inc_hdr] + hdrs, extra=f"incemit{lo_}-{hi_}|{' '.join(FLAGS)}")))
-    anyk = os.path.join(CSRC, "incremental_any.hip")   # the general incremental kernel
-    for part in (0, 1, 2):   # the LDS kernel + KM = 4 | KM = 8 | KM = 16 register planes
-        tasks.append((anyk, os.path.join(OBJ, f"incremental_any_{part}.o"), [f"-DANY_PART={part}"],
-                      _digest([anyk, inc_hdr] + hdrs, extra=f"any{part}|{' '.join(FLAGS)}")))
-    duo = os.path.join(CSRC, "incremental_duo.hip")   # two lanes per walker (round 6)
-    for lo_, hi_ in DUO_DQ_RANGES:
-        tasks.append((duo, os.path.join(OBJ, f"incremental_duo_{lo_}.o"),
-                      [f"-DMCMC_DUO_DQ_LO={lo_}", f"-DMCMC_DUO_DQ_HI={hi_}"],
-                      _digest([duo, inc_hdr] + hdrs, extra=f"duo{lo_}-{hi_}|{' '.join(FLAGS)}")))
-    huge = os.path.join(CSRC, "huge_kernels.hip")   # 128 < d <= 256 (run-time d)
-    huge_hdr = os.path.join(CSRC, "huge_args.h")
-    tasks.append((huge, os.path.join(OBJ, "huge.o"), [],
-                  _digest([huge, huge_hdr] + hdrs, extra=" ".join(FLAGS))))
-    fnk = os.path.join(CSRC, "function_kernels.hip")   # function targets (the user's batched device function)
-    fn_hdr = os.path.join(CSRC, "function_args.h")
-    tasks.append((fnk, os.path.join(OBJ, "function.o"), [],
-                  _digest([fnk, fn_hdr] + hdrs, extra=" ".join(FLAGS))))
-    tasks.append((capi, os.path.join(OBJ, "capi.o"), [],
-                  _digest([capi, root_hdr, pl_hdr, ck_hdr, comm_hdr, huge_hdr, fn_hdr] + hdrs, extra=" ".join(FLAGS))))
+    _file_digests.clear()
+    tasks = [(os.path.join(CSRC, src), os.path.join(OBJ, name + ".o"), defines)
+             for src, name, defines in translation_units(dims, big=not os.environ.get("MCMC_HIP_NO_BIG"))]
     jobs = jobs or min(len(tasks), os.cpu_count() or 4)
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         rebuilt = list(ex.map(lambda t: _compile(*t), tasks))

@@ -1,0 +1,540 @@
+// libmcmc_hip.so: the binned Gaussian target (pliklite_kernels.hip) and function targets
+// (function_kernels.hip) -- their setters, evaluation and steppers.
+#include "ctx.h"
+#include "host_linalg.h"
+
+namespace {
+
+// ------------------------------------------------------------------ binned Gaussian target
+// chain of the chi2 sum that row tile R of NT joins (oracle: binned_class): its position in its
+// group of eight tiles, the groups counted down from the last tile.  pl_fused_kernel gives the
+// tile at a position to one wave per pair of walker tiles; pl_chi2_kernel (explicit points) gives
+// wave q the tiles of class q.
+inline int binned_shift(int NT) { return (8 - NT % 8) % 8; }
+inline int binned_class(int R, int NT) { return (R + binned_shift(NT)) & 7; }
+
+// the 32 partial sums of chi2 per walker of the residuals held in `delta` (n walkers, a multiple
+// of 64) -> psum[32][n]; chi2 (may be null): their combination, one value per walker
+int binned_chi2(mcmc_hip_ctx* h, const double* delta, double* psum, double* chi2, int n)
+{
+    auto& B = h->bg;
+    mcmc::PlChi2Args c{};
+    c.delta = delta; c.Astream = B.Astream.p; c.psum = psum;
+    std::memcpy(c.tile_off, B.tile_off, sizeof c.tile_off);
+    std::memcpy(c.nk, B.nk, sizeof c.nk);
+    c.KT = B.KT; c.ntw = B.ntw; c.n_walkers = n; c.n_sets = n / 64;
+    HIP_TRY(h, mcmc_hip_launch_pl_chi2(&c, h->stream));
+    if (chi2) HIP_TRY(h, mcmc_hip_launch_pl_combine(psum, chi2, n, h->stream));
+    return MCMC_HIP_OK;
+}
+
+int binned_residual(mcmc_hip_ctx* h, const double* trial, double* delta, int n)
+{
+    auto& B = h->bg;
+    // MCMC_HIP_PL_SCALAR_RESIDUAL (developer switch): the lane-per-walker kernel of round 3
+    static const bool scalar = getenv("MCMC_HIP_PL_SCALAR_RESIDUAL") != nullptr;
+    if (!scalar) {
+        mcmc::PlResidualMfmaArgs m{};
+        m.trial = trial; m.theta0 = B.theta0.p; m.bjs = B.bjs.p; m.es = B.es.p; m.delta = delta;
+        m.W = n; m.KT = B.KT; m.n_lin = B.n_lin; m.np = (B.n_lin + 7) / 8; m.calib = B.calib;
+        m.n_tiles = (B.KT + 3) / 4;
+        HIP_TRY(h, mcmc_hip_launch_pl_residual_mfma(&m, h->stream));
+        return MCMC_HIP_OK;
+    }
+    mcmc::PlResidualArgs r{};
+    r.trial = trial; r.theta0 = B.theta0.p; r.resp = B.resp.p; r.delta = delta;
+    r.W = n; r.n_bins = B.n_bins; r.KT = B.KT; r.n_lin = B.n_lin; r.nlp = B.nlp; r.calib = B.calib;
+    HIP_TRY(h, mcmc_hip_launch_pl_residual(&r, h->stream));
+    return MCMC_HIP_OK;
+}
+
+}  // namespace
+
+// Model.logposterior for n points on the binned target (mcmc_hip_evaluate)
+int evaluate_binned_points(mcmc_hip_ctx* h, int n, const double* x, double* logprior, double* loglike)
+{
+    auto& B = h->bg;
+    const size_t d = h->d, np = ((size_t)n + 63) & ~(size_t)63;
+    std::vector<double> t(d * np);
+    for (size_t w = 0; w < np; ++w)
+        for (size_t i = 0; i < d; ++i) t[i * np + w] = x[(w < (size_t)n ? w : 0) * d + i];
+    HIP_TRY(h, B.etrial.resize(d * np));
+    HIP_TRY(h, B.elp.resize(np));
+    HIP_TRY(h, B.echi2.resize(np));
+    HIP_TRY(h, B.edelta.resize((np / 64) * (size_t)B.KT * 256 + (size_t)mcmc::kPlPad * 256));
+    HIP_TRY(h, hipMemcpyAsync(B.etrial.p, t.data(), sizeof(double) * d * np, hipMemcpyHostToDevice,
+                              h->stream));
+    HIP_TRY(h, mcmc_hip_launch_pl_prior(B.etrial.p, (int)np, (int)d, h->cblock.p, h->norm_mask,
+                                        h->uniform_logp, B.elp.p, h->stream));
+    int rc = binned_residual(h, B.etrial.p, B.edelta.p, (int)np);
+    if (rc) return rc;
+    HIP_TRY(h, B.epsum.resize(32 * np));
+    rc = binned_chi2(h, B.edelta.p, B.epsum.p, B.echi2.p, (int)np);
+    if (rc) return rc;
+    std::vector<double> c2(np), lp(np);
+    HIP_TRY(h, hipMemcpyAsync(lp.data(), B.elp.p, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(c2.data(), B.echi2.p, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int w = 0; w < n; ++w) {
+        logprior[w] = lp[w];
+        // (the likelihood is skipped outside the prior support, model.py:650-653)
+        loglike[w] = std::isinf(lp[w]) ? -INFINITY : -0.5 * c2[w];
+    }
+    return MCMC_HIP_OK;
+}
+
+// mcmc_hip_step on the binned target: per step  [accept of the previous trial +] proposal ->
+// residuals -> chi2 on the matrix cores; a call ends with the accept of its last trial, so the
+// state is complete between calls.
+int step_binned(mcmc_hip_ctx* h, int n_steps)
+{
+    auto& B = h->bg;
+    const int d = h->d, W = h->W;
+    if (h->blocked || h->drag_last_slow >= 0 || h->own_basis || h->cfg.emit_capacity > 0 || h->any_periodic)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "the binned Gaussian target serves one parameter block, the shared basis, "
+                    "non-periodic priors and emit_capacity 0");
+    HIP_TRY(h, B.trial.resize((size_t)d * W));
+    HIP_TRY(h, B.lp_t.resize(W));
+    HIP_TRY(h, B.Ea.resize(W));
+    HIP_TRY(h, B.psum.resize((size_t)32 * W));
+    // MCMC_HIP_PL_UNFUSED (developer switch): residuals and chi2 as two launches (round 3)
+    static const bool unfused = getenv("MCMC_HIP_PL_UNFUSED") != nullptr;
+    if (unfused)    // (fused: delta lives in LDS, 323 MB of HBM less at 65 536 walkers)
+        HIP_TRY(h, B.delta.resize(((size_t)W / 64) * (size_t)B.KT * 256 + (size_t)mcmc::kPlPad * 256));
+    const size_t dd = (size_t)mcmc::v_slab(d);
+    const int max_cyc = (int)std::max<size_t>(1, (64u << 20) / (sizeof(double) * dd * (size_t)h->G));
+    mcmc::PlWalkerArgs a{};
+    a.s.x = h->x.p; a.s.logpost = h->logpost.p; a.s.logprior = h->logprior.p;
+    a.s.loglike = h->loglike.p; a.s.weight = h->weight_i.p; a.s.prior_rej = h->prej.p;
+    a.s.burn_left = h->burn.p; a.s.n_accept = h->nacc.p; a.s.stuck = h->stuck.p;
+    a.s.accept_total = h->acc_total.p;
+    a.s.cblock = h->cblock.p; a.s.W = W; a.s.group_size = h->gs; a.s.n_modes = 0;
+    a.s.norm_mask = h->norm_mask; a.s.walker0 = h->cfg.walker_offset;
+    a.s.key0 = (uint32_t)h->cfg.seed; a.s.key1 = (uint32_t)(h->cfg.seed >> 32);
+    a.s.uniform_logp = h->uniform_logp; a.s.temperature = h->cfg.temperature;
+    a.s.max_tries = h->cfg.max_tries; a.s.cps = d; a.s.slab = (int)dd;
+    a.d = d; a.trial = B.trial.p; a.lp_t = B.lp_t.p; a.Ea = B.Ea.p; a.psum_t = B.psum.p;
+    int left = n_steps;
+    bool pending = false;   // a trial has been proposed and evaluated, not yet accepted / rejected
+    while (left > 0) {
+        const unsigned long long c0 = h->step / (unsigned long long)d;
+        const unsigned long long room = (c0 + (unsigned long long)max_cyc) * d - h->step;
+        const int n = (int)std::min<unsigned long long>((unsigned long long)left, room);
+        const int ncyc = (int)((h->step + (unsigned long long)n - 1) / d - c0 + 1);
+        {
+            Timed t(h, 1);
+            HIP_TRY(h, h->V.resize((size_t)h->G * ncyc * dd));
+            mcmc::BasisArgs b{};
+            b.T = h->dT.p; b.V = h->V.p;
+            b.group0 = h->cfg.walker_offset / (uint32_t)h->gs;
+            b.cycle0 = (uint32_t)c0;
+            b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
+            b.ncyc = ncyc;
+            HIP_TRY(h, h->k->basis(b, h->G, h->stream));
+        }
+        a.s.V = h->V.p; a.s.ncyc = ncyc;
+        for (int s = 0; s < n; ++s) {
+            a.s.step0 = h->step;
+            a.cyc = (int)(h->step / (unsigned long long)d - c0);
+            a.col = (int)(h->step % (unsigned long long)d);
+            {
+                Timed t(h, 3);
+                HIP_TRY(h, mcmc_hip_launch_pl_walker(&a, pending ? 1 : 0, 1, h->stream));
+            }
+            if (unfused) {
+                {
+                    Timed t(h, 4);
+                    const int rc = binned_residual(h, B.trial.p, B.delta.p, W);
+                    if (rc) return rc;
+                }
+                Timed t(h, 5);
+                const int rc = binned_chi2(h, B.delta.p, B.psum.p, nullptr, W);
+                if (rc) return rc;
+            } else {
+                Timed t(h, 5);
+                mcmc::PlFusedArgs f{};
+                f.trial = B.trial.p; f.theta0 = B.theta0.p; f.bjs = B.bjs.p; f.es = B.es.p;
+                f.Astream = B.Afused.p; f.psum = B.psum.p;
+                std::memcpy(f.a_off, B.f_off, sizeof f.a_off);
+                std::memcpy(f.a_pairs, B.f_pairs, sizeof f.a_pairs);
+                f.W = W; f.KT = B.KT; f.n_lin = B.n_lin; f.np = (B.n_lin + 7) / 8; f.calib = B.calib;
+                f.n_tiles = (B.KT + 3) / 4; f.shift = B.f_shift; f.ng = B.f_ng; f.n_sets = W / 64;
+                HIP_TRY(h, mcmc_hip_launch_pl_fused(&f, h->stream));
+            }
+            h->n_step_launches += 1;
+            pending = true;
+            h->step += 1;
+        }
+        left -= n;
+    }
+    if (pending) {
+        Timed t(h, 3);
+        HIP_TRY(h, mcmc_hip_launch_pl_walker(&a, 1, 0, h->stream));
+    }
+    take_noted_kernel(h, "n_bins", B.n_bins);
+    return MCMC_HIP_OK;
+}
+
+namespace {
+
+// ------------------------------------------------------------------ function target
+// what may be set before or after the target: checked by mcmc_hip_set_target_function and again by
+// every mcmc_hip_step
+int function_refusals(mcmc_hip_ctx* h)
+{
+    if (h->blocked || h->drag_last_slow >= 0)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target serves one parameter block with Metropolis steps (parameter "
+                    "blocks, oversampling and dragging are not served)");
+    if (h->any_periodic)
+        return fail(h, MCMC_HIP_ERR_ARG, "a function target does not serve periodic parameters");
+    return MCMC_HIP_OK;
+}
+
+}  // namespace
+
+int function_call(mcmc_hip_ctx* h, int n, const double* points, double* loglike)
+{
+    const int rc = h->fnt.fn(h->fnt.user, n, h->d, points, loglike, (void*)h->stream);
+    if (rc)
+        return fail(h, MCMC_HIP_ERR_CALLBACK, "the callback of the function target returned %d", rc);
+    return MCMC_HIP_OK;
+}
+
+// mcmc_hip_step on a function target: per step  [accept of the previous trial +] proposal ->
+// the user's function on the trial points; a call ends with the accept of its last trial, so the
+// state is complete between calls.  Nothing here waits for the device.
+int step_function(mcmc_hip_ctx* h, int n_steps)
+{
+    auto& F = h->fnt;
+    const int d = h->d, W = h->W;
+    int rc = function_refusals(h);
+    if (rc) return rc;
+    HIP_TRY(h, F.points.resize((size_t)d * W));
+    HIP_TRY(h, F.lp_t.resize(W));
+    HIP_TRY(h, F.Ea.resize(W));
+    HIP_TRY(h, F.ll_t.resize(W));
+    const size_t dd = h->kb ? (size_t)mcmc::v_slab_big(d) : (size_t)mcmc::v_slab(d);
+    const int max_cyc = (int)std::max<size_t>(1, (64u << 20) / (sizeof(double) * dd * (size_t)h->G));
+    mcmc::FnWalkerArgs a{};
+    a.s.x = h->x.p; a.s.logpost = h->logpost.p; a.s.logprior = h->logprior.p;
+    a.s.loglike = h->loglike.p; a.s.weight = h->weight_i.p; a.s.prior_rej = h->prej.p;
+    a.s.burn_left = h->burn.p; a.s.n_accept = h->nacc.p; a.s.stuck = h->stuck.p;
+    a.s.accept_total = h->acc_total.p;
+    a.s.cblock = h->cblock.p; a.s.W = W; a.s.group_size = h->gs; a.s.n_modes = 0;
+    a.s.norm_mask = h->norm_mask; a.s.walker0 = h->cfg.walker_offset;
+    a.s.key0 = (uint32_t)h->cfg.seed; a.s.key1 = (uint32_t)(h->cfg.seed >> 32);
+    a.s.uniform_logp = h->uniform_logp; a.s.temperature = h->cfg.temperature;
+    a.s.max_tries = h->cfg.max_tries; a.s.cps = d; a.s.slab = (int)dd;
+    a.d = d; a.ld = h->kb ? mcmc::v_ld(d) : d;
+    for (int q = 0; q < 4; ++q) a.norm_mask4[q] = h->norm_mask4[q];
+    a.points = F.points.p; a.lp_t = F.lp_t.p; a.Ea = F.Ea.p; a.ll_t = F.ll_t.p; a.bad = F.bad.p;
+    int left = n_steps;
+    bool pending = false;   // a trial has been proposed and evaluated, not yet accepted / rejected
+    rc = MCMC_HIP_OK;
+    while (left > 0 && rc == MCMC_HIP_OK) {
+        const unsigned long long c0 = h->step / (unsigned long long)d;
+        const unsigned long long room = (c0 + (unsigned long long)max_cyc) * d - h->step;
+        const int n = (int)std::min<unsigned long long>((unsigned long long)left, room);
+        const int ncyc = (int)((h->step + (unsigned long long)n - 1) / d - c0 + 1);
+        {
+            Timed t(h, 1);
+            HIP_TRY(h, h->V.resize((size_t)h->G * ncyc * dd));
+            mcmc::BasisArgs b{};
+            b.T = h->dT.p; b.V = h->V.p;
+            b.group0 = h->cfg.walker_offset / (uint32_t)h->gs;
+            b.cycle0 = (uint32_t)c0;
+            b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
+            b.ncyc = ncyc;
+            if (h->kb) HIP_TRY(h, h->kb->basis(b, h->G, d, h->stream));
+            else HIP_TRY(h, h->k->basis(b, h->G, h->stream));
+        }
+        a.s.V = h->V.p; a.s.ncyc = ncyc;
+        for (int s = 0; s < n; ++s) {
+            a.s.step0 = h->step;
+            a.cyc = (int)(h->step / (unsigned long long)d - c0);
+            a.col = (int)(h->step % (unsigned long long)d);
+            {
+                Timed t(h, 0);
+                HIP_TRY(h, mcmc_hip_launch_fn_walker(&a, pending ? 1 : 0, 1, h->stream));
+            }
+            h->n_step_launches += 1;
+            // (the launch has settled the previous trial; a callback that fails drops THIS one:
+            // state and step counter stay as of the last completed step)
+            pending = false;
+            rc = function_call(h, W, F.points.p, F.ll_t.p);
+            if (rc) break;
+            pending = true;
+            h->step += 1;
+        }
+        left -= n;
+    }
+    if (pending) {
+        Timed t(h, 0);
+        HIP_TRY(h, mcmc_hip_launch_fn_walker(&a, 1, 0, h->stream));
+    }
+    take_noted_kernel(h);
+    return rc;
+}
+
+// the flag of a function target that returned NaN or +inf inside the support (1 + walker, 0: none)
+int function_target_error(mcmc_hip_ctx* h, int bad)
+{
+    return fail(h, MCMC_HIP_ERR_TARGET,
+                "the function target returned NaN or +inf inside the prior support (walker %d): a "
+                "log-likelihood there must be finite or -inf", bad - 1);
+}
+
+extern "C" {
+
+int mcmc_hip_set_target_function(mcmc_hip_ctx* h, mcmc_hip_loglike_fn fn, void* user)
+{
+    if (!h) return MCMC_HIP_ERR_ARG;
+    if (!fn) return fail(h, MCMC_HIP_ERR_ARG, "null argument");
+    if (h->d > kMaxDimBig)
+        return fail(h, MCMC_HIP_ERR_ARG, "a function target serves d <= %d, got d=%d", kMaxDimBig, h->d);
+    if (h->cfg.flags & MCMC_HIP_FLAG_INCREMENTAL)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target is evaluated from scratch (incremental evaluation, "
+                    "MCMC_HIP_FLAG_INCREMENTAL, is not served)");
+    if (h->cfg.flags & MCMC_HIP_FLAG_OWN_BASIS)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target needs the shared basis (own basis, MCMC_HIP_FLAG_OWN_BASIS / "
+                    "shared_basis: False, is not served)");
+    if (h->cfg.emit_capacity > 0)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target emits no rows on the device (emit_capacity > 0 / emit: chains is "
+                    "not served; use emit: snapshots)");
+    const int rc = function_refusals(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, h->fnt.bad.resize(1));
+    HIP_TRY(h, hipMemsetAsync(h->fnt.bad.p, 0, sizeof(int), h->stream));
+    h->fnt.fn = fn;
+    h->fnt.user = user;
+    h->fnt.on = true;
+    h->K = 0;
+    h->bg.on = false;
+    h->mean.clear(); h->Linv.clear(); h->cnorm.clear(); h->weight.clear();
+    h->have_target = true;
+    ++h->dir_epoch;
+    h->have_state = false;
+    return upload_constants(h);
+}
+
+int mcmc_hip_set_target_binned_gaussian(mcmc_hip_ctx* h, int32_t n_bins, const int32_t* bins,
+                                        int32_t lmax, const double* weights, const double* X,
+                                        const double* cov, int32_t n_lin, const double* theta0,
+                                        const double* D0, const double* J, int32_t calib_index)
+{
+    if (!h) return MCMC_HIP_ERR_ARG;
+    if (h->huge)
+        return fail(h, MCMC_HIP_ERR_ARG, "d=%d > %d: the binned Gaussian target is not served", h->d, kMaxDimBig);
+    if (!bins || !weights || !X || !cov || !theta0 || !D0 || !J)
+        return fail(h, MCMC_HIP_ERR_ARG, "null argument");
+    const int d = h->d;
+    if (!h->k || n_lin != d - 1 || n_lin < 1 || calib_index < 0 || calib_index >= d)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "the binned Gaussian target takes d - 1 = %d emulator parameters and one "
+                    "calibration parameter among 2 <= d <= 32 sampled ones (n_lin=%d, calib=%d)",
+                    d - 1, n_lin, calib_index);
+    if (n_bins < 1 || n_bins > 640 || lmax < 1)
+        return fail(h, MCMC_HIP_ERR_ARG, "n_bins must be in 1..640 (got %d) and lmax >= 1", n_bins);
+    if (h->incremental || h->own_basis || h->cfg.emit_capacity > 0)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "the binned Gaussian target is evaluated from scratch with the shared basis "
+                    "and emit_capacity 0 (it is not Gaussian in the calibration parameter)");
+    for (int b = 0; b < n_bins; ++b) {
+        const int tp = bins[3 * b], l0 = bins[3 * b + 1], l1 = bins[3 * b + 2];
+        if (tp < 0 || tp > 2 || l0 < 0 || l1 < l0 || l1 > lmax)
+            return fail(h, MCMC_HIP_ERR_ARG, "bin %d = (%d, %d, %d) is not inside 0..%d", b, tp, l0, l1, lmax);
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    auto& B = h->bg;
+    const size_t n = n_bins, L1 = (size_t)lmax + 1;
+    // cov = L L^T; chi2 = |L^-1 delta|^2 (the quadratic form of functions.py:64-78)
+    std::vector<double> L(n * n);
+    B.Linv.assign(n * n, 0.0);
+    if (!is_symmetric(n_bins, cov) || !cholesky_lower(n_bins, cov, L.data()))
+        return fail(h, MCMC_HIP_ERR_NOT_PD,
+                    "the covariance of the binned data is not a symmetric positive-definite matrix");
+    tri_inverse_lower(n_bins, L.data(), B.Linv.data());
+    // binned response of the linear emulator (oracle: orc_binned_collapse)
+    B.Bc0.assign(n, 0.0);
+    B.BJ.assign(n * (size_t)n_lin, 0.0);
+    for (size_t b = 0; b < n; ++b) {
+        const size_t tp = bins[3 * b], l0 = bins[3 * b + 1], l1 = bins[3 * b + 2];
+        double acc = 0.0;
+        for (size_t l = l0; l <= l1; ++l) acc = std::fma(D0[tp * L1 + l], weights[l], acc);
+        B.Bc0[b] = acc;
+        for (int p = 0; p < n_lin; ++p) {
+            double a = 0.0;
+            for (size_t l = l0; l <= l1; ++l) a = std::fma(J[(tp * L1 + l) * n_lin + p], weights[l], a);
+            B.BJ[b * n_lin + p] = a;
+        }
+    }
+    B.n_bins = n_bins; B.lmax = lmax; B.n_lin = n_lin; B.calib = calib_index;
+    B.nlp = (n_lin + 3) & ~3;
+    // k-steps of four bins, an EVEN number of them: pl_chi2_kernel fetches the operands of two
+    // k-steps with one 16-byte load (a padding k-step is zeros: exact no-ops at the end of a chain)
+    B.KT = (((n_bins + 3) / 4) + 1) & ~1;
+    B.bins.assign(bins, bins + 3 * n);
+    const int NT = (n_bins + 15) / 16;
+    B.ntw = (NT + 7) / 8;
+    // records (Bc0_b, BJ_b0 .. BJ_b,nlp-1, X_b) and the padded fiducial point
+    std::vector<double> resp(n * (size_t)(B.nlp + 2), 0.0), th((size_t)B.nlp, 0.0);
+    for (size_t b = 0; b < n; ++b) {
+        double* r = resp.data() + b * (size_t)(B.nlp + 2);
+        r[0] = B.Bc0[b];
+        for (int p = 0; p < n_lin; ++p) r[1 + p] = B.BJ[b * n_lin + p];
+        r[1 + B.nlp] = X[b];
+    }
+    th.resize(32, 0.0);    // (pl_residual_mfma_kernel reads 8 np <= 32 entries)
+    std::copy(theta0, theta0 + n_lin, th.begin());
+    // the same response as matrix-core operands (PlResidualMfmaArgs)
+    const int n_tiles = (B.KT + 3) / 4, npairs = (n_lin + 7) / 8;
+    std::vector<double> bjs((size_t)n_tiles * npairs * 128, 0.0), es((size_t)n_tiles * 4 * 128, 0.0);
+    for (int T = 0; T < n_tiles; ++T) {
+        for (int jp = 0; jp < npairs; ++jp)
+            for (int l = 0; l < 64; ++l)
+                for (int e = 0; e < 2; ++e) {
+                    const size_t b = 16 * (size_t)T + (l & 15);
+                    const int p = 4 * (2 * jp + e) + (l >> 4);
+                    if (b < n && p < n_lin)
+                        bjs[(((size_t)T * npairs + jp) * 64 + l) * 2 + e] = B.BJ[b * n_lin + p];
+                }
+        for (int l = 0; l < 64; ++l)
+            for (int r = 0; r < 4; ++r) {
+                const size_t b = 16 * (size_t)T + 4 * r + (l >> 4);
+                if (b >= n) continue;
+                es[(((size_t)T * 4 + r / 2) * 64 + l) * 2 + (r & 1)] = B.Bc0[b];
+                es[(((size_t)T * 4 + 2 + r / 2) * 64 + l) * 2 + (r & 1)] = X[b];
+            }
+    }
+    HIP_TRY(h, B.bjs.resize(bjs.size()));
+    HIP_TRY(h, B.es.resize(es.size()));
+    HIP_TRY(h, hipMemcpy(B.bjs.p, bjs.data(), sizeof(double) * bjs.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(B.es.p, es.data(), sizeof(double) * es.size(), hipMemcpyHostToDevice));
+    // tiles of L^-1 per wave of pl_chi2_kernel: wave q owns the 16-row tiles of class q in
+    // ascending order, absent tiles first; tile R has min(4 R + 4, KT) k-steps
+    std::vector<double> As;
+    for (int q = 0; q < 8; ++q) {
+        std::vector<int> mine;
+        for (int R = 0; R < NT; ++R)
+            if (binned_class(R, NT) == q) mine.push_back(R);
+        const int absent = B.ntw - (int)mine.size();
+        for (int t = 0; t < 5; ++t) { B.nk[q][t] = 0; B.tile_off[q][t] = 0; }
+        for (int t = 0; t < (int)mine.size(); ++t) {
+            const int R = mine[t], nk = std::min(4 * R + 4, B.KT);   // (even)
+            B.nk[q][absent + t] = nk;
+            B.tile_off[q][absent + t] = As.size();
+            // (A-operand lane order, the k-steps 2 m and 2 m + 1 of a lane side by side)
+            for (int kk2 = 0; kk2 < nk / 2; ++kk2)
+                for (int l = 0; l < 64; ++l)
+                    for (int h2 = 0; h2 < 2; ++h2) {
+                        const size_t j = 16 * (size_t)R + (l & 15), i = 4 * (size_t)(2 * kk2 + h2) + (l >> 4);
+                        As.push_back((j < n && i <= j) ? B.Linv[j * n + i] : 0.0);
+                    }
+        }
+    }
+    As.resize(As.size() + (size_t)mcmc::kPlPad * 64, 0.0);   // (operands are fetched ahead)
+    // pl_fused_kernel: per wave q and group G of eight virtual tiles (virtual = real + shift) the
+    // tile at position s = min(q, 7 - q) (half 0) and at 7 - s (half 1), each as a stream of its
+    // k-step pairs from pair 0, in A-operand lane order; absent tiles point at a block of zeros
+    {
+        const int sh = binned_shift(NT), NG = (NT + sh) / 8;
+        B.f_shift = sh; B.f_ng = NG;
+        std::vector<double> Af(128, 0.0);       // [0, 128): the zero block
+        for (int q = 0; q < 8; ++q) {
+            const int s_pos = q < 4 ? q : 7 - q;
+            for (int G = 0; G < 5; ++G)
+                for (int hf = 0; hf < 2; ++hf) {
+                    B.f_off[q][G][hf] = 0; B.f_pairs[q][G][hf] = 0;
+                    const int R = 8 * G + (hf ? 7 - s_pos : s_pos) - sh;
+                    if (G >= NG || R < 0 || R >= NT) continue;
+                    const int np2 = std::min(2 * R + 2, B.KT / 2);
+                    B.f_off[q][G][hf] = Af.size();
+                    B.f_pairs[q][G][hf] = np2 + 2 * sh;
+                    for (int P = 0; P < np2; ++P)
+                        for (int l = 0; l < 64; ++l)
+                            for (int e = 0; e < 2; ++e) {
+                                const size_t j = 16 * (size_t)R + (l & 15), i = 4 * (size_t)(2 * P + e) + (l >> 4);
+                                Af.push_back((j < n && i <= j) ? B.Linv[j * n + i] : 0.0);
+                            }
+                }
+        }
+        Af.resize(Af.size() + 256, 0.0);
+        HIP_TRY(h, B.Afused.resize(Af.size()));
+        HIP_TRY(h, hipMemcpy(B.Afused.p, Af.data(), sizeof(double) * Af.size(), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(h, B.resp.resize(resp.size()));
+    HIP_TRY(h, B.theta0.resize(th.size()));
+    HIP_TRY(h, B.Astream.resize(As.size()));
+    HIP_TRY(h, B.weights.resize(L1));
+    HIP_TRY(h, B.X.resize(n));
+    HIP_TRY(h, B.dbins.resize(3 * n));
+    HIP_TRY(h, hipMemcpy(B.resp.p, resp.data(), sizeof(double) * resp.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(B.theta0.p, th.data(), sizeof(double) * th.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(B.Astream.p, As.data(), sizeof(double) * As.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(B.weights.p, weights, sizeof(double) * L1, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(B.X.p, X, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(B.dbins.p, bins, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice));
+    B.on = true;
+    h->fnt.on = false;
+    h->K = 0;
+    h->mean.clear(); h->Linv.clear(); h->cnorm.clear(); h->weight.clear();
+    h->have_target = true;
+    ++h->dir_epoch;
+    h->have_state = false;
+    return upload_constants(h);
+}
+
+int mcmc_hip_get_binned_constants(const mcmc_hip_ctx* h, double* Linv, double* Bc0, double* BJ)
+{
+    if (!h || !h->bg.on) return MCMC_HIP_ERR_STATE;
+    const auto& B = h->bg;
+    if (Linv) std::copy(B.Linv.begin(), B.Linv.end(), Linv);
+    if (Bc0) std::copy(B.Bc0.begin(), B.Bc0.end(), Bc0);
+    if (BJ) std::copy(B.BJ.begin(), B.BJ.end(), BJ);
+    return MCMC_HIP_OK;
+}
+
+int mcmc_hip_evaluate_binned(mcmc_hip_ctx* h, int32_t n_pts, int32_t L0, int32_t n_ell,
+                             const double* cl, const double* A, double* chi2)
+{
+    if (!h) return MCMC_HIP_ERR_ARG;
+    if (!h->bg.on) return fail(h, MCMC_HIP_ERR_STATE, "set_target_binned_gaussian must precede evaluate_binned");
+    auto& B = h->bg;
+    if (n_pts <= 0 || !cl || !A || !chi2 || L0 < 0 || n_ell <= 0)
+        return fail(h, MCMC_HIP_ERR_ARG, "bad argument");
+    for (int b = 0; b < B.n_bins; ++b)
+        if (B.bins[3 * b + 1] < L0 || B.bins[3 * b + 2] - L0 >= n_ell)
+            return fail(h, MCMC_HIP_ERR_ARG, "bin %d (l = %d..%d) is outside the spectra given (l = %d..%d)",
+                        b, B.bins[3 * b + 1], B.bins[3 * b + 2], L0, L0 + n_ell - 1);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t np = ((size_t)n_pts + 63) & ~(size_t)63;
+    HIP_TRY(h, B.ecl.resize((size_t)n_pts * 3 * n_ell));
+    HIP_TRY(h, B.eA.resize(n_pts));
+    HIP_TRY(h, B.echi2.resize(np));
+    HIP_TRY(h, B.edelta.resize((np / 64) * (size_t)B.KT * 256 + (size_t)mcmc::kPlPad * 256));
+    HIP_TRY(h, hipMemcpyAsync(B.ecl.p, cl, sizeof(double) * (size_t)n_pts * 3 * n_ell,
+                              hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(B.eA.p, A, sizeof(double) * n_pts, hipMemcpyHostToDevice, h->stream));
+    mcmc::PlBinArgs b{};
+    b.cl = B.ecl.p; b.A = B.eA.p; b.bins = B.dbins.p; b.weights = B.weights.p; b.X = B.X.p;
+    b.delta = B.edelta.p; b.n_pts = n_pts; b.n_bins = B.n_bins; b.KT = B.KT; b.L0 = L0; b.stride = n_ell;
+    HIP_TRY(h, mcmc_hip_launch_pl_bin(&b, h->stream));
+    HIP_TRY(h, B.epsum.resize(32 * np));
+    const int rc = binned_chi2(h, B.edelta.p, B.epsum.p, B.echi2.p, (int)np);
+    if (rc) return rc;
+    std::vector<double> c2(np);
+    HIP_TRY(h, hipMemcpyAsync(c2.data(), B.echi2.p, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::copy(c2.begin(), c2.begin() + n_pts, chi2);
+    take_noted_kernel(nullptr);
+    return MCMC_HIP_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// Kernel arguments of checkpoint_kernels.hip (shared with capi.hip).
+// Kernel arguments of checkpoint_kernels.hip (shared with capi_checkpoint.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,3 +61,11 @@ struct CkptBoundsReduceArgs {
 };
 
 }  // namespace mcmc
+
+// the launchers of checkpoint_kernels.hip: declared here alone, for the kernels' translation unit
+// and the host side
+extern "C" hipError_t mcmc_hip_launch_ckpt_window(const mcmc::CkptWindowArgs* a, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_ckpt_payload(const mcmc::CkptPayloadArgs* a, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_ckpt_solve(const mcmc::CkptSolveArgs* a, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_ckpt_bounds(const mcmc::CkptBoundsArgs* a, int G, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_ckpt_bounds_reduce(const mcmc::CkptBoundsReduceArgs* a, hipStream_t st);

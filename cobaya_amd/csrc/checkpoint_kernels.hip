@@ -8,7 +8,7 @@
 //   ckpt_payload_kernel  group means, sum_m, sum_mm, sum_N cov: the buffer the all-reduce carries
 //   ckpt_solve_kernel    W, B, R-1 = max eig(L^-1 Bhat L^-T); T = scale diag(std) chol(corr(W))
 // The dense linear algebra (d <= 128) is one workgroup: Cholesky, triangular inverse and the two
-// products in the operation order of the host routines in capi.hip (cholesky_lower,
+// products in the operation order of the host routines in host_linalg.cpp (cholesky_lower,
 // tri_inverse_lower, mcmc_hip_gelman_rubin, mcmc_hip_set_proposal_cov) -- so the transform the
 // device writes is bit for bit the one the host would compute from the same statistics --, the
 // largest eigenvalue by Householder tridiagonalisation + Sturm bisection (the host uses QL: R-1
@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(256) ckpt_payload_kernel(const CkptPayloadArgs
 }
 
 // ---------------------------------------------------------------- dense linear algebra, one workgroup
-// lower Cholesky, row-major (capi.hip cholesky_lower: the same operations in the same order);
+// lower Cholesky, row-major (host_linalg.cpp cholesky_lower: the same operations in the same order);
 // returns false if not positive definite.  One thread per row, two barriers per column.
 // (PT: `double*` in global memory, or an LDS pointer -- ds_read / ds_write, which the compiler
 // pipelines freely; through a generic pointer every access is a flat instruction it serialises)
@@ -137,7 +137,7 @@ __device__ bool wg_cholesky(int n, PT A, PT L, int* flag)
     return true;
 }
 
-// inverse of a lower-triangular matrix (capi.hip tri_inverse_lower): one thread per column
+// inverse of a lower-triangular matrix (host_linalg.cpp tri_inverse_lower): one thread per column
 template <typename PT>
 __device__ void wg_tri_inverse(int n, PT L, PT Li)
 {

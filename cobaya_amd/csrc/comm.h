@@ -1,4 +1,4 @@
-// comm.h -- what capi.hip needs of the communicator (comm.hip): the in-stream all-reduce of the
+// comm.h -- what capi_checkpoint.hip needs of the communicator (comm.hip): the in-stream all-reduce of the
 // device checkpoint's payload.  Internal to libmcmc_hip.so (hidden visibility).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -129,7 +129,7 @@ int reserve(mcmc_hip_comm* c, size_t n)
 
 }  // namespace
 
-// ---- what capi.hip uses (comm.h) ----------------------------------------------------------------
+// ---- what capi_checkpoint.hip uses (comm.h) ----------------------------------------------------------------
 int mcmc_comm_allreduce_on_stream(mcmc_hip_comm* c, double* dev, size_t n, int op, hipStream_t st)
 {
     if (!c || !c->comm) return MCMC_HIP_ERR_STATE;

@@ -1,0 +1,397 @@
+// The engine context and what every host translation unit of libmcmc_hip.so shares: error
+// reporting, the timing regions, the per-dimension kernel lookups and the noted step kernel.
+// Private to the library (the C ABI is include/mcmc_hip.h).  gfx950 only; no CPU fallback.
+#pragma once
+#include "../../include/mcmc_hip.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+// the host side may find a launcher missing (a developer build of a few dimensions): there, and
+// only there, the optional launchers are weak references (kernels.h: MCMC_HIP_OPTIONAL)
+#define MCMC_HIP_HOST_SIDE 1
+#include "kernels.h"
+#include "huge_args.h"
+#include "pliklite_args.h"
+#include "function_args.h"
+#include "checkpoint_args.h"
+#include "comm.h"
+#include "inc_choice.h"
+
+MCMC_DECLARE_DIM(1) MCMC_DECLARE_DIM(2) MCMC_DECLARE_DIM(3) MCMC_DECLARE_DIM(4)
+MCMC_DECLARE_DIM(5) MCMC_DECLARE_DIM(6) MCMC_DECLARE_DIM(7) MCMC_DECLARE_DIM(8)
+MCMC_DECLARE_DIM(9) MCMC_DECLARE_DIM(10) MCMC_DECLARE_DIM(11) MCMC_DECLARE_DIM(12)
+MCMC_DECLARE_DIM(13) MCMC_DECLARE_DIM(14) MCMC_DECLARE_DIM(15) MCMC_DECLARE_DIM(16)
+MCMC_DECLARE_DIM(17) MCMC_DECLARE_DIM(18) MCMC_DECLARE_DIM(19) MCMC_DECLARE_DIM(20)
+MCMC_DECLARE_DIM(21) MCMC_DECLARE_DIM(22) MCMC_DECLARE_DIM(23) MCMC_DECLARE_DIM(24)
+MCMC_DECLARE_DIM(25) MCMC_DECLARE_DIM(26) MCMC_DECLARE_DIM(27) MCMC_DECLARE_DIM(28)
+MCMC_DECLARE_DIM(29) MCMC_DECLARE_DIM(30) MCMC_DECLARE_DIM(31) MCMC_DECLARE_DIM(32)
+
+MCMC_DECLARE_BIG(48) MCMC_DECLARE_BIG(56) MCMC_DECLARE_BIG(64) MCMC_DECLARE_BIG(72)
+MCMC_DECLARE_BIG(80) MCMC_DECLARE_BIG(88) MCMC_DECLARE_BIG(96) MCMC_DECLARE_BIG(100)
+MCMC_DECLARE_BIG(112) MCMC_DECLARE_BIG(120) MCMC_DECLARE_BIG(128)
+
+MCMC_DECLARE_PAIR(33) MCMC_DECLARE_PAIR(34) MCMC_DECLARE_PAIR(35) MCMC_DECLARE_PAIR(36)
+MCMC_DECLARE_PAIR(37) MCMC_DECLARE_PAIR(38) MCMC_DECLARE_PAIR(39) MCMC_DECLARE_PAIR(40)
+MCMC_DECLARE_PAIR(41) MCMC_DECLARE_PAIR(42) MCMC_DECLARE_PAIR(43) MCMC_DECLARE_PAIR(44)
+MCMC_DECLARE_PAIR(45) MCMC_DECLARE_PAIR(46) MCMC_DECLARE_PAIR(47) MCMC_DECLARE_PAIR(48)
+MCMC_DECLARE_PAIR(49) MCMC_DECLARE_PAIR(50) MCMC_DECLARE_PAIR(51) MCMC_DECLARE_PAIR(52)
+MCMC_DECLARE_PAIR(53) MCMC_DECLARE_PAIR(54) MCMC_DECLARE_PAIR(55) MCMC_DECLARE_PAIR(56)
+
+using mcmc::BigKernels;
+using mcmc::ConstLayout;
+using mcmc::DimKernels;
+
+constexpr int kMaxDimBig = 128;  // basis_big_kernel keeps H (d*d doubles) in 160 KiB of LDS
+
+// smallest compiled padded size that serves dimension d (32 < d <= 128)
+inline const BigKernels* big_for_dim(int d)
+{
+    typedef const BigKernels* (*getter)();
+    static const getter table[] = {mcmc_hip_big_48,  mcmc_hip_big_56,  mcmc_hip_big_64,
+                                   mcmc_hip_big_72,  mcmc_hip_big_80,  mcmc_hip_big_88,
+                                   mcmc_hip_big_96,  mcmc_hip_big_100, mcmc_hip_big_112,
+                                   mcmc_hip_big_120, mcmc_hip_big_128};
+    if (d <= mcmc::kMaxDimLane || d > kMaxDimBig) return nullptr;
+    for (getter g : table)
+        if (g != nullptr && g()->dp >= d) return g();
+    return nullptr;
+}
+
+// the two-wave step kernel of a dimension 32 < d <= kMaxDimPair, if compiled
+inline const mcmc::PairKernels* pair_for_dim(int d)
+{
+    typedef const mcmc::PairKernels* (*getter)();
+    static const getter table[] = {mcmc_hip_pair_33, mcmc_hip_pair_34, mcmc_hip_pair_35,
+                                   mcmc_hip_pair_36, mcmc_hip_pair_37, mcmc_hip_pair_38,
+                                   mcmc_hip_pair_39, mcmc_hip_pair_40, mcmc_hip_pair_41,
+                                   mcmc_hip_pair_42, mcmc_hip_pair_43, mcmc_hip_pair_44,
+                                   mcmc_hip_pair_45, mcmc_hip_pair_46, mcmc_hip_pair_47,
+                                   mcmc_hip_pair_48, mcmc_hip_pair_49, mcmc_hip_pair_50,
+                                   mcmc_hip_pair_51, mcmc_hip_pair_52, mcmc_hip_pair_53,
+                                   mcmc_hip_pair_54, mcmc_hip_pair_55, mcmc_hip_pair_56};
+    static_assert(sizeof(table) / sizeof(table[0]) == mcmc::kMaxDimPair - mcmc::kMaxDimLane, "");
+    if (d <= mcmc::kMaxDimLane || d > mcmc::kMaxDimPair) return nullptr;
+    const getter g = table[d - mcmc::kMaxDimLane - 1];
+    return g != nullptr ? g() : nullptr;
+}
+
+inline const DimKernels* kernels_for_dim(int d)
+{
+    typedef const DimKernels* (*getter)();
+    static const getter table[33] = {
+        nullptr,          mcmc_hip_dim_1,  mcmc_hip_dim_2,  mcmc_hip_dim_3,  mcmc_hip_dim_4,
+        mcmc_hip_dim_5,   mcmc_hip_dim_6,  mcmc_hip_dim_7,  mcmc_hip_dim_8,  mcmc_hip_dim_9,
+        mcmc_hip_dim_10,  mcmc_hip_dim_11, mcmc_hip_dim_12, mcmc_hip_dim_13, mcmc_hip_dim_14,
+        mcmc_hip_dim_15,  mcmc_hip_dim_16, mcmc_hip_dim_17, mcmc_hip_dim_18, mcmc_hip_dim_19,
+        mcmc_hip_dim_20,  mcmc_hip_dim_21, mcmc_hip_dim_22, mcmc_hip_dim_23, mcmc_hip_dim_24,
+        mcmc_hip_dim_25,  mcmc_hip_dim_26, mcmc_hip_dim_27, mcmc_hip_dim_28, mcmc_hip_dim_29,
+        mcmc_hip_dim_30,  mcmc_hip_dim_31, mcmc_hip_dim_32};
+    if (d < 1 || d > 32 || table[d] == nullptr) return nullptr;
+    return table[d]();
+}
+
+inline std::string g_create_error;
+
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    hipError_t resize(size_t count)
+    {
+        if (count <= n) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+        hipError_t e = hipMalloc((void**)&p, sizeof(T) * count);
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+struct mcmc_hip_ctx {
+    mcmc_hip_config cfg{};
+    const DimKernels* k = nullptr;    // d <= 32: lane-per-walker kernels of that dimension
+    const BigKernels* kb = nullptr;   // 32 < d <= 128: column-sweep / matrix-core kernels
+    const mcmc::PairKernels* kp = nullptr;   // 32 < d <= 56: the two-wave step kernel, if it fits
+    bool huge = false;                // 128 < d <= 256: huge_kernels.hip (incremental, one block, K <= 4)
+    // huge: the Haar columns of one cycle of every basis group ([BG][d][d]), the basis scratch, and
+    // the per-step direction columns of a launch ([BG][n][huge_col_stride])
+    DevBuf<double> hV, hScratch, hCols;
+    unsigned long long hV_cycle = ~0ull, hV_epoch = ~0ull;
+    hipStream_t stream = nullptr;
+    std::string err;
+    int d = 0, W = 0, G = 0, gs = 0, K = -1;
+    bool have_prior = false, have_target = false, have_cov = false, have_state = false;
+    // host copies of the problem
+    std::vector<int32_t> kind, periodic;
+    std::vector<double> lo, hi, loc, scale, mls;
+    double uniform_logp = 0.0;
+    uint32_t norm_mask = 0, periodic_mask = 0;
+    uint32_t norm_mask4[4] = {0, 0, 0, 0};
+    bool any_periodic = false;
+    std::vector<double> mean, Linv, cnorm, weight;  // Linv: [K][d*d] row-major
+    std::vector<double> cov, T;                     // proposal
+    // parameter blocks (proposal.py:96-196); blocked == false: one block, identity order
+    bool blocked = false;
+    std::vector<int32_t> blk_size, blk_over, i_of_j;
+    int drag_last_slow = -1, drag_steps = 0;
+    DevBuf<int> dblk, vflag, vflag_f;               // dblk: size | oversample | i_of_j
+    DevBuf<double> Vf;                              // dragging: directions of the fast blocks
+    DevBuf<double> drag_cs;                         // drag_general_kernel: start points [d][W]
+    std::vector<double> shift;                      // moment shift
+    // device
+    DevBuf<double> x, logpost, logprior, loglike, cblock, dT, V, rows, gsum, Sg, pooled, dshift;
+    DevBuf<double> ex, elp, ell, eder, escratch, dLrow, dLcol;
+    // incremental evaluation (MCMC_HIP_FLAG_INCREMENTAL): carried y, per-step (v, u) pairs,
+    // padded prior constants, row-major L^-1 and the mean of the one mode
+    bool incremental = false;
+    bool y_valid = false;
+    bool own_basis = false;     // MCMC_HIP_FLAG_OWN_BASIS (d > 1): a Haar basis per walker
+    // incremental mode: walkers sharing one Haar basis (a multiple of group_size, flags bits
+    // 8..11 = log2 of the multiple); the R-1 groups (moments) stay group_size wide
+    int bgs = 0, BG = 0;
+    DevBuf<double> y, inc_prior, inc_Lrow, inc_mean;
+    // mixtures on the kernels that carry the log-density of every mode (inc_choice.h: IncChoice::carry_modes):
+    // amode[K][W]; valid = written by a launch (or set) since y was; else re-anchored on y
+    DevBuf<double> amode;
+    bool amode_valid = false;
+    // The directions of a launch -- Haar columns V (Vf: the fast blocks' when dragging) and their
+    // whitened pairs VU -- do not depend on the walkers' state, so the set of the NEXT launch is
+    // computed on a second stream while the step kernel of this one runs (two sets, used in
+    // turn).  A set computed ahead is used only if the launch that comes is the one predicted
+    // (same first step, same length) and nothing the directions depend on has been set since
+    // (dir_epoch); otherwise it is recomputed on the main stream.
+    struct DirSet {
+        DevBuf<double> V, Vf, VU;
+        DevBuf<int> vflag, vflag_f, colflag;   // colflag: 1-D columns of the launch, in VU order
+        bool has_flags = false;
+        DevBuf<double> UU;                   // |u|^2 of the columns (step_inc_kernel: one mode, no periodic parameter)
+        DevBuf<double> VW, NL;               // the carried log-prior's stream and (v.w, loc.w) of the columns
+        hipEvent_t ready = nullptr;          // recorded on the stream that filled the set
+        bool ahead = false;                  // filled ahead of its launch (on stream2)
+        unsigned long long step0 = ~0ull, epoch = 0;
+        int n = 0;
+    } dirs[2];
+    int dir_cur = 0;
+    unsigned long long dir_epoch = 0;
+    hipStream_t stream2 = nullptr;
+    hipEvent_t mark = nullptr;               // main stream: behind the last step kernel
+    bool mark_valid = false;
+    bool prefetch = true;
+    // the directions of the launch a call BEGINS with are formed at that call, not at the end of
+    // the previous one (capi_incremental.hip: acquire_direction_set): a proposal refreshed in between is then in them at once
+    bool lazy_dirs = true;
+    // step_inc_kernel: calls whose directions are formed together (MCMC_HIP_LOOKAHEAD, default 4)
+    int lookahead = 4;
+    // incremental_duo.hip (two lanes per walker): -1 = where the ensemble fills the chip with it
+    // (kDuoMinWalkers), 0 = never, 1 = wherever the kernel serves the model (MCMC_HIP_DUO)
+    int duo = -1;
+    hipEvent_t T_event = nullptr;            // main stream: behind the last write of dT
+    bool T_fresh = false;                    // ... which no direction set has been ordered behind yet
+    // asynchronous checkpoint (mcmc_hip_request_moments / mcmc_hip_fetch_moments) and
+    // stream-ordered proposal refresh: pinned host staging
+    double* pin_mom = nullptr;                      // [G*d + d(d+1)/2 + 2]
+    double* pin_T = nullptr;                        // ring of 4 transforms [4][d*d]
+    int pin_T_slot = 0;
+    hipEvent_t pin_T_done[4] = {nullptr, nullptr, nullptr, nullptr};   // the copy out of slot k has run
+    hipEvent_t mom_event = nullptr;
+    bool mom_pending = false;
+    bool mom_fn = false;                            // the pending read-out carries a function target's error flag
+    int64_t mom_n = 0;
+    unsigned long long mom_step = 0;
+    // drain_samples_pinned: ring of pinned host slots the packed rows are copied into (PCIe at
+    // full rate, and the caller reads them in place)
+    struct HostSlot { double* p = nullptr; size_t cap_rows = 0; };
+    std::vector<HostSlot> slots = std::vector<HostSlot>(4);
+    int slot_next = 0;
+    DevBuf<double> pack_out;                        // drain_samples: packed rows
+    DevBuf<long long> pack_off;
+    DevBuf<int> weight_i, prej, burn, stuck, nrows;
+    DevBuf<int> thin_acc;   // thinned emission (mcmc_hip_set_emit_thin): the weight a walker has added up
+    int emit_thin = 1;
+    DevBuf<long long> nacc;
+    DevBuf<unsigned long long> acc_total;
+    unsigned long long step = 0;
+    int64_t n_snapshots = 0;
+    // timing
+    bool timing = false;
+    struct Ev {
+        hipEvent_t a, b;
+        int kind;
+    };
+    std::vector<Ev> pending;
+    std::vector<hipEvent_t> pool;
+    // kinds 0..2: step kernels / directions / moment snapshots; 3..5: the three kernels of a
+    // step on the binned target (pl_walker, pl_residual, pl_chi2), each launch timed
+    double ms[6] = {0, 0, 0, 0, 0, 0};
+    int64_t n_seen[6] = {0, 0, 0, 0, 0, 0}, n_timed[6] = {0, 0, 0, 0, 0, 0};   // timed regions per kind (Timed)
+    int64_t n_step_launches = 0;
+    std::string last_step_kernel;     // what the last step launcher said it launched
+    // device-side learn / convergence checkpoint (checkpoint_kernels.hip)
+    struct Ckpt {
+        DevBuf<double> ring, wsum, payload, ws, out;
+        DevBuf<unsigned long long> acc_prev;
+        int cap = 0;               // ring slots
+        long long n_done = 0;      // checkpoints taken so far (the next one goes to slot n_done % cap)
+        double* pin_out = nullptr; // [8 + 2 d^2 + d]: the solve's outcome, or the reduced payload
+        hipEvent_t ev = nullptr;
+        bool begun = false, pending = false;
+        bool payload_only = false; // the pending read-out is the payload (checkpoint_request_payload)
+    } ck;
+    // R-1 of the confidence bounds (mcmc.py:918-1002): ring of ensemble snapshots [slot][d][W]
+    struct Bounds {
+        DevBuf<double> ring, bounds, payload;
+        int n_slots = 0;
+        double* pin = nullptr;     // [1 + 4 d + G d 2]
+    } bd;
+    // the walker shards' communicator (comm.hip; not owned): the device checkpoint all-reduces
+    // its payload over it in stream order
+    mcmc_hip_comm* comm = nullptr;
+    // binned-bandpower Gaussian target (planck_pliklite.py:143-155; pliklite_kernels.hip)
+    struct Binned {
+        bool on = false;
+        int n_bins = 0, KT = 0, ntw = 0, n_lin = 0, nlp = 0, calib = 0, lmax = 0;
+        std::vector<int32_t> bins;                       // [n_bins][3]
+        std::vector<double> Linv, Bc0, BJ;               // host copies (tests hand them to the oracle)
+        DevBuf<double> resp, theta0, Astream, weights, X, bjs, es;   // bjs, es: pl_residual_mfma_kernel
+        DevBuf<double> Afused;                           // pl_fused_kernel: half-tile streams of L^-1
+        unsigned long long f_off[8][5][2];
+        int f_pairs[8][5][2];
+        int f_shift = 0, f_ng = 0;
+        DevBuf<int> dbins;
+        DevBuf<double> delta, trial, lp_t, Ea, psum;     // step scratch, W walkers
+        DevBuf<double> edelta, etrial, elp, echi2, epsum, ecl, eA;   // evaluate scratch
+        unsigned long long tile_off[8][5];
+        int nk[8][5];
+    } bg;
+    // function target (mcmc_hip_set_target_function; function_kernels.hip): the user's batched
+    // device function stands where the likelihood kernels of the other targets do
+    struct Function {
+        bool on = false;
+        mcmc_hip_loglike_fn fn = nullptr;
+        void* user = nullptr;
+        DevBuf<double> points, lp_t, Ea, ll_t;   // step scratch: trial [W][d], its log-prior, E_a, the function's values
+        DevBuf<int> bad;                         // [1] 1 + global id of the first walker with NaN / +inf inside the support
+    } fnt;
+};
+
+// what the last step launcher said it was about to launch (mcmc_hip_note_step_kernel)
+inline thread_local const char* g_noted_kernel = nullptr;
+
+// keeps the noted kernel as the context's last step kernel, "<name> (<what>=<value>)"; value < 0:
+// the dimension.  h == nullptr: the note is dropped (a launcher ran outside a step).
+inline void take_noted_kernel(mcmc_hip_ctx* h, const char* what = "d", int value = -1)
+{
+    if (!g_noted_kernel) return;
+    if (h)
+        h->last_step_kernel = std::string(g_noted_kernel) + " (" + what + "=" +
+                              std::to_string(value < 0 ? h->d : value) + ")";
+    g_noted_kernel = nullptr;
+}
+
+inline int fail(mcmc_hip_ctx* h, int code, const char* fmt, ...)
+{
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (h) h->err = buf;
+    else g_create_error = buf;
+    return code;
+}
+
+#define HIP_TRY(h, call)                                                                      \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail(h, MCMC_HIP_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+inline hipEvent_t get_event(mcmc_hip_ctx* h)
+{
+    if (!h->pool.empty()) {
+        hipEvent_t e = h->pool.back();
+        h->pool.pop_back();
+        return e;
+    }
+    hipEvent_t e = nullptr;
+    (void)hipEventCreate(&e);
+    return e;
+}
+
+struct Timed {
+    mcmc_hip_ctx* h;
+    int kind;
+    hipEvent_t a = nullptr, b = nullptr;
+    hipStream_t st;
+    bool on = false;
+    // Every step kernel is timed; of the regions around it (kind 1: directions, kind 2: moment
+    // snapshot) one in eight, scaled up in mcmc_hip_kernel_times: an event record is a packet
+    // of its own between two dependent kernels (about 6 us each on the critical path).
+    Timed(mcmc_hip_ctx* h_, int kind_, hipStream_t st_ = nullptr)
+        : h(h_), kind(kind_), st(st_ ? st_ : h_->stream)
+    {
+        if (h->timing) {
+            on = kind == 0 || kind >= 3 || (h->n_seen[kind] % 8) == 0;
+            h->n_seen[kind] += 1;
+        }
+        if (on) {
+            h->n_timed[kind] += 1;
+            a = get_event(h);
+            b = get_event(h);
+            (void)hipEventRecord(a, st);
+        }
+    }
+    ~Timed()
+    {
+        if (on) {
+            (void)hipEventRecord(b, st);
+            h->pending.push_back({a, b, kind});
+        }
+    }
+};
+
+inline void resolve_timing(mcmc_hip_ctx* h)
+{
+    for (auto& e : h->pending) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) h->ms[e.kind] += ms;
+        h->pool.push_back(e.a);
+        h->pool.push_back(e.b);
+    }
+    h->pending.clear();
+}
+
+// ---- what one host translation unit defines for the others ----
+// capi.hip
+// slots per cycle of the blocked proposer's three sequences (oracle: orc_block_slots)
+int block_slots(const mcmc_hip_ctx* h, int which);
+int upload_constants(mcmc_hip_ctx* h);
+// capi_targets.hip: the binned Gaussian target and function targets
+int step_binned(mcmc_hip_ctx* h, int n_steps);
+int step_function(mcmc_hip_ctx* h, int n_steps);
+int evaluate_binned_points(mcmc_hip_ctx* h, int n, const double* x, double* logprior, double* loglike);
+int function_call(mcmc_hip_ctx* h, int n, const double* points, double* loglike);
+int function_target_error(mcmc_hip_ctx* h, int bad);
+// capi_incremental.hip: incremental evaluation (d <= 128: step_incremental; above: step_huge)
+int blocked_basis(mcmc_hip_ctx* h, int which, unsigned long long c0, int ncyc, int L, size_t slab,
+                  DevBuf<double>& V, DevBuf<int>& flag, bool& any_1d, hipStream_t st = nullptr);
+int step_huge(mcmc_hip_ctx* h, int n_steps);
+int step_incremental(mcmc_hip_ctx* h, int n_steps);
+// the kernel that serves this engine's incremental steps and what it carries (inc_choice.h);
+// not served when the engine is not in incremental mode
+mcmc::IncChoice inc_choice_of(const mcmc_hip_ctx* h);

@@ -1,4 +1,4 @@
-// Kernel arguments of function_kernels.hip (shared with capi.hip).
+// Kernel arguments of function_kernels.hip (shared with capi_targets.hip).
 #pragma once
 #include "kernels.h"
 
@@ -26,3 +26,8 @@ struct FnWalkerArgs {
 };
 
 }  // namespace mcmc
+
+// the launcher of function_kernels.hip: declared here alone, for the kernels' translation unit
+// and the host side
+extern "C" hipError_t mcmc_hip_launch_fn_walker(const mcmc::FnWalkerArgs* a, int accept, int propose,
+                                                hipStream_t st);

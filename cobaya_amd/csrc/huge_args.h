@@ -3,6 +3,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "kernels.h"   // MomentArgs, hipStream_t
+
 namespace mcmc {
 
 constexpr int kMaxDimHuge = 256;
@@ -74,3 +76,11 @@ struct HugeEvalArgs {
 };
 
 }  // namespace mcmc
+
+// the launchers of huge_kernels.hip (128 < d <= 256, run-time d; incremental evaluation, one block,
+// up to four modes): declared here alone, for the kernels' translation unit and the host side
+extern "C" hipError_t mcmc_hip_launch_huge_basis(const mcmc::HugeBasisArgs*, int, int, hipStream_t);
+extern "C" hipError_t mcmc_hip_launch_huge_dirs(const mcmc::HugeDirArgs*, int, hipStream_t);
+extern "C" hipError_t mcmc_hip_launch_huge_step(const mcmc::HugeStepArgs*, hipStream_t);
+extern "C" hipError_t mcmc_hip_launch_huge_evaluate(const mcmc::HugeEvalArgs*, hipStream_t);
+extern "C" hipError_t mcmc_hip_launch_huge_moments(const mcmc::MomentArgs*, int, int, hipStream_t);

@@ -981,7 +981,7 @@ extern "C" hipError_t mcmc_hip_launch_inc_regs_16(const mcmc::IncStepArgs*, hipS
 
 namespace mcmc {
 namespace {
-// the register kernel serves what capi.hip sends here -- mixtures that the tuned
+// the register kernel serves what the choice of kernel (inc_choice.h) sends here -- mixtures that the tuned
 // step_inc_mix_kernel (K <= 4, dq <= 16) does not serve, and emitted rows (`emit: chains`) of
 // anything but the one Gaussian mode of step_inc_kernel<.., EMIT> -- without periodic parameters,
 // as far as the registers hold the residuals

@@ -36,11 +36,11 @@
 // walkers, same box (profiles/r07_one_mode_two_lanes.txt): step kernel 1.11 -> 0.99 ms per 1 200
 // steps (bench.py: 0.902 -> 0.856), 20 % fewer vector instructions; chains {2 h, 2 h + 1} (16 rows,
 // two padded) 4 % slower than {h, h + 2}; the next step's pairs requested a step ahead 22 % slower.
-// Below 65 536 walkers the four-lane kernel is as fast or faster (capi.hip: kDuo1MinWalkers).
+// Below 65 536 walkers the four-lane kernel is as fast or faster (inc_choice.h: kDuo1MinWalkers).
 //
 // Served: Metropolis steps, no periodic parameter, no emitted rows, no block of one parameter, whole
 // workgroups of 128 walkers inside one basis group -- for ensembles that fill the chip with it
-// (capi.hip: kDuoMinWalkers); smaller ensembles keep the four-lane kernel, whose twice as many
+// (inc_choice.h: kDuoMinWalkers); smaller ensembles keep the four-lane kernel, whose twice as many
 // waves cover their latencies better.
 #include <string>
 

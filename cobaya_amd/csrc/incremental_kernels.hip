@@ -376,7 +376,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
         static_assert((NORMP ? 3 : 2) * C >= 32 || (NORMP && DQ >= 29) || PER,
                       "the chunk buffers hold the deviations of the workgroup's 64 walkers");
         // (MODE 2 from d = 113 on: the chunks are too small; the host refreshes y with
-        // whiten_state_kernel before every such launch -- capi.hip: IncPlan::fold)
+        // whiten_state_kernel before every such launch -- inc_choice.h: IncChoice::fold)
         constexpr int TW = 8;
         static_assert(sizeof(pair_t) * kStagedPairs >= sizeof(double) * dpad * TW, "the tile fits sRE");
         double* const sdev = (double*)sVU + (size_t)(tid >> 2) * dpad;   // this walker's deviations

@@ -3,11 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "inc_choice.h"   // kMaxModes, inc_mix_serves, duo_serves, kIncMaxPeriodic: what the choice of kernel and the kernels share
+
 namespace mcmc {
 
 constexpr int kMaxDimLane = 32;   // lane-per-walker kernels: d <= 32 (state in VGPRs)
 constexpr int kMaxDimPair = 56;   // ... and the two-wave step kernel alone up to here
-constexpr int kMaxModes = 64;   // (16 until round 5; the tuned incremental kernels: 16, incremental_any.hip)
 
 // Whitening factor L_k^-1 (lower triangular) packed in the order the kernels consume it, so
 // that the wave-uniform operand stream is read front to back with wide scalar loads:
@@ -217,44 +218,12 @@ struct GeneralDragArgs {
     int n_drag;
 };
 
-// step_inc_mix_kernel (carried mode log-densities): 2..4 modes up to d = 64, 5 and 6 as far as
-// the state -- dq (K + 1) doubles per lane -- leaves the body its registers at two waves per SIMD
-// (K = 5: d <= 32, K = 6: d <= 28; measured at d = 30, ms per 1200 steps of 65 536 walkers:
-// K = 5 7.71 on the register-plane kernel -> 5.84 here; K = 6 at dq = 8 spills: 13.3 against ~8.6);
-// everything else: the general incremental kernels
-constexpr int kIncMixWideDq = 8;
-__host__ __device__ constexpr bool inc_mix_serves(int K, int dq)
-{
-    return K >= 2 && ((K <= 4 && dq <= 16) || (K <= 6 && dq <= kIncMixWideDq && dq * (K + 1) <= 50));
-}
-
-// step_duo_mix_kernel (incremental_duo.hip, round 6): the same step with TWO lanes per walker, each
-// holding 2 dq dimensions -- 2..4 modes while the residuals y_1 .. y_K of a lane (2 dq K doubles) leave
-// the body its registers at two waves per SIMD; x moves to LDS where it does not fit beside them
-// (duo_x_in_lds: two modes from d = 33 on, three from d = 25 on, four from d = 21 on).  K = 2: d <= 48;
-// K = 3: d <= 32; K = 4: d <= 24.
-constexpr int kDuoStateDoubles = 48;
-#ifndef MCMC_DUO_MAX_DQ
-#define MCMC_DUO_MAX_DQ 12
-#endif
-constexpr int kDuoMaxDq = MCMC_DUO_MAX_DQ;   // two modes up to d = 48 (round 6, late)
-__host__ __device__ constexpr bool duo_serves(int K, int dq)
-{
-    return K >= 2 && K <= 4 && dq <= kDuoMaxDq && 2 * dq * K <= kDuoStateDoubles;
-}
 // x, y_1 .. y_K of a lane in registers up to 50 doubles, x in LDS above -- measured (65 536 walkers, ms per
 // 40 d steps, x in LDS / in registers): K = 4 at d = 20 (50 doubles) 1.64 / 1.53; K = 3 at d = 28 (56) 2.43 / 2.90
 #ifndef MCMC_DUO_XLDS_ABOVE
 #define MCMC_DUO_XLDS_ABOVE 50   // (experiment hook)
 #endif
 __host__ __device__ constexpr bool duo_x_in_lds(int K, int dq) { return 2 * dq * (K + 1) > MCMC_DUO_XLDS_ABOVE; }
-
-// step_inc_duo_kernel (incremental_duo.hip, round 7): one mode, MODE 0, two lanes per walker up to d = 32
-constexpr int kDuo1MaxDq = 8;
-
-// periodic parameters step_inc_kernel<.., PER> serves (one mode, Metropolis steps, no emitted rows);
-// more: the general incremental kernels (incremental_any.hip)
-constexpr int kIncMaxPeriodic = 16;
 
 // Incremental evaluation (incremental_kernels.hip): one Gaussian mode, non-periodic priors,
 // one block; 2 <= d <= 128 with dq = ceil(d / 4) dimensions per lane, four lanes per walker.
@@ -352,6 +321,51 @@ struct BigKernels {
 // keeps the last one for mcmc_hip_last_step_kernel, so that reports quote the kernel that ran
 // instead of guessing it from the problem shape.
 extern "C" void mcmc_hip_note_step_kernel(const char* name);
+
+// ---- the launchers (extern "C", one per kernel family), declared HERE and nowhere else: the
+// translation unit that defines one and the host side that calls it both see this declaration, so
+// a signature that drifts is a compile error.  The host side (ctx.h defines MCMC_HIP_HOST_SIDE)
+// may find the launchers of the incremental kernels missing -- a developer build of a few
+// translation units -- and sees them as weak references; the definitions stay strong.
+#ifdef MCMC_HIP_HOST_SIDE
+#define MCMC_HIP_OPTIONAL __attribute__((weak))
+#else
+#define MCMC_HIP_OPTIONAL
+#endif
+// general_kernels.hip, blocked_kernels.hip
+extern "C" hipError_t mcmc_hip_launch_general_step(const mcmc::GeneralStepArgs* b, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_general_drag(const mcmc::GeneralDragArgs* g, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_pack_rows(const double* rows, const int* n_rows,
+                                                const long long* offset, double* out, int W,
+                                                int cap, int d, uint32_t walker0, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_blocked_basis(const mcmc::BlockedBasisArgs* a, int n_groups,
+                                                    hipStream_t st);
+// incremental_kernels.hip: one translation unit per range of dq = ceil(d / 4)
+extern "C" hipError_t mcmc_hip_launch_inc_step_1(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_inc_step_9(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_inc_step_17(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_inc_step_25(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+// ... and their EMIT instantiations (accepted rows stored, `emit: chains`): -DMCMC_INC_EMIT_TU
+extern "C" hipError_t mcmc_hip_launch_inc_emit_1(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_inc_emit_9(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_inc_emit_17(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_inc_emit_25(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_whiten_state(const double* x, double* y, const double* mean,
+                                                   const double* Lrow, int d, int W, int K,
+                                                   hipStream_t st) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_whiten_directions(const mcmc::IncDirArgs* a, int n_groups,
+                                                        hipStream_t st) MCMC_HIP_OPTIONAL;
+// incremental_any.hip: the general incremental kernel (any number of modes / periodic parameters)
+extern "C" hipError_t mcmc_hip_launch_inc_any(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_whiten_directions_planes(const mcmc::IncDirArgs*, int,
+                                                               hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" int mcmc_hip_inc_any_fits(int d, int n_modes, int n_periodic, int n_walkers,
+                                     int group_size) MCMC_HIP_OPTIONAL;
+// incremental_duo.hip (round 6): the incremental step of a mixture with TWO lanes per walker (K = 2 up to
+// d = 48, K = 3 up to d = 32, K = 4 up to d = 24: inc_choice.h duo_serves); one mode (MODE 0) up to d = 32
+extern "C" hipError_t mcmc_hip_launch_inc_duo_1(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_inc_duo_9(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+extern "C" hipError_t mcmc_hip_launch_inc_duo1(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
 
 #define MCMC_DECLARE_BIG(DP) extern "C" const mcmc::BigKernels* mcmc_hip_big_##DP() __attribute__((weak));
 #define MCMC_DECLARE_PAIR(D) extern "C" const mcmc::PairKernels* mcmc_hip_pair_##D() __attribute__((weak));

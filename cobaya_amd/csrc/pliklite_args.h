@@ -1,4 +1,4 @@
-// Kernel arguments of pliklite_kernels.hip (shared with capi.hip).
+// Kernel arguments of pliklite_kernels.hip (shared with capi_targets.hip).
 #pragma once
 #include "kernels.h"
 
@@ -81,3 +81,17 @@ struct PlChi2Args {
 };
 
 }  // namespace mcmc
+
+// the launchers of pliklite_kernels.hip: declared here alone, for the kernels' translation unit
+// and the host side
+extern "C" hipError_t mcmc_hip_launch_pl_walker(const mcmc::PlWalkerArgs* a, int accept, int propose,
+                                                hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_pl_prior(const double* t, int n, int d, const double* C,
+                                               uint32_t norm_mask, double uniform_logp, double* lp,
+                                               hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_pl_residual(const mcmc::PlResidualArgs* a, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_pl_bin(const mcmc::PlBinArgs* a, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_pl_residual_mfma(const mcmc::PlResidualMfmaArgs* a, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_pl_fused(const mcmc::PlFusedArgs* a, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_pl_chi2(const mcmc::PlChi2Args* a, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_pl_combine(const double* psum, double* chi2, int n, hipStream_t st);

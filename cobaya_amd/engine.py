@@ -56,6 +56,24 @@ class Config(C.Structure):
     ]
 
 
+class IncShape(C.Structure):
+    """mcmc_hip_inc_shape: the model and ensemble as far as the choice of the incremental kernel
+    depends on them (flags are 0 / 1; duo: -1 where it pays, 0 never, 1 wherever it serves)."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "d", "n_modes", "n_periodic", "n_drag", "n_walkers", "basis_group_size", "any_normal",
+        "one_box", "box_lo_is_zero", "has_1d_block", "emit", "duo")]
+
+
+class IncChoice(C.Structure):
+    """mcmc_hip_inc_choice: the kernel family (INC_*) and what that kernel carries."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "family", "reason", "dq_lo", "carry", "carry_modes", "carry_prior", "carry_periodic",
+        "fold", "chunk_steps", "colb", "thins_on_device", "box")]
+
+
+(INC_NOT_SERVED, INC_STEP, INC_STEP_EMIT, INC_MIX, INC_ANY, INC_DRAG, INC_DUO_MIX,
+ INC_DUO_ONE) = range(8)
+
 # every symbol include/mcmc_hip.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = [
@@ -64,6 +82,7 @@ SYMBOLS = [
     ("mcmc_hip_dim_supported", C.c_int, [C.c_int]),
     ("mcmc_hip_max_dim", C.c_int32, []),
     ("mcmc_hip_incremental_supported", C.c_int, [C.c_int32] * 6),
+    ("mcmc_hip_incremental_choice", C.c_int, [C.POINTER(IncShape), C.POINTER(IncChoice)]),
     ("mcmc_hip_create", C.c_int, [C.POINTER(Config), C.POINTER(_H)]),
     ("mcmc_hip_destroy", None, [_H]),
     ("mcmc_hip_set_prior", C.c_int, [_H, c_int32_p, c_double_p, c_double_p, c_int32_p]),
@@ -214,6 +233,22 @@ def incremental_supported(d, n_modes, n_periodic, n_drag, n_walkers, basis_group
     shape?  (mcmc_hip_incremental_supported: a pure function of the library, no device.)"""
     return bool(load_library().mcmc_hip_incremental_supported(
         int(d), int(n_modes), int(n_periodic), int(n_drag), int(n_walkers), int(basis_group_size)))
+
+
+def incremental_choice(d, n_modes, n_periodic=0, n_drag=0, n_walkers=65536, basis_group_size=256,
+                       any_normal=False, one_box=False, box_lo_is_zero=False, has_1d_block=False,
+                       emit=False, duo=-1):
+    """Which incremental step kernel serves this shape and what it carries, as a dict of the
+    fields of mcmc_hip_inc_choice (mcmc_hip_incremental_choice: the library's one rule, a pure
+    function -- no device).  family == INC_NOT_SERVED: `reason` says why."""
+    shape = IncShape(int(d), int(n_modes), int(n_periodic), int(n_drag), int(n_walkers),
+                     int(basis_group_size), int(any_normal), int(one_box), int(box_lo_is_zero),
+                     int(has_1d_block), int(emit), int(duo))
+    out = IncChoice()
+    rc = load_library().mcmc_hip_incremental_choice(C.byref(shape), C.byref(out))
+    if rc != OK:
+        raise EngineError(rc, "mcmc_hip_incremental_choice is not served by this library")
+    return {n: int(getattr(out, n)) for n, _ in IncChoice._fields_}
 
 
 def gelman_rubin(n_chains, sum_N, sum_Ncov, sum_mean, sum_mm):

@@ -209,7 +209,7 @@ class EnsembleMCMC:
     fallback_covmat_scale = 4.0  # sampler.py:474
     _LoggedError = LoggedError   # the hosted class raises cobaya.log.LoggedError instead
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
-    MAX_DIM = 128    # capi.hip: kMaxDimBig, every path (mixtures: at most 64 modes, model.py)
+    MAX_DIM = 128    # ctx.h: kMaxDimBig, every path (mixtures: at most 64 modes, model.py)
     HUGE_MAX_MODES = 4   # 128 < d <= max_dim(): huge_kernels.hip (huge_args.h: kHugeMaxModes)
 
     def _max_dim(self):

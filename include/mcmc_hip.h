@@ -98,6 +98,42 @@ MCMC_HIP_API int32_t mcmc_hip_max_dim(void);
 MCMC_HIP_API int mcmc_hip_incremental_supported(int32_t d, int32_t n_modes, int32_t n_periodic, int32_t n_drag,
                                    int32_t n_walkers, int32_t basis_group_size);
 
+/* The rule behind mcmc_hip_incremental_supported in full: which incremental step kernel serves a
+ * shape and what that kernel carries.  A pure function as well (no device), so the rule is tested
+ * where there is no GPU.  Flags are 0 / 1. */
+typedef struct mcmc_hip_inc_shape {
+    int32_t d, n_modes, n_periodic;
+    int32_t n_drag;             /* interpolation steps per dragging step; 0: Metropolis steps */
+    int32_t n_walkers, basis_group_size;
+    int32_t any_normal;         /* some prior is normal */
+    int32_t one_box;            /* every parameter uniform on the same interval */
+    int32_t box_lo_is_zero;     /* ... which begins at 0 */
+    int32_t has_1d_block;       /* a parameter block of one parameter */
+    int32_t emit;               /* emit_capacity > 0 */
+    int32_t duo;                /* two lanes per walker: -1 where it pays, 0 never, 1 wherever it serves */
+} mcmc_hip_inc_shape;
+#define MCMC_HIP_INC_NOT_SERVED 0
+#define MCMC_HIP_INC_STEP 1       /* one mode, four lanes per walker */
+#define MCMC_HIP_INC_STEP_EMIT 2  /* ... with emitted rows */
+#define MCMC_HIP_INC_MIX 3        /* mixture with carried mode log-densities, four lanes */
+#define MCMC_HIP_INC_ANY 4        /* the general kernels */
+#define MCMC_HIP_INC_DRAG 5       /* dragging */
+#define MCMC_HIP_INC_DUO_MIX 6    /* mixture, two lanes per walker */
+#define MCMC_HIP_INC_DUO_ONE 7    /* one mode, two lanes per walker */
+typedef struct mcmc_hip_inc_choice {
+    int32_t family;             /* MCMC_HIP_INC_* */
+    int32_t reason;             /* not served: 1 shape out of range, 2 dragging with a mixture / a periodic
+                                 * parameter / too many columns, 3 the general kernel's state does not fit,
+                                 * 4 emitted rows with dragging; served: 0 */
+    int32_t dq_lo;              /* first dq = ceil(d / 4) of the launcher's translation unit; 0: one launcher */
+    int32_t carry, carry_modes, carry_prior, carry_periodic, fold;
+    int32_t chunk_steps;        /* dragging steps per LDS chunk */
+    int32_t colb;               /* doubles per direction column */
+    int32_t thins_on_device;    /* mcmc_hip_set_emit_thin is served */
+    int32_t box;                /* the step kernel takes the one-interval path of the prior */
+} mcmc_hip_inc_choice;
+MCMC_HIP_API int mcmc_hip_incremental_choice(const mcmc_hip_inc_shape* shape, mcmc_hip_inc_choice* out);
+
 /* Sampler.__init__ + MCMC.initialize (cobaya/sampler.py:257-322, mcmc.py:111-271) */
 MCMC_HIP_API int mcmc_hip_create(const mcmc_hip_config* cfg, mcmc_hip_ctx** out);
 MCMC_HIP_API void mcmc_hip_destroy(mcmc_hip_ctx* h);

@@ -166,7 +166,7 @@ def test_mixture_bench_launch_bit_exact_on_two_lanes(K):
 
 @pytest.mark.parametrize("W,want", [(32768, "step_inc_mix_kernel"), (49152, "step_duo_mix_kernel")])
 def test_the_launcher_takes_two_lanes_from_the_measured_size_on(W, want):
-    """capi.hip: kDuoMinWalkers = 49 152 (profiles/r06_duo.txt): below, a two-mode mixture runs with four
+    """inc_choice.h: kDuoMinWalkers = 49 152 (profiles/r06_duo.txt): below, a two-mode mixture runs with four
     lanes per walker, from there on with two -- either way bit for bit the oracle's walkers."""
     d, gs, bgs = 30, 256, 1024
     eng, prob, st, mean, cov = _pair(d, W, gs, bgs, 0, K=2)

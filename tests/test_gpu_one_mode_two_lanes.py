@@ -15,7 +15,7 @@ from tests.test_gpu_bench_geometry import _compare, _pair  # noqa: E402
 from tests.test_gpu_parity import assert_bit_equal, compare_state, make_pair  # noqa: E402
 
 TWO = "two lanes"
-DUO1_MIN_WALKERS = 65536   # capi.hip: kDuo1MinWalkers
+DUO1_MIN_WALKERS = 65536   # inc_choice.h: kDuo1MinWalkers
 
 
 @pytest.mark.parametrize("offset", [0, 7 * 65536], ids=["rank0", "rank7-of-configs2"])

@@ -832,7 +832,7 @@ def test_incremental_steps_bit_exact(d, W, gs, normal, T):
                   "drag_last_slow": 0, "drag_steps": 3})])
 def test_directions_computed_ahead_never_change_the_results(d, W, gs, kw):
     """The directions of the next launch are computed on a second stream while a step kernel
-    runs (capi.hip, DirSet), on the guess that the next call is like this one.  Whatever comes
+    runs (ctx.h, DirSet), on the guess that the next call is like this one.  Whatever comes
     instead -- the same call (the set is used), another length, a new proposal covariance, a
     restored state -- the states are those of the oracle, bit for bit: a set computed ahead is
     dropped when it does not fit."""
@@ -1542,7 +1542,7 @@ def test_device_checkpoint_payload_read_out():
     (12, 256, 64, {"blocks": [[0, 1, 2], [3], list(range(4, 12))], "over": [1, 2, 3]}),
     (30, 256, 64, {"cap": 400})])
 def test_calls_of_several_launches_refresh_y_inside_the_step_kernel(d, W, gs, kw):
-    """Round 5 (capi.hip plan_span, step_inc_kernel `anchor & 2`): a call that spans several refresh
+    """Round 5 (capi_incremental.hip plan_span, step_inc_kernel `anchor & 2`): a call that spans several refresh
     intervals forms its directions as ONE set and every launch after the first refreshes
     y = L^-1 (x - mu) itself -- deviations and eight-column tiles of L^-1 through LDS, the same
     ascending chains as whiten_state_kernel -- before it re-anchors the carried log-likelihood.

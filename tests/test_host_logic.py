@@ -86,7 +86,7 @@ def test_capi_exports_every_declared_symbol():
                          check=True).stdout.split()
     exported = {t for t in dyn if t.startswith("mcmc_hip") or "mcmc" in t}
     assert exported == declared, sorted(exported ^ declared)
-    with open(os.path.join(ROOT, "cobaya_amd", "csrc", "capi.hip")) as f:
+    with open(os.path.join(ROOT, "cobaya_amd", "csrc", "ctx.h")) as f:   # (the lookups' getters)
         capi = f.read()
     assert {int(x) for x in re.findall(r"MCMC_DECLARE_PAIR\((\d+)\)", capi)} == set(B.PAIR_DIMS)
     assert {int(x) for x in re.findall(r"MCMC_DECLARE_BIG\((\d+)\)", capi)} == set(B.BIG_DPS)
@@ -778,6 +778,142 @@ def test_incremental_supported_is_a_pure_function_of_the_shape():
     assert not ok(30, 1, 0, 0, W, 100) and not ok(30, 1, 0, 0, 1000, 256)
 
 
+def _golden_inc_grid():
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_golden_inc_supported as G
+    g = np.load(os.path.join(ROOT, "tests", "golden", "inc_supported_parent.npz"))
+    axes = {k: g[k] for k in G.AXES}
+    return G, axes, np.unpackbits(g["bits"])[:int(g["n"])]
+
+
+def test_incremental_supported_answers_as_before_the_rule_moved():
+    """The rule "which incremental kernel serves this shape" lives in csrc/inc_choice.h alone; the
+    table of mcmc_hip_incremental_supported over 150 930 shapes (every d in 1..129, mode counts
+    around each threshold, periodic counts around 16, dragging, three ensembles) was recorded from
+    a library built at the commit BEFORE it moved there (tests/golden/make_golden_inc_supported.py)
+    and is the same now, shape by shape."""
+    G, axes, parent = _golden_inc_grid()
+    for k, v in G.AXES.items():
+        assert np.array_equal(axes[k], v), k          # the committed table is of the committed grid
+    now = G.table(E.load_library(), axes)
+    assert now.size == parent.size == 150930
+    bad = np.flatnonzero(now != parent)
+    assert bad.size == 0, [s for i, s in enumerate(G.shapes(axes)) if i in set(bad[:5].tolist())]
+    assert 15000 < int(now.sum()) < 25000             # (neither table is all zeros or all ones)
+
+
+def test_incremental_choice_is_the_rule_the_oracle_engine_restates():
+    """mcmc_hip_incremental_choice against the Python restatement in tests/oracle_engine.py
+    (carries_modes, carries_periodic -- what the oracle of every GPU parity test is configured
+    with): equal over the grid of the golden table times emit in {0, 1}.  Shapes no engine can have
+    (reason 1: d < 2 or d > 128, no mode or more than 64, more periodic parameters than parameters
+    -- mcmc_hip_create and the setters refuse them) are where the C rule carries nothing; the
+    restatement is not asked there.  The answer for emit = 0 without a one-parameter block is also
+    the one of mcmc_hip_incremental_supported."""
+    from tests.oracle_engine import OracleEngine
+    G, axes, parent = _golden_inc_grid()
+    lib = E.load_library()
+    shape, out = E.IncShape(), E.IncChoice()
+    double = object.__new__(OracleEngine)
+    double.incremental = True
+    n_invalid = n = 0
+    for i, (d, K, per, nd, W, bgs) in enumerate(G.shapes(axes)):
+        for emit in (0, 1):
+            shape.d, shape.n_modes, shape.n_periodic, shape.n_drag = d, K, per, nd
+            shape.n_walkers, shape.basis_group_size, shape.emit, shape.duo = W, bgs, emit, -1
+            assert lib.mcmc_hip_incremental_choice(C_byref(shape), C_byref(out)) == 0
+            if not emit:
+                assert (out.family != E.INC_NOT_SERVED) == bool(parent[i]), (d, K, per, nd, W, bgs)
+            assert (out.family == E.INC_NOT_SERVED) == (out.reason != 0)
+            if out.reason == 1:
+                n_invalid += 1
+                assert not (out.carry or out.carry_modes or out.carry_prior or out.carry_periodic)
+                continue
+            n += 1
+            double.d, double.K, double.cap = d, K, 48 * emit
+            double._prior = (None, None, None, np.arange(d) < per)
+            double._blocking = {"drag_last_slow": 0} if nd else None
+            assert bool(out.carry_modes) == double.carries_modes(), (d, K, per, nd, W, bgs, emit)
+            assert bool(out.carry_periodic) == double.carries_periodic(), (d, K, per, nd, W, bgs, emit)
+    assert n + n_invalid == 2 * 150930 and n > 200000
+
+
+def C_byref(x):
+    import ctypes
+    return ctypes.byref(x)
+
+
+def test_the_thresholds_of_the_incremental_kernels_without_a_gpu():
+    """What the GPU tests pin through last_step_kernel(), asked of the rule itself
+    (mcmc_hip_incremental_choice; inc_choice.h)."""
+    ch = E.incremental_choice
+    fam = lambda *a, **k: ch(*a, **k)["family"]
+    # two modes at d = 30: two lanes per walker from 49 152 walkers on (kDuoMinWalkers)
+    assert fam(30, 2, n_walkers=32768) == E.INC_MIX
+    assert fam(30, 2, n_walkers=49152) == E.INC_DUO_MIX
+    # one mode, one box [0, hi]: two lanes from 65 536 walkers on (kDuo1MinWalkers) ...
+    box = dict(one_box=True, box_lo_is_zero=True)
+    assert fam(30, 1, n_walkers=65536, **box) == E.INC_DUO_ONE
+    assert fam(30, 1, n_walkers=49152, **box) == E.INC_STEP
+    # ... not with lo != 0, a one-parameter block, or workgroups that straddle basis groups
+    assert fam(30, 1, n_walkers=65536, one_box=True, box_lo_is_zero=False) == E.INC_STEP
+    assert fam(30, 1, n_walkers=65536, has_1d_block=True, **box) == E.INC_STEP
+    assert fam(30, 1, n_walkers=65536, basis_group_size=64, **box) == E.INC_STEP
+    assert fam(30, 1, n_walkers=65536, basis_group_size=192 * 2, **box) == E.INC_NOT_SERVED   # (65 536 % 384)
+    assert fam(30, 1, n_walkers=65536 * 3, basis_group_size=192, **box) == E.INC_STEP
+    # duo = 0 never gives a two-lane kernel; duo = 1 wherever one serves
+    for W in (256, 49152, 65536, 131072):
+        assert fam(30, 1, n_walkers=W, duo=0, **box) == E.INC_STEP
+        assert fam(30, 2, n_walkers=W, duo=0) == E.INC_MIX
+        assert fam(30, 1, n_walkers=W, duo=1, **box) == E.INC_DUO_ONE
+        assert fam(30, 2, n_walkers=W, duo=1) == E.INC_DUO_MIX
+    # the reach of the two-lane mixture kernels: K = 3 up to d = 32, K = 4 up to d = 24
+    assert fam(36, 3) == E.INC_MIX and fam(32, 3) == E.INC_DUO_MIX
+    assert fam(24, 4) == E.INC_DUO_MIX and fam(28, 4) == E.INC_MIX
+    # five modes at d = 30: a mixture kernel that carries the modes; seven: the general kernel
+    c = ch(30, 5)
+    assert c["family"] == E.INC_MIX and c["carry_modes"] and c["colb"] == 4 * 6 * 8
+    c = ch(30, 7)
+    assert c["family"] == E.INC_ANY and not c["carry_modes"] and c["dq_lo"] == 0
+    # periodic parameters: 16 on the four-lane kernel, 17 on the general one
+    c = ch(30, 1, n_periodic=16)
+    assert c["family"] == E.INC_STEP and c["carry"] and c["carry_periodic"] and not c["fold"]
+    c = ch(30, 1, n_periodic=17)
+    assert c["family"] == E.INC_ANY and not c["carry"] and not c["carry_periodic"]
+    # emitted rows: one mode stays, anything else is general
+    assert fam(30, 1, emit=True) == E.INC_STEP_EMIT
+    assert fam(30, 2, emit=True) == fam(30, 1, n_periodic=1, emit=True) == E.INC_ANY
+    assert fam(30, 1, has_1d_block=True, emit=True) == E.INC_ANY
+    assert fam(30, 1, has_1d_block=True) == E.INC_STEP
+    assert not ch(30, 2, emit=True)["carry_modes"] and ch(30, 2)["carry_modes"]
+    # dragging: one mode, no mixture, no emitted rows
+    c = ch(27, 1, n_drag=7)
+    assert c["family"] == E.INC_DRAG and c["chunk_steps"] == (1024 // 28) // 8 and not c["thins_on_device"]
+    c = ch(27, 2, n_drag=7)
+    assert c["family"] == E.INC_NOT_SERVED and c["reason"] == 2
+    assert ch(27, 1, n_drag=7, emit=True)["reason"] == 4
+    assert ch(128, 16)["reason"] == 3 and ch(1, 1)["reason"] == 1
+    # fold (the kernel refreshes y itself, a direction set spans calls): not with a periodic
+    # parameter, not with a carried log-prior from d = 113 on
+    assert ch(30, 1)["fold"] and ch(30, 1, any_normal=True)["fold"] and ch(30, 1, any_normal=True)["carry_prior"]
+    assert not ch(30, 1, n_periodic=1)["fold"]
+    assert ch(112, 1, any_normal=True)["fold"] and not ch(113, 1, any_normal=True)["fold"]
+    assert ch(113, 1, any_normal=True)["carry_prior"] and ch(113, 1)["fold"]
+    # the launcher's translation unit
+    assert [ch(d, 1)["dq_lo"] for d in (32, 33, 64, 65, 96, 97, 128)] == [1, 9, 9, 17, 17, 25, 25]
+    assert ch(30, 2, n_walkers=65536)["dq_lo"] == 1 and ch(40, 2, n_walkers=65536)["dq_lo"] == 9
+
+
+def test_inc_choice_header_is_plain_cxx(tmp_path):
+    """csrc/inc_choice.h holds the rule and nothing of HIP: it compiles with the host compiler
+    alone, so the rule can be reasoned about -- and unit-tested -- without the kernels."""
+    src = tmp_path / "choice.cpp"
+    src.write_text('#include "inc_choice.h"\n'
+                   'int main() { return mcmc::inc_choose(mcmc::IncShape{}, false).family; }\n')
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only",
+                    "-I", os.path.join(ROOT, "cobaya_amd", "csrc"), str(src)], check=True)
+
+
 def test_window_sums_are_a_fixed_function_of_the_intervals_and_cost_log_n():
     """Round 4: the host-path checkpoint sums the window (the later half of the run) in
     O(log n) array additions -- `WindowSums`: aligned dyadic blocks over the run's interval
@@ -985,6 +1121,11 @@ def test_compat_stubs_of_an_older_library_answer_no(tmp_path, monkeypatch):
         assert old.mcmc_hip_get_thin_carry(None, None) == E.ERR_ARG
         assert old.mcmc_hip_incremental_supported(30, 1, 0, 0, 65536, 4096) == 0
         assert old.mcmc_hip_incremental_carries_modes(None) == 0
+        # (a rule it cannot answer is an error, not a choice of zeros)
+        assert old.mcmc_hip_incremental_choice(None, None) == E.ERR_ARG
+        with pytest.raises(E.EngineError):
+            E._lib = old
+            E.incremental_choice(30, 1)
     finally:
         E._lib = saved
     monkeypatch.delenv("MCMC_HIP_LIB_COMPAT")
