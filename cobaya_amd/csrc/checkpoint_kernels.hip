@@ -283,7 +283,8 @@ __global__ void __launch_bounds__(256) ckpt_solve_kernel(const CkptSolveArgs a)
     const int n = a.d, t = threadIdx.x, nt = blockDim.x, nn = n * n;
     const double* __restrict__ P = a.payload;
     double* __restrict__ out = a.out;
-    // the workspace: LDS where 7 n^2 + 5 n doubles fit (n <= 50), else global memory (L2)
+    // the workspace: LDS where 7 n^2 + 5 n doubles fit in 150 KB (n <= 52), global memory (L2)
+    // from n = 53 on (mcmc_hip_launch_ckpt_solve)
     extern __shared__ __attribute__((aligned(16))) double ck_lds[];
     PT Wm;                           // mean of covs
     if constexpr (IN_LDS) Wm = (lds_dp)ck_lds; else Wm = a.ws;
@@ -363,6 +364,8 @@ __global__ void __launch_bounds__(256) ckpt_solve_kernel(const CkptSolveArgs a)
             cov[e] = a.i_of_j ? Wm[a.i_of_j[i] * n + a.i_of_j[j]] : Wm[e];
         }
         __syncthreads();
+        // (defensive, as in mcmc_hip_set_proposal_cov: behind status == 0 the diagonal is positive and
+        // finite -- nW has it over a positive scale, and its Cholesky factorisation has succeeded)
         if (t == 0) {
             flag = 1;
             for (int i = 0; i < n; ++i)

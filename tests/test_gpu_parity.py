@@ -1080,6 +1080,7 @@ def test_own_basis_steps_bit_exact(d, W, gs, K, extra):
     gsum, S = O.moments(st.x, gs, shift=shift)
     n, g_gs, g_S = eng.read_moments()
     assert_bit_equal(g_gs, gsum, "group sums")
+    assert_bit_equal(g_S, S, "pooled second moments")
     eng.close()
 
 
