@@ -104,6 +104,7 @@ def translation_units(dims, big=True):
             ("general_kernels.hip", "general", []),
             ("pliklite_kernels.hip", "pliklite", []),
             ("checkpoint_kernels.hip", "checkpoint", []),
+            ("marginal_kernels.hip", "marginal", []),   # streaming 1-D / 2-D marginal histograms
             ("comm.hip", "comm", [])]   # the RCCL communicator (bound at run time)
     tus += [("incremental_kernels.hip", f"incremental_{lo}", [f"-DMCMC_DQ_LO={lo}", f"-DMCMC_DQ_HI={hi}"])
             for lo, hi in INC_DQ_RANGES]
@@ -122,7 +123,8 @@ def translation_units(dims, big=True):
             ("capi_targets.hip", "capi_targets", []),
             ("capi_incremental.hip", "capi_incremental", []),
             ("capi_rows.hip", "capi_rows", []),
-            ("capi_checkpoint.hip", "capi_checkpoint", [])]
+            ("capi_checkpoint.hip", "capi_checkpoint", []),
+            ("capi_marginals.hip", "capi_marginals", [])]
     return tus
 
 

@@ -380,6 +380,9 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     h->bd.ring.release(); h->bd.bounds.release(); h->bd.payload.release();
     if (h->bd.pin) (void)hipHostFree(h->bd.pin);
     if (h->ck.pin_out) (void)hipHostFree(h->ck.pin_out);
+    h->mg.slab.release(); h->mg.entries.release();
+    if (h->mg.pin) (void)hipHostFree(h->mg.pin);
+    if (h->mg.ev) (void)hipEventDestroy(h->mg.ev);
     if (h->ck.ev) (void)hipEventDestroy(h->ck.ev);
     if (h->pin_mom) (void)hipHostFree(h->pin_mom);
     if (h->pin_T) (void)hipHostFree(h->pin_T);

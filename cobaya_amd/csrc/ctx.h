@@ -21,6 +21,7 @@
 #include "pliklite_args.h"
 #include "function_args.h"
 #include "checkpoint_args.h"
+#include "marginal_args.h"
 #include "comm.h"
 #include "inc_choice.h"
 
@@ -257,6 +258,19 @@ struct mcmc_hip_ctx {
         int n_slots = 0;
         double* pin = nullptr;     // [1 + 4 d + G d 2]
     } bd;
+    // streaming marginal histograms (mcmc_hip_marginals_*; marginal_kernels.hip): the uint64 slab
+    // [1-D entries: under, over, bins1 | pairs: outside, bins2 x bins2], its pinned read-out
+    struct Marginals {
+        DevBuf<unsigned long long> slab;
+        DevBuf<mcmc::MargEntry> entries;
+        unsigned long long* pin = nullptr;     // [n_counters]
+        size_t n_counters = 0, off_pairs = 0;
+        int n1 = 0, n2 = 0, bins1 = 0, bins2 = 0, n_entries = 0, lds_words = 0;
+        int64_t n_acc = 0;                     // accumulations since the last request / set
+        int64_t pend_n = 0;                    // ... of the pending read-out
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+    } mg;
     // the walker shards' communicator (comm.hip; not owned): the device checkpoint all-reduces
     // its payload over it in stream order
     mcmc_hip_comm* comm = nullptr;

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(CSRC, "libmcmc_hip.so")
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
 c_int64_p = C.POINTER(C.c_int64)
+c_uint64_p = C.POINTER(C.c_uint64)
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOT_PD, ERR_STATE, ERR_STUCK = 0, -1, -2, -3, -4, -5
 ERR_TARGET, ERR_CALLBACK = -6, -7
@@ -141,6 +142,14 @@ SYMBOLS = [
     ("mcmc_hip_set_moments", C.c_int, [_H, C.c_int64, c_double_p, c_double_p]),
     ("mcmc_hip_request_moments", C.c_int, [_H]),
     ("mcmc_hip_fetch_moments", C.c_int, [_H, c_int64_p, c_double_p, c_double_p, c_int64_p]),
+    ("mcmc_hip_marginals_configure", C.c_int, [_H, C.c_int32, c_int32_p, C.c_int32, C.c_int32,
+                                               c_int32_p, C.c_int32, c_double_p, c_double_p]),
+    ("mcmc_hip_marginals_accumulate", C.c_int, [_H]),
+    ("mcmc_hip_marginals_request", C.c_int, [_H]),
+    ("mcmc_hip_marginals_fetch", C.c_int, [_H, c_uint64_p, C.c_int64, c_int64_p]),
+    ("mcmc_hip_marginals_set", C.c_int, [_H, c_uint64_p, C.c_int64, C.c_int64]),
+    ("mcmc_hip_marginals_layout", C.c_int, [_H, c_int64_p, c_int32_p, c_int32_p, c_int32_p,
+                                            c_int32_p, c_int64_p]),
     ("mcmc_hip_gelman_rubin", C.c_int, [C.c_int32, C.c_double, C.c_double, c_double_p,
                                         c_double_p, c_double_p, c_double_p, c_double_p]),
     ("mcmc_hip_enable_timing", C.c_int, [_H, C.c_int32]),
@@ -784,6 +793,54 @@ class Engine:
         self._check(self._lib.mcmc_hip_fetch_moments(self._h, C.byref(n), _dp(gs), _dp(S),
                                                      c.ctypes.data_as(c_int64_p)))
         return n.value, gs, S, {"steps": int(c[0]), "accepted": int(c[1])}
+
+    # -- streaming marginal histograms
+    def configure_marginals(self, dims1=(), bins1=128, pairs=(), bins2=32, lo=None, hi=None):
+        """The histograms every `accumulate_marginals` adds the ensemble to (mcmc_hip_marginals_configure):
+        `dims1` sampler indices with `bins1` bins each, `pairs` ordered (i, j) with `bins2` x `bins2`
+        bins each, `lo` / `hi` [d] the fixed range of every parameter in use.  Nothing listed: off."""
+        dims1 = np.ascontiguousarray(dims1, dtype=np.int32).reshape(-1)
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        n1, n2 = len(dims1), len(pairs)
+        lo = _f64(lo, (self.d,)) if (n1 or n2) else None
+        hi = _f64(hi, (self.d,)) if (n1 or n2) else None
+        self._check(self._lib.mcmc_hip_marginals_configure(
+            self._h, n1, _ip(dims1) if n1 else None, int(bins1), n2, _ip(pairs) if n2 else None,
+            int(bins2), _dp(lo) if lo is not None else None, _dp(hi) if hi is not None else None))
+
+    def marginals_layout(self):
+        """{"n_counters", "n1", "bins1", "n2", "bins2", "offset_pairs"} of the slab
+        (mcmc_hip_marginals_layout); n_counters == 0: the feature is off."""
+        n, off = C.c_int64(), C.c_int64()
+        v = [C.c_int32() for _ in range(4)]
+        self._check(self._lib.mcmc_hip_marginals_layout(self._h, C.byref(n), C.byref(v[0]), C.byref(v[1]),
+                                                        C.byref(v[2]), C.byref(v[3]), C.byref(off)))
+        return {"n_counters": n.value, "n1": v[0].value, "bins1": v[1].value, "n2": v[2].value,
+                "bins2": v[3].value, "offset_pairs": off.value}
+
+    def accumulate_marginals(self):
+        """Queue one accumulation: every walker of this process, once, into every histogram."""
+        self._check(self._lib.mcmc_hip_marginals_accumulate(self._h))
+
+    def request_marginals(self):
+        """Queue the read-out and the reset of the slab behind the work already in the stream."""
+        self._check(self._lib.mcmc_hip_marginals_request(self._h))
+
+    def fetch_marginals(self):
+        """(counts[n_counters] uint64, n_accumulations) of the pending request; waits for its copy
+        only."""
+        n = self.marginals_layout()["n_counters"]
+        out = np.zeros(n, np.uint64)
+        k = C.c_int64()
+        self._check(self._lib.mcmc_hip_marginals_fetch(self._h, out.ctypes.data_as(c_uint64_p), n,
+                                                       C.byref(k)))
+        return out, k.value
+
+    def marginals_set(self, counts, n_accumulations):
+        """Restore the counts of an unfinished interval (resume)."""
+        c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        self._check(self._lib.mcmc_hip_marginals_set(self._h, c.ctypes.data_as(c_uint64_p), len(c),
+                                                     int(n_accumulations)))
 
     # -- the checkpoint on the device
     def checkpoint_set_ring(self, intervals=(), min_capacity=16, first_index=0):

@@ -1,0 +1,300 @@
+"""Streaming marginal histograms of the ensemble: the product (`Marginals`) and the sampler
+option behind it (`parse_option`, `resolve_ranges`).
+
+The counts come from the engine (mcmc_hip_marginals_*; marginal_kernels.hip), which adds every
+walker of every moment snapshot of the window -- not only the rows `max_rows` retains.  The rule
+("Marginals"): on an axis of B bins over [lo, hi] a value is in range iff
+lo <= x <= hi and falls in bin min(floor((x - lo) * s), B - 1) with s = B / (hi - lo); x == hi
+falls in the last bin, a value on an interior edge in the upper one.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MAX_BINS_1D = 1024          # marginal_args.h: kMargMaxBins1
+MAX_BINS_2D = 64            # marginal_args.h: kMargMaxBins2
+MAX_SLAB_BYTES = 64 << 20   # the uint64 slab (and its pinned read-out) one process may take
+OPTION_KEYS = ("params", "pairs", "bins", "bins2d", "ranges")
+
+
+class MarginalsError(ValueError):
+    """A `marginals` option (or a pair of products) that cannot be served; the message begins
+    with the option's name."""
+
+
+def slab_size(n1, bins, n2, bins2d):
+    """Counters of the slab: per 1-D entry [under, over, bins], per pair [outside, bins2d^2]."""
+    return (n1 * (bins + 2) if n1 else 0) + (n2 * (bins2d * bins2d + 1) if n2 else 0)
+
+
+class Marginals:
+    """1-D and 2-D histograms over fixed ranges.
+
+    `params`: names of the 1-D entries; `pairs`: (row name, column name) of the 2-D entries;
+    `ranges`: {name: (lo, hi)} of every name in use; `slab`: the uint64 counters in the engine's
+    layout (1-D entry k at k (bins + 2): [under, over, c_0 ..]; pair p behind them at
+    p (bins2d^2 + 1): [outside, c_00 ..] row-major, first name = row); `n_accumulations`: ensemble
+    snapshots added; `n_samples`: walkers added (accumulations x walkers)."""
+
+    def __init__(self, params, pairs, bins, bins2d, ranges, slab=None, n_accumulations=0,
+                 n_samples=0):
+        self.params = [str(p) for p in params]
+        self.pairs = [(str(a), str(b)) for a, b in pairs]
+        self.bins, self.bins2d = int(bins), int(bins2d)
+        self.ranges = {str(k): (float(v[0]), float(v[1])) for k, v in ranges.items()}
+        for name in self.names_in_use():
+            if name not in self.ranges:
+                raise MarginalsError(f"marginals: no range for parameter {name!r}")
+        n = slab_size(len(self.params), self.bins, len(self.pairs), self.bins2d)
+        self.slab = (np.zeros(n, np.uint64) if slab is None
+                     else np.array(slab, dtype=np.uint64).reshape(-1))
+        if len(self.slab) != n:
+            raise MarginalsError(f"marginals: this layout holds {n} counters, got {len(self.slab)}")
+        self.n_accumulations, self.n_samples = int(n_accumulations), int(n_samples)
+
+    # -- layout
+    def names_in_use(self):
+        seen = list(self.params)
+        for a, b in self.pairs:
+            seen += [n for n in (a, b) if n not in seen]
+        return seen
+
+    def _layout(self):
+        return (tuple(self.params), tuple(self.pairs), self.bins, self.bins2d,
+                tuple((n,) + self.ranges[n] for n in self.names_in_use()))
+
+    def _entry(self, name):
+        try:
+            k = self.params.index(name)
+        except ValueError:
+            raise KeyError(f"no 1-D marginal of {name!r} (have {self.params})") from None
+        return self.slab[k * (self.bins + 2):(k + 1) * (self.bins + 2)]
+
+    def _entry2d(self, a, b):
+        try:
+            p = self.pairs.index((a, b))
+        except ValueError:
+            raise KeyError(f"no 2-D marginal of ({a!r}, {b!r}) (have {self.pairs}; the order "
+                           "matters: the first name is the row)") from None
+        n2 = self.bins2d * self.bins2d + 1
+        off = len(self.params) * (self.bins + 2) if self.params else 0
+        return self.slab[off + p * n2:off + (p + 1) * n2]
+
+    # -- counts
+    def counts(self, name):
+        """uint64 [bins]: the walkers per bin of `name`."""
+        return self._entry(name)[2:].copy()
+
+    def counts2d(self, a, b):
+        """uint64 [bins2d, bins2d]: rows follow `a`, columns `b`."""
+        return self._entry2d(a, b)[1:].reshape(self.bins2d, self.bins2d).copy()
+
+    def outside(self, name, b=None):
+        """1-D: (under, over) of `name`; with a second name the `outside` count of that pair
+        (a walker either coordinate of which left its range)."""
+        if b is not None:
+            return int(self._entry2d(name, b)[0])
+        e = self._entry(name)
+        return int(e[0]), int(e[1])
+
+    def edges(self, name, bins=None):
+        """The bins + 1 edges of `name` (`bins`: default the 1-D bin count; pass `bins2d` for the
+        axis of a pair)."""
+        lo, hi = self.ranges[name]
+        return np.linspace(lo, hi, (self.bins if bins is None else int(bins)) + 1)
+
+    # -- derived
+    def density(self, name):
+        """Counts normalised to integrate to 1 over [lo, hi] (what fell outside is left out)."""
+        c = self.counts(name).astype(np.float64)
+        lo, hi = self.ranges[name]
+        total = c.sum()
+        if total == 0:
+            raise MarginalsError(f"marginals: no sample of {name!r} inside its range")
+        return c / (total * ((hi - lo) / self.bins))
+
+    def density2d(self, a, b):
+        c = self.counts2d(a, b).astype(np.float64)
+        (alo, ahi), (blo, bhi) = self.ranges[a], self.ranges[b]
+        total = c.sum()
+        if total == 0:
+            raise MarginalsError(f"marginals: no sample of ({a!r}, {b!r}) inside its ranges")
+        return c / (total * ((ahi - alo) / self.bins2d) * ((bhi - blo) / self.bins2d))
+
+    def mean(self, name):
+        """Sum of bin centres weighted by the counts: within half a bin width of the mean of the
+        samples when none fell outside."""
+        c = self.counts(name).astype(np.float64)
+        e = self.edges(name)
+        return float((c * 0.5 * (e[:-1] + e[1:])).sum() / c.sum())
+
+    def quantile(self, name, q):
+        """The value below which a fraction q of the in-range samples lies, linear inside a bin."""
+        q = np.asarray(q, dtype=np.float64)
+        if np.any((q < 0) | (q > 1)):
+            raise MarginalsError("marginals: a quantile lies in [0, 1]")
+        c = self.counts(name).astype(np.float64)
+        if c.sum() == 0:
+            raise MarginalsError(f"marginals: no sample of {name!r} inside its range")
+        cum = np.concatenate(([0.0], np.cumsum(c)))
+        target = q * cum[-1]
+        # the bin in which the cumulative count reaches the target (empty bins are skipped)
+        k = np.clip(np.searchsorted(cum, target, side="left") - 1, 0, self.bins - 1)
+        e = self.edges(name)
+        frac = np.where(c[k] > 0, (target - cum[k]) / np.where(c[k] > 0, c[k], 1.0), 0.0)
+        out = e[k] + frac * (e[k + 1] - e[k])
+        return float(out) if out.ndim == 0 else out
+
+    # -- arithmetic, files
+    def __add__(self, other):
+        if not isinstance(other, Marginals):
+            return NotImplemented
+        if self._layout() != other._layout():
+            raise MarginalsError("marginals: only histograms of the same layout (parameters, pairs, "
+                                 "bins and ranges) add up")
+        return Marginals(self.params, self.pairs, self.bins, self.bins2d, self.ranges,
+                         self.slab + other.slab, self.n_accumulations + other.n_accumulations,
+                         self.n_samples + other.n_samples)
+
+    def __eq__(self, other):
+        return (isinstance(other, Marginals) and self._layout() == other._layout()
+                and np.array_equal(self.slab, other.slab)
+                and (self.n_accumulations, self.n_samples) == (other.n_accumulations, other.n_samples))
+
+    __hash__ = None
+
+    def save(self, path):
+        names = self.names_in_use()
+        with open(path, "wb") as f:   # (np.savez would append ".npz" to a bare name)
+            np.savez(f, params=np.array(self.params, dtype=str),
+                     pairs=np.array(self.pairs, dtype=str).reshape(-1, 2),
+                     bins=np.array([self.bins, self.bins2d], dtype=np.int64),
+                     range_names=np.array(names, dtype=str),
+                     ranges=np.array([self.ranges[n] for n in names], dtype=np.float64).reshape(-1, 2),
+                     slab=self.slab,
+                     n=np.array([self.n_accumulations, self.n_samples], dtype=np.int64))
+
+    @classmethod
+    def load(cls, path):
+        z = np.load(path, allow_pickle=False)
+        ranges = {str(n): (float(r[0]), float(r[1])) for n, r in zip(z["range_names"], z["ranges"])}
+        return cls([str(p) for p in z["params"]], [(str(a), str(b)) for a, b in z["pairs"]],
+                   int(z["bins"][0]), int(z["bins"][1]), ranges, z["slab"], int(z["n"][0]),
+                   int(z["n"][1]))
+
+
+# ---------------------------------------------------------------------------------- the option
+def parse_option(opt, sampled):
+    """The sampler option `marginals` -> None (off) or a dict
+    {"params": [names], "pairs": [(a, b)], "bins", "bins2d", "ranges": dict | "prior" | "covmat"}.
+    `True` = every sampled parameter in 1-D, no pairs.  Refuses, by the option's name, unknown
+    keys and parameter names, pairs of one parameter, bin counts out of range and a slab above
+    64 MiB."""
+    if opt is None or opt is False:
+        return None
+    sampled = list(sampled)
+    if opt is True:
+        opt = {"params": "all"}
+    if not isinstance(opt, dict):
+        raise MarginalsError(f"marginals: expected True, None or a dict, got {opt!r}")
+    unknown = sorted(set(opt) - set(OPTION_KEYS))
+    if unknown:
+        raise MarginalsError(f"marginals: unknown key(s) {unknown}; valid keys: {list(OPTION_KEYS)}")
+    params = opt.get("params", "all")
+    if isinstance(params, str):
+        if params != "all":
+            raise MarginalsError(f"marginals: params must be a list of names or 'all', got {params!r}")
+        params = list(sampled)
+    params = [str(p) for p in (params or [])]
+    pairs = opt.get("pairs", None)
+    if isinstance(pairs, str):
+        if pairs != "all":
+            raise MarginalsError(f"marginals: pairs must be a list of [a, b], 'all' or None, got {pairs!r}")
+        pairs = [(a, b) for k, a in enumerate(sampled) for b in sampled[k + 1:]]
+    out_pairs = []
+    for pr in pairs or []:
+        if isinstance(pr, str) or len(pr) != 2:
+            raise MarginalsError(f"marginals: pairs holds [a, b] entries, got {pr!r}")
+        out_pairs.append((str(pr[0]), str(pr[1])))
+    bad = sorted({n for n in params if n not in sampled}
+                 | {n for pr in out_pairs for n in pr if n not in sampled})
+    if bad:
+        raise MarginalsError(f"marginals: unknown parameter name(s) {bad}; the sampled parameters "
+                             f"are {sampled}")
+    if len(set(params)) != len(params):
+        raise MarginalsError("marginals: params lists a parameter twice")
+    for a, b in out_pairs:
+        if a == b:
+            raise MarginalsError(f"marginals: the pair [{a!r}, {b!r}] needs two different parameters")
+    if not params and not out_pairs:
+        raise MarginalsError("marginals: neither params nor pairs lists anything (use None to turn "
+                             "the option off)")
+    bins, bins2d = opt.get("bins", 128), opt.get("bins2d", 32)
+    for key, v, cap in (("bins", bins, MAX_BINS_1D), ("bins2d", bins2d, MAX_BINS_2D)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= cap:
+            raise MarginalsError(f"marginals: {key} must be an integer in 1..{cap}, got {v!r}")
+    bins, bins2d = int(bins), int(bins2d)
+    nbytes = 8 * slab_size(len(params), bins, len(out_pairs), bins2d)
+    if nbytes > MAX_SLAB_BYTES:
+        raise MarginalsError(f"marginals: {len(params)} parameters x {bins} bins and {len(out_pairs)} "
+                             f"pairs x {bins2d}^2 bins take {nbytes} bytes of counters, above the "
+                             f"{MAX_SLAB_BYTES} allowed: list fewer pairs or lower bins2d")
+    ranges = opt.get("ranges", "prior")
+    if isinstance(ranges, str):
+        if ranges not in ("prior", "covmat"):
+            raise MarginalsError(f"marginals: ranges must be a dict, 'prior' or 'covmat', got {ranges!r}")
+    elif isinstance(ranges, dict):
+        bad = sorted(str(n) for n in ranges if n not in sampled)
+        if bad:
+            raise MarginalsError(f"marginals: ranges names unknown parameter(s) {bad}")
+        clean = {}
+        for n, r in ranges.items():
+            try:
+                lo, hi = float(r[0]), float(r[1])
+                ok = len(r) == 2
+            except (TypeError, ValueError, IndexError):
+                ok = False
+            if not ok or not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+                raise MarginalsError(f"marginals: ranges[{n!r}] must be a finite [lo, hi] with lo < hi, "
+                                     f"got {r!r}")
+            clean[str(n)] = (lo, hi)
+        ranges = clean
+    else:
+        raise MarginalsError(f"marginals: ranges must be a dict, 'prior' or 'covmat', got {ranges!r}")
+    return {"params": params, "pairs": out_pairs, "bins": bins, "bins2d": bins2d, "ranges": ranges}
+
+
+def resolve_ranges(cfg, spec, centre=None, covmat=None):
+    """{name: (lo, hi)} of every parameter in use.  An explicit entry wins; the rest follow the
+    mode: "prior" (also behind a dict) -- the bounds of a uniform prior, loc +- 5 scale of a normal
+    one; "covmat" -- centre +- 5 sigma of `covmat` (the initial points' mean and the proposal
+    covariance in force at initialize()), clipped to the prior support."""
+    names = list(cfg["params"])
+    for pr in cfg["pairs"]:
+        names += [n for n in pr if n not in names]
+    explicit = cfg["ranges"] if isinstance(cfg["ranges"], dict) else {}
+    mode = cfg["ranges"] if isinstance(cfg["ranges"], str) else "prior"
+    out = {}
+    for n in names:
+        if n in explicit:
+            out[n] = explicit[n]
+            continue
+        i = spec.sampled.index(n)
+        uniform = int(spec.kinds[i]) == 0
+        a, b = float(spec.a[i]), float(spec.b[i])
+        plo, phi = (a, b) if uniform else (a - 5.0 * b, a + 5.0 * b)
+        if mode == "covmat":
+            if centre is None or covmat is None:
+                raise MarginalsError("marginals: ranges: 'covmat' needs the initial points and the "
+                                     "proposal covariance")
+            sig = float(np.sqrt(covmat[i, i]))
+            lo, hi = float(centre[i]) - 5.0 * sig, float(centre[i]) + 5.0 * sig
+            if uniform:
+                lo, hi = max(lo, a), min(hi, b)
+        else:
+            lo, hi = plo, phi
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise MarginalsError(f"marginals: ranges: {mode!r} gives [{lo}, {hi}] for {n!r}; give it "
+                                 "an explicit range")
+        out[n] = (lo, hi)
+    return out

@@ -33,6 +33,7 @@ import numpy as np
 import pandas as pd
 
 from . import dist
+from . import marginals as marginals_mod
 from .collection import SampleCollection
 from .engine import (ChainStuck, Engine, EngineError, NotPositiveDefinite, gelman_rubin,
                      incremental_supported)
@@ -131,6 +132,13 @@ HIP_DEFAULTS = {
                               # single-process default) a launch of 0.9 ms no longer covers it
                               # on a slow host, and with several processes the collective's
                               # kernel needs the room as well -- see `advance`
+    "marginals": None,        # streaming 1-D / 2-D marginal histograms of the ensemble, counted on the
+                              # device from EVERY walker of every moment snapshot of the window
+                              # (the later half of the run) -- products()["marginals"], a
+                              # `cobaya_amd.marginals.Marginals`.  None: off.  True: every sampled
+                              # parameter in 1-D.  Or {"params": [names] | "all", "pairs": [[a, b],
+                              # ...] | "all" | None, "bins": 128, "bins2d": 32, "ranges": {name:
+                              # [lo, hi]} | "prior" | "covmat"}; the ranges are fixed for the run
     "shared_basis": True,     # True: the walkers of a group share one Haar basis per cycle;
                               # False: every walker draws its own (proposal.py:59-69 to the
                               # letter: the reference-faithful control, much slower)
@@ -211,6 +219,8 @@ class EnsembleMCMC:
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
     MAX_DIM = 128    # ctx.h: kMaxDimBig, every path (mixtures: at most 64 modes, model.py)
     HUGE_MAX_MODES = 4   # 128 < d <= max_dim(): huge_kernels.hip (huge_args.h: kHugeMaxModes)
+    marginals = None     # (the option's default: off)
+    _marg = _marg_fetched = None   # the parsed option (None: off); a read-out fetched ahead
 
     def _max_dim(self):
         """The cap of the engine behind the seam: its max_dim() where it has one, else 128 (the
@@ -426,6 +436,7 @@ class EnsembleMCMC:
         if int(self.basis_group_size) != int(self.group_size) and not self.incremental:
             self._fail("basis_group_size (%s) differs from group_size (%s): this needs "
                        "incremental evaluation", self.basis_group_size, self.group_size)
+        self._check_marginals(spec)
         try:
             self.engine = self._engine_factory(d, W, group_size=int(self.group_size), device=int(device),
                                  seed=self.seed, walker_offset=self.rank * W,
@@ -508,7 +519,106 @@ class EnsembleMCMC:
         self.engine.set_moment_shift(self._shift)
         self._init_bookkeeping()
         self._init_bounds_ring()
+        self._init_marginals(centre=self._shift, covmat=self._initial_covmat)
         self._init_device_checkpoint()
+
+    # ------------------------------------------------------------------ marginals
+    def _check_marginals(self, spec):
+        """The `marginals` option, parsed and refused by its name BEFORE the engine is created."""
+        self._marg = None
+        try:
+            cfg = marginals_mod.parse_option(self.marginals, spec.sampled)
+        except marginals_mod.MarginalsError as e:
+            self._fail("%s", str(e), cause=e)
+        if cfg is None:
+            return
+        if self.temperature != 1:
+            self._fail("marginals: the histograms count the walkers as they are, which at "
+                       "temperature %g follow the tempered law, not the posterior; use temperature: 1 "
+                       "or turn marginals off", self.temperature)
+        if not all(hasattr(self._engine_factory, m) for m in
+                   ("configure_marginals", "accumulate_marginals", "request_marginals",
+                    "fetch_marginals", "marginals_set")):
+            self._fail("marginals: this engine has no marginal histograms (its library predates "
+                       "mcmc_hip_marginals_*)")
+        self._marg = cfg
+
+    def _init_marginals(self, centre=None, covmat=None, ranges=None):
+        """Fix the ranges (given: those of the state file) and hand the layout to the engine."""
+        cfg = self._marg
+        if cfg is None:
+            return
+        spec = self.spec
+        try:
+            cfg["resolved"] = dict(ranges) if ranges is not None else marginals_mod.resolve_ranges(
+                cfg, spec, centre, covmat)
+        except marginals_mod.MarginalsError as e:
+            self._fail("%s", str(e), cause=e)
+        lo, hi = np.full(spec.d, np.nan), np.full(spec.d, np.nan)
+        for n, (a, b) in cfg["resolved"].items():
+            lo[spec.sampled.index(n)], hi[spec.sampled.index(n)] = a, b
+        try:
+            self.engine.configure_marginals(
+                [spec.sampled.index(n) for n in cfg["params"]], cfg["bins"],
+                [(spec.sampled.index(a), spec.sampled.index(b)) for a, b in cfg["pairs"]],
+                cfg["bins2d"], lo, hi)
+        except EngineError as e:
+            self._fail("marginals: %s", str(e), cause=e)
+        cfg["n_counters"] = marginals_mod.slab_size(len(cfg["params"]), cfg["bins"],
+                                                    len(cfg["pairs"]), cfg["bins2d"])
+        if hasattr(self.engine, "marginals_layout"):
+            # the engine's slab is the authority: the product must read it the way it is written
+            lay = self.engine.marginals_layout()
+            if (lay["n_counters"], lay["offset_pairs"]) != (
+                    cfg["n_counters"], marginals_mod.slab_size(len(cfg["params"]), cfg["bins"], 0, 0)):
+                self._fail("marginals: the engine lays its counters out differently (%r) from the "
+                           "product (%d counters)", lay, cfg["n_counters"])
+        self._marg_open = (np.zeros(cfg["n_counters"], np.uint64), 0)
+
+    def _marginals_geometry(self):
+        """What a resumed run must repeat: names, bins and ranges, as arrays for the state file."""
+        cfg = self._marg
+        names = list(cfg["resolved"])
+        return {"marg_params": np.array(cfg["params"], dtype=str),
+                "marg_pairs": np.array(cfg["pairs"], dtype=str).reshape(-1, 2),
+                "marg_bins": np.array([cfg["bins"], cfg["bins2d"]], dtype=np.int64),
+                "marg_range_names": np.array(names, dtype=str),
+                "marg_ranges": np.array([cfg["resolved"][n] for n in names], dtype=np.float64).reshape(-1, 2)}
+
+    def _marginals_drain(self):
+        """Move what the device holds of the unfinished interval into the host's copy of it
+        (`_marg_open`); a read-out still pending from a checkpoint request is fetched first and
+        kept for `_finish_checkpoint`.  Integers: where the counts are held changes no sum."""
+        eng = self.engine
+        if self._ckpt_pending and self._marg_fetched is None:
+            self._marg_fetched = eng.fetch_marginals()
+        eng.request_marginals()
+        c, n = eng.fetch_marginals()
+        self._marg_open = (self._marg_open[0] + c, self._marg_open[1] + n)
+
+    def _marginals_product(self, combined=False):
+        """Sum over the intervals of the window plus the unfinished interval -> `Marginals`."""
+        cfg = self._marg
+        if self.engine is not None:
+            self._marginals_drain()
+        slab, n_acc = self._marg_open[0].copy(), int(self._marg_open[1])
+        if self._marg_fetched is not None:   # (requested, not filed yet: the newest interval)
+            slab += self._marg_fetched[0]
+            n_acc += int(self._marg_fetched[1])
+        ivs = self._intervals
+        for (n_snap, _, _), c in zip(ivs, self._marg_ivs):
+            slab += c
+            n_acc += int(n_snap)
+        n_samples = n_acc * int(self.n_walkers)
+        if combined and self.size > 1:
+            # ONE host all-reduce of integers (exact in float64 below 2^53), here and not in the loop
+            buf = np.concatenate((slab.astype(np.float64), [float(n_samples)]))
+            if buf.max() >= 2.0 ** 53:
+                self._fail("marginals: a count above 2^53 cannot be summed over processes exactly")
+            dist.all_reduce_sum(buf)
+            slab, n_samples = buf[:-1].astype(np.uint64), int(buf[-1])
+        return marginals_mod.Marginals(cfg["params"], cfg["pairs"], cfg["bins"], cfg["bins2d"],
+                                       cfg["resolved"], slab, n_acc, n_samples)
 
     def _init_bounds_ring(self):
         """`bounds_snapshots` ensemble snapshots on the device (mcmc_hip_bounds_configure)."""
@@ -713,6 +823,9 @@ class EnsembleMCMC:
         self._carried = None     # table rows of earlier legs, read back at resume
         self._intervals = []     # per checkpoint: (n_snapshots, group_sum[G,d], pooled_S[d,d])
         self._iv0 = 0            # absolute index of _intervals[0] (intervals dropped so far)
+        # marginals: the counts of every interval of `_intervals` (same index), the host's part of
+        # the unfinished interval (counts, accumulations), a read-out fetched ahead of its checkpoint
+        self._marg_ivs, self._marg_open, self._marg_fetched = [], None, None
         self._wsums = WindowSums()
         self._dropped_snapshots = 0
         self._progress_rows = {}  # i_learn -> row dict (DataFrame built on demand: `progress`)
@@ -852,6 +965,10 @@ class EnsembleMCMC:
         self.log.info("Sampling complete after %d accepted steps.", self._accepted_total)
         if self.output:
             self.write_checkpoint(force_state=True)
+        if self.output and self._marg:
+            m = self._marginals_product(combined=True)   # (collective: every process calls it)
+            if self.rank == 0:
+                m.save(self._out_file(".marginals.npz"))
 
     def advance(self):
         """One pass of the hot loop (the body of mcmc.py:451-528 for every walker): a fused
@@ -889,6 +1006,8 @@ class EnsembleMCMC:
                 self._finish_checkpoint()
         if self._launches % max(1, int(self.moments_every)) == 0:
             eng.accumulate_moments()
+            if self._marg:
+                eng.accumulate_marginals()
             self._snaps_in_interval += 1
             self._bounds_take()
         snap_every = int(self.snapshot_every) if self.snapshot_every else None
@@ -918,6 +1037,8 @@ class EnsembleMCMC:
             return
         if hasattr(self.engine, "request_moments"):
             self.engine.request_moments()
+        if self._marg:
+            self.engine.request_marginals()
         self._ckpt_on_device = False
         if self._device_ckpt and self._snaps_in_interval > 0:
             self._begin_device_checkpoint()
@@ -963,6 +1084,8 @@ class EnsembleMCMC:
         self._ckpt_pending = False
         moments = (self.engine.fetch_moments() if hasattr(self.engine, "fetch_moments")
                    else None)
+        if self._marg and self._marg_fetched is None:
+            self._marg_fetched = self.engine.fetch_marginals()
         dev = payload = None
         if self._ckpt_on_device and self._ckpt_solve_on_device:
             dev = self.engine.checkpoint_fetch()
@@ -1040,6 +1163,13 @@ class EnsembleMCMC:
             acc_n, acc_gs, acc_S = self.engine.read_moments(reset=False)
             st.update(acc_n=np.int64(acc_n), acc_gs=acc_gs, acc_S=acc_S)
             ivs = self._intervals
+            if self._marg:
+                self._marginals_drain()
+                st.update(self._marginals_geometry())
+                st["marg_iv"] = np.array(self._marg_ivs, dtype=np.uint64).reshape(
+                    len(self._marg_ivs), self._marg["n_counters"])
+                st["marg_open"] = self._marg_open[0]
+                st["marg_open_n"] = np.int64(self._marg_open[1])
             # the bounds ring: its books always, its snapshots while they are small (a resumed run
             # then forms the same Rminus1_cl; a large ring restarts empty)
             held = [k for k, j in enumerate(self._bslots) if j >= 0]
@@ -1178,6 +1308,8 @@ class EnsembleMCMC:
                               "of the bounds restarts empty.")
         self._intervals = [(int(n), gs, S) for n, gs, S in zip(z["iv_n"], z["iv_gs"], z["iv_S"])]
         self._iv0 = int(z["iv0"]) if "iv0" in z else 0
+        if self._marg:
+            self._load_marginals(z)
         self._wsums = WindowSums()
         (self.n_steps_raw, self.i_learn, self._acc_last, self._steps_last, self._launches,
          self._dropped_snapshots, self._accepted_total) = (int(v) for v in book[:7])
@@ -1205,6 +1337,38 @@ class EnsembleMCMC:
         self._load_chain_file(txt_rows)
         self.log.info("Resumed from %s at %d steps per walker (%d stored rows).",
                       self._state_file(), self.n_steps_raw, self._txt_rows)
+
+    def _load_marginals(self, z):
+        """Resume: the ranges are part of the geometry -- the saved ones are taken where the option
+        derives them from the run's start (`covmat`) and must be repeated where it states them."""
+        cfg = self._marg
+        if "marg_iv" not in z:
+            self._fail("marginals: cannot resume -- the run was written without marginals (the window "
+                       "of a histogram cannot begin in mid-run)")
+        saved = {str(n): (float(r[0]), float(r[1]))
+                 for n, r in zip(z["marg_range_names"], z["marg_ranges"])}
+        same = ([str(p) for p in z["marg_params"]] == cfg["params"]
+                and [(str(a), str(b)) for a, b in z["marg_pairs"]] == cfg["pairs"]
+                and [int(v) for v in z["marg_bins"]] == [cfg["bins"], cfg["bins2d"]])
+        if same and cfg["ranges"] != "covmat":
+            try:
+                same = marginals_mod.resolve_ranges(cfg, self.spec) == saved
+            except marginals_mod.MarginalsError as e:
+                self._fail("%s", str(e), cause=e)
+        elif same:
+            explicit = cfg["ranges"] if isinstance(cfg["ranges"], dict) else {}
+            same = all(saved.get(n) == r for n, r in explicit.items() if n in saved)
+        if not same:
+            self._fail("marginals: cannot resume -- the run was written with other parameters, pairs, "
+                       "bins or ranges (the counts of different bins do not add up); saved ranges: %r",
+                       saved)
+        self._init_marginals(ranges=saved)
+        self._marg_ivs = [np.array(c, dtype=np.uint64) for c in z["marg_iv"]]
+        if len(self._marg_ivs) != len(self._intervals):
+            self._fail("marginals: the state file holds %d interval histograms for %d intervals",
+                       len(self._marg_ivs), len(self._intervals))
+        # the unfinished interval goes back to the device, where the next accumulation adds to it
+        self.engine.marginals_set(z["marg_open"], int(z["marg_open_n"]))
 
     def _load_chain_file(self, n_rows):
         """The first `n_rows` rows of this process' chain file become the head of the
@@ -1372,6 +1536,8 @@ class EnsembleMCMC:
             k += 1
         self._dropped_snapshots += sum(counts[:k])
         self._intervals = ivs = ivs[k:]
+        if getattr(self, "_marg", None):
+            self._marg_ivs = self._marg_ivs[k:]
         self._iv0 += k
         if k:
             self._wsums.forget_below(self._iv0)
@@ -1396,6 +1562,14 @@ class EnsembleMCMC:
             c = eng.counters()
         else:
             n_snap, gs, S, c = moments
+        if getattr(self, "_marg", None):
+            # the interval's counts: what the request read out plus what the host held of it
+            fetched = self._marg_fetched[0] if self._marg_fetched is not None else 0
+            counts = self._marg_open[0] + fetched
+            self._marg_fetched = None
+            self._marg_open = (np.zeros_like(counts), 0)
+            if n_snap:
+                self._marg_ivs.append(counts)
         if n_snap:
             self._intervals.append((n_snap, gs, S))
         if not self._intervals:
@@ -1592,7 +1766,12 @@ class EnsembleMCMC:
     def products(self, combined=False, skip_samples=0, to_getdist=False):
         """mcmc.py:1150-1184: {"sample": SampleCollection, "progress": DataFrame}."""
         self.collection = self.samples(combined, skip_samples, to_getdist)
-        return {"sample": self.collection, "progress": self.progress}
+        out = {"sample": self.collection, "progress": self.progress}
+        if getattr(self, "_marg", None):
+            # the window of the covariance and of R-1 (the later half of the run) plus the
+            # unfinished interval, counted from every walker of every moment snapshot
+            out["marginals"] = self._marginals_product(combined)
+        return out
 
     # ------------------------------------------------------------------ reference-style views
     class _ProposerView:
@@ -1654,6 +1833,8 @@ class EnsembleMCMC:
 
     def close(self):
         if self.engine is not None:
+            if self._marg and self._marg_open is not None:
+                self._marginals_drain()     # (the device's part of the unfinished interval)
             self._materialise_row_views()   # products()/samples() stay valid after close
             self.engine.close()
             self.engine = None
@@ -1716,7 +1897,7 @@ class MCMCHip(EnsembleMCMC):
             return [], []
         head = re.escape(prefix) + (r"[\._]" if prefix else "")
         chain = re.compile(head + r"\d+\.txt$")
-        rest = re.compile(head + r"(checkpoint|progress|covmat|\d+\.(state\.npz|bounds\.npy|bounds_tags\.npy))$")
+        rest = re.compile(head + r"(checkpoint|progress|covmat|marginals\.npz|\d+\.(state\.npz|bounds\.npy|bounds_tags\.npy))$")
         names = sorted(os.listdir(folder))
         return ([os.path.join(folder, n) for n in names if chain.match(n)],
                 [os.path.join(folder, n) for n in names if rest.match(n)])

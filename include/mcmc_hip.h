@@ -337,6 +337,40 @@ MCMC_HIP_API int mcmc_hip_request_moments(mcmc_hip_ctx* h);
 MCMC_HIP_API int mcmc_hip_fetch_moments(mcmc_hip_ctx* h, int64_t* n_snapshots, double* group_sum,
                            double* pooled_S, int64_t counters[2]);
 
+/* Streaming marginal histograms of the ensemble (marginal_kernels.hip): the 1-D densities and 2-D
+ * contours GetDist draws from the stored rows (MCSamples.get1DDensity / get2DDensity behind
+ * SampleCollection.to_getdist, collection.py), counted here from EVERY walker of every
+ * accumulation instead of from the rows that `max_rows` retains.  Same life cycle as the moments.
+ * The rule ("Marginals"): on an axis of B bins over [lo, hi] a value is in
+ * range iff x >= lo && x <= hi and falls in bin k = min((int)floor((x - lo) * s), B - 1),
+ * s = B / (hi - lo) formed in double on the host; x == hi falls in the last bin, a value on an
+ * interior edge in the upper one.  Counters are uint64:
+ *   1-D entry k (0 <= k < n1) at k (bins1 + 2):            [under, over, c_0 .. c_{bins1-1}]
+ *   pair p (0 <= p < n2) at offset_pairs + p (bins2^2 + 1): [outside, c_{0,0} .. ], row-major with the
+ *   pair's FIRST parameter as the row; `outside` counts a walker either coordinate of which is out.
+ * configure: dims1[n1] sampler indices, 1 <= bins1 <= 1024; pairs[n2][2] ordered (i, j), i != j,
+ * 1 <= bins2 <= 64; lo[d], hi[d] indexed by sampler index (read for the parameters in use only:
+ * finite, lo < hi).  Allocates and zeroes the slab and its pinned read-out; n1 = n2 = 0 frees them
+ * (the feature is off).  A bad call returns MCMC_HIP_ERR_ARG and names the argument.
+ * accumulate: ONE launch on the engine's stream adds every walker of this process once to every
+ * entry (the population a moment snapshot sums); no host synchronisation, no allocation.
+ * MCMC_HIP_ERR_STATE without a state or a slab.
+ * request / fetch: the contract of mcmc_hip_request_moments / mcmc_hip_fetch_moments -- `request`
+ * queues the copy of the slab to pinned host memory and the zeroing of the slab in stream order,
+ * `fetch` waits for that copy only; counts[n] with n = n_counters of `layout`,
+ * *n_accumulations = accumulations the read-out holds.  One request may be pending.
+ * set: restores the counts of an unfinished interval (resume); synchronous.
+ * layout: n_counters (0: off), n1, bins1, n2, bins2, offset_pairs; any pointer may be NULL. */
+MCMC_HIP_API int mcmc_hip_marginals_configure(mcmc_hip_ctx* h, int32_t n1, const int32_t* dims1, int32_t bins1,
+                                 int32_t n2, const int32_t* pairs, int32_t bins2, const double* lo,
+                                 const double* hi);
+MCMC_HIP_API int mcmc_hip_marginals_accumulate(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_marginals_request(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_marginals_fetch(mcmc_hip_ctx* h, uint64_t* counts, int64_t n, int64_t* n_accumulations);
+MCMC_HIP_API int mcmc_hip_marginals_set(mcmc_hip_ctx* h, const uint64_t* counts, int64_t n, int64_t n_accumulations);
+MCMC_HIP_API int mcmc_hip_marginals_layout(const mcmc_hip_ctx* h, int64_t* n_counters, int32_t* n1, int32_t* bins1,
+                              int32_t* n2, int32_t* bins2, int64_t* offset_pairs);
+
 /* The learn / convergence checkpoint ON THE DEVICE (MCMC.check_convergence_and_learn_proposal,
  * mcmc.py:773-1032; checkpoint_kernels.hip): the intervals between checkpoints are kept in a
  * device ring, the statistics of the window (the later half of the run, mcmc.py:787-790) are

@@ -56,6 +56,7 @@ else:
         basis_group_size: int | None = HIP_DEFAULTS["basis_group_size"]
         checkpoint_lag: int | None = HIP_DEFAULTS["checkpoint_lag"]
         emit_thin: int | None = HIP_DEFAULTS["emit_thin"]
+        marginals: bool | dict | None = HIP_DEFAULTS["marginals"]
 
         def _export_collection(self, coll):
             """Our table -> `cobaya.collection.SampleCollection` (same columns,
@@ -81,6 +82,8 @@ else:
                 regexps.append((re.compile(output.prefix_regexp_str
                                            + r"\d+\.(state\.npz|bounds\.npy|bounds_tags\.npy)$"),
                                 None))
+                # the histograms of `marginals` (written once, at the end of the run)
+                regexps.append((re.compile(output.prefix_regexp_str + r"marginals\.npz$"), None))
             return regexps
 
 
