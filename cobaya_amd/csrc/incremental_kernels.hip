@@ -306,9 +306,19 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
             const double bh = a.prior[dpad + i];
             sLH[i] = make_double2(a.prior[i], (i < d && is_periodic(i)) ? pred_double(bh) : bh);
         }
-    if (kFloatLds)
-        for (int e = tid; e < 4 * ((DQ + 1) / 2); e += 256) {
-            const int kk0 = 2 * (e >> 2), cc = e & 3;
+    // kFloatVec: the median form cannot express an EMPTY interval.  Where the inward copies of some
+    // dimension CROSS (lo_f > hi_f: bounds closer than two single-precision ulps at their magnitude
+    // -- a Julian date on [2450000, 2450000.1] --, bounds below the single-precision subnormals)
+    // med3(t, lo_f, hi_f) is t for every t between them: "inside for certain" for a trial that has
+    // left the box.  (The two compares of the scalar form are never both true there.)  Such a
+    // problem takes the exact comparisons at every step: its verdict starts out "not certain".
+    unsigned fcross = 0u;   // wave-uniform
+    if (kFloatLds) {
+        // (every wave converts -- one entry per lane -- and sees the crossing; the first wave stores)
+        static_assert(4 * ((DQ + 1) / 2) <= 64 || !kFloatLds, "one entry of sFB per lane");
+        bool crossed = false;
+        if (lane < 4 * ((DQ + 1) / 2)) {
+            const int e = lane, kk0 = 2 * (e >> 2), cc = e & 3;
             float v[4];
             for (int h = 0; h < 2; ++h) {
                 const int i = 4 * (kk0 + h) + cc;   // (beyond the padded rows: no bound)
@@ -321,11 +331,14 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
                     if (fl > -INFINITY) fl = nextafterf(fl, INFINITY);
                     if (fh < INFINITY) fh = nextafterf(fh, -INFINITY);
                 }
+                crossed |= !(fl <= fh) || fl == INFINITY || fh == -INFINITY;
                 v[2 * h] = fl;
                 v[2 * h + 1] = fh;
             }
-            sFB[e] = make_float4(v[0], v[1], v[2], v[3]);
+            if (wave == 0) sFB[e] = make_float4(v[0], v[1], v[2], v[3]);
         }
+        if (kFloatVec) fcross = lanes(crossed) != 0ull ? 1u : 0u;
+    }
     if (PER) {
         for (int i = tid; i < dpad; i += 256) {
             const double plo = a.prior[i], phi = a.prior[dpad + i];
@@ -507,7 +520,9 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
                     // wave-uniform branch that a posterior away from the walls never takes
                     unsigned hmx = 0u;
                     float4 fb2 = make_float4(0.f, 0.f, 0.f, 0.f);   // (kFloatLds) the bounds of two rows
-                    unsigned facc = 0u;   // (kFloatLds) 0: every trial coordinate so far is inside its float bounds
+                    // (kFloatLds) 0: every trial coordinate so far is inside its float bounds (never 0
+                    // where the copies of some dimension cross, see fcross)
+                    unsigned facc = fcross;
                     auto trial = [&](int kk, const pair_t p) {
                         const double t = fma(r, p.x, x[kk]);
                         if (MODE == 0) {
