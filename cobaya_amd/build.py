@@ -105,6 +105,7 @@ def translation_units(dims, big=True):
             ("pliklite_kernels.hip", "pliklite", []),
             ("checkpoint_kernels.hip", "checkpoint", []),
             ("marginal_kernels.hip", "marginal", []),   # streaming 1-D / 2-D marginal histograms
+            ("autocorr_kernels.hip", "autocorr", []),   # lagged cross-products (autocorrelation time)
             ("comm.hip", "comm", [])]   # the RCCL communicator (bound at run time)
     tus += [("incremental_kernels.hip", f"incremental_{lo}", [f"-DMCMC_DQ_LO={lo}", f"-DMCMC_DQ_HI={hi}"])
             for lo, hi in INC_DQ_RANGES]
@@ -124,7 +125,8 @@ def translation_units(dims, big=True):
             ("capi_incremental.hip", "capi_incremental", []),
             ("capi_rows.hip", "capi_rows", []),
             ("capi_checkpoint.hip", "capi_checkpoint", []),
-            ("capi_marginals.hip", "capi_marginals", [])]
+            ("capi_marginals.hip", "capi_marginals", []),
+            ("capi_autocorr.hip", "capi_autocorr", [])]
     return tus
 
 

@@ -383,6 +383,10 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     h->mg.slab.release(); h->mg.entries.release();
     if (h->mg.pin) (void)hipHostFree(h->mg.pin);
     if (h->mg.ev) (void)hipEventDestroy(h->mg.ev);
+    h->ac.ring.release(); h->ac.ringS.release(); h->ac.Pg.release(); h->ac.acc.release();
+    h->ac.dims.release();
+    if (h->ac.pin) (void)hipHostFree(h->ac.pin);
+    if (h->ac.ev) (void)hipEventDestroy(h->ac.ev);
     if (h->ck.ev) (void)hipEventDestroy(h->ck.ev);
     if (h->pin_mom) (void)hipHostFree(h->pin_mom);
     if (h->pin_T) (void)hipHostFree(h->pin_T);
@@ -1058,10 +1062,17 @@ int mcmc_hip_set_moment_shift(mcmc_hip_ctx* h, const double* shift)
     if (!h || !shift) return MCMC_HIP_ERR_ARG;
     if (h->n_snapshots != 0)
         return fail(h, MCMC_HIP_ERR_STATE, "the moment shift can only change right after a reset");
+    const bool changed = !std::equal(h->shift.begin(), h->shift.end(), shift);
     h->shift.assign(shift, shift + h->d);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipMemcpyAsync(h->dshift.p, h->shift.data(), sizeof(double) * h->d,
                               hipMemcpyHostToDevice, h->stream));
+    if (changed && h->ac.acc.p) {
+        // the autocorrelation ring's group sums and the open accumulators refer to the old shift
+        h->ac.held = h->ac.head = 0;
+        std::fill(h->ac.n_pairs.begin(), h->ac.n_pairs.end(), (int64_t)0);
+        HIP_TRY(h, hipMemsetAsync(h->ac.acc.p, 0, sizeof(double) * h->ac.acc.n, h->stream));
+    }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MCMC_HIP_OK;
 }

@@ -22,6 +22,7 @@
 #include "function_args.h"
 #include "checkpoint_args.h"
 #include "marginal_args.h"
+#include "autocorr_args.h"
 #include "comm.h"
 #include "inc_choice.h"
 
@@ -271,6 +272,20 @@ struct mcmc_hip_ctx {
         hipEvent_t ev = nullptr;
         bool pending = false;
     } mg;
+    // lagged cross-products for the autocorrelation time (mcmc_hip_autocorr_*; autocorr_kernels.hip):
+    // the ring of the last lags + 1 snapshots with their group sums, the accumulators
+    // [3][lags + 1][n] (P, A, B) and their pinned read-out; the pair counts live on the host
+    struct AutoCorr {
+        DevBuf<double> ring, ringS, Pg, acc;
+        DevBuf<int> dims;
+        double* pin = nullptr;                 // [3][lags + 1][n]
+        int n = 0, lags = 0, rows_per_pass = 0;
+        int held = 0;                          // snapshots the ring holds (<= lags + 1)
+        int head = 0;                          // slot of the NEXT snapshot
+        std::vector<int64_t> n_pairs, pend_pairs;   // [lags + 1]: open, of the pending read-out
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+    } ac;
     // the walker shards' communicator (comm.hip; not owned): the device checkpoint all-reduces
     // its payload over it in stream order
     mcmc_hip_comm* comm = nullptr;

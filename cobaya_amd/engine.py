@@ -150,6 +150,13 @@ SYMBOLS = [
     ("mcmc_hip_marginals_set", C.c_int, [_H, c_uint64_p, C.c_int64, C.c_int64]),
     ("mcmc_hip_marginals_layout", C.c_int, [_H, c_int64_p, c_int32_p, c_int32_p, c_int32_p,
                                             c_int32_p, c_int64_p]),
+    ("mcmc_hip_autocorr_configure", C.c_int, [_H, C.c_int32, c_int32_p, C.c_int32]),
+    ("mcmc_hip_autocorr_accumulate", C.c_int, [_H]),
+    ("mcmc_hip_autocorr_request", C.c_int, [_H]),
+    ("mcmc_hip_autocorr_fetch", C.c_int, [_H, c_double_p, C.c_int64, c_int64_p]),
+    ("mcmc_hip_autocorr_set", C.c_int, [_H, c_double_p, C.c_int64, c_int64_p]),
+    ("mcmc_hip_autocorr_reset", C.c_int, [_H]),
+    ("mcmc_hip_autocorr_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int64_p, c_int32_p]),
     ("mcmc_hip_gelman_rubin", C.c_int, [C.c_int32, C.c_double, C.c_double, c_double_p,
                                         c_double_p, c_double_p, c_double_p, c_double_p]),
     ("mcmc_hip_enable_timing", C.c_int, [_H, C.c_int32]),
@@ -841,6 +848,54 @@ class Engine:
         c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
         self._check(self._lib.mcmc_hip_marginals_set(self._h, c.ctypes.data_as(c_uint64_p), len(c),
                                                      int(n_accumulations)))
+
+    # -- lagged cross-products for the autocorrelation time
+    def configure_autocorr(self, dims=(), lags=16):
+        """The parameters (`dims`: distinct sampler indices) whose lagged cross-products with the
+        previous `lags` accumulated snapshots every `accumulate_autocorr` adds
+        (mcmc_hip_autocorr_configure).  Nothing listed: off."""
+        dims = np.ascontiguousarray(dims, dtype=np.int32).reshape(-1)
+        self._check(self._lib.mcmc_hip_autocorr_configure(
+            self._h, len(dims), _ip(dims) if len(dims) else None, int(lags)))
+
+    def autocorr_layout(self):
+        """{"n_dims", "lags", "n_doubles", "held"} (mcmc_hip_autocorr_layout); all zero: off."""
+        n, L, held, nd = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        self._check(self._lib.mcmc_hip_autocorr_layout(self._h, C.byref(n), C.byref(L), C.byref(nd),
+                                                       C.byref(held)))
+        return {"n_dims": n.value, "lags": L.value, "n_doubles": nd.value, "held": held.value}
+
+    def accumulate_autocorr(self):
+        """Queue one accumulation: the ensemble as it is becomes the ring's newest snapshot and is
+        multiplied with every snapshot the ring holds."""
+        self._check(self._lib.mcmc_hip_autocorr_accumulate(self._h))
+
+    def request_autocorr(self):
+        """Queue the read-out and the zeroing of the accumulators behind the work already in the
+        stream; the ring is kept."""
+        self._check(self._lib.mcmc_hip_autocorr_request(self._h))
+
+    def fetch_autocorr(self):
+        """(sums[3][lags + 1][n_dims] (P, A, B), n_pairs[lags + 1] int64) of the pending request;
+        waits for its copy only."""
+        lay = self.autocorr_layout()
+        out = np.zeros((3, lay["lags"] + 1, lay["n_dims"]), np.float64)
+        k = np.zeros(lay["lags"] + 1, np.int64)
+        self._check(self._lib.mcmc_hip_autocorr_fetch(self._h, _dp(out), out.size,
+                                                      k.ctypes.data_as(c_int64_p)))
+        return out, k
+
+    def autocorr_set(self, sums, n_pairs):
+        """Restore open accumulators (resume); the ring is not restored."""
+        s = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1)
+        k = np.ascontiguousarray(n_pairs, dtype=np.int64).reshape(-1)
+        if len(k) != self.autocorr_layout()["lags"] + 1:
+            raise EngineError(ERR_ARG, "autocorr_set: n_pairs holds %d counts, not lags + 1" % len(k))
+        self._check(self._lib.mcmc_hip_autocorr_set(self._h, _dp(s), len(s), k.ctypes.data_as(c_int64_p)))
+
+    def autocorr_reset(self):
+        """Empty the ring: the next accumulation pairs with itself only."""
+        self._check(self._lib.mcmc_hip_autocorr_reset(self._h))
 
     # -- the checkpoint on the device
     def checkpoint_set_ring(self, intervals=(), min_capacity=16, first_index=0):

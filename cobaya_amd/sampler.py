@@ -33,6 +33,7 @@ import numpy as np
 import pandas as pd
 
 from . import dist
+from . import autocorr as autocorr_mod
 from . import marginals as marginals_mod
 from .collection import SampleCollection
 from .engine import (ChainStuck, Engine, EngineError, NotPositiveDefinite, gelman_rubin,
@@ -139,6 +140,13 @@ HIP_DEFAULTS = {
                               # parameter in 1-D.  Or {"params": [names] | "all", "pairs": [[a, b],
                               # ...] | "all" | None, "bins": 128, "bins2d": 32, "ranges": {name:
                               # [lo, hi]} | "prior" | "covmat"}; the ranges are fixed for the run
+    "autocorr": None,         # integrated autocorrelation times of the ensemble: every moment snapshot
+                              # of the window is multiplied, on the device and walker by walker,
+                              # with the previous `lags` snapshots -- products()["autocorr"], a
+                              # `cobaya_amd.autocorr.AutoCorr` (rho_k, tau, the effective sample
+                              # size, a thinning suggestion).  None: off.  True: every sampled
+                              # parameter, 16 lags.  Or {"params": [names] | "all", "lags": 1..64};
+                              # one lag is steps_per_launch x moments_every steps
     "shared_basis": True,     # True: the walkers of a group share one Haar basis per cycle;
                               # False: every walker draws its own (proposal.py:59-69 to the
                               # letter: the reference-faithful control, much slower)
@@ -221,6 +229,8 @@ class EnsembleMCMC:
     HUGE_MAX_MODES = 4   # 128 < d <= max_dim(): huge_kernels.hip (huge_args.h: kHugeMaxModes)
     marginals = None     # (the option's default: off)
     _marg = _marg_fetched = None   # the parsed option (None: off); a read-out fetched ahead
+    autocorr = None      # (the option's default: off)
+    _ac = _ac_fetched = _ac_open = None   # as `_marg`; the open sums as last read (kept past close)
 
     def _max_dim(self):
         """The cap of the engine behind the seam: its max_dim() where it has one, else 128 (the
@@ -437,6 +447,7 @@ class EnsembleMCMC:
             self._fail("basis_group_size (%s) differs from group_size (%s): this needs "
                        "incremental evaluation", self.basis_group_size, self.group_size)
         self._check_marginals(spec)
+        self._check_autocorr(spec)
         try:
             self.engine = self._engine_factory(d, W, group_size=int(self.group_size), device=int(device),
                                  seed=self.seed, walker_offset=self.rank * W,
@@ -488,6 +499,7 @@ class EnsembleMCMC:
         if self._is_resuming() and self.output and os.path.exists(self._state_file()):
             self._init_bookkeeping()
             self._init_bounds_ring()
+            self._init_autocorr()
             self._load_checkpoint()
             self._init_device_checkpoint()
             return
@@ -520,6 +532,7 @@ class EnsembleMCMC:
         self._init_bookkeeping()
         self._init_bounds_ring()
         self._init_marginals(centre=self._shift, covmat=self._initial_covmat)
+        self._init_autocorr()
         self._init_device_checkpoint()
 
     # ------------------------------------------------------------------ marginals
@@ -619,6 +632,109 @@ class EnsembleMCMC:
             slab, n_samples = buf[:-1].astype(np.uint64), int(buf[-1])
         return marginals_mod.Marginals(cfg["params"], cfg["pairs"], cfg["bins"], cfg["bins2d"],
                                        cfg["resolved"], slab, n_acc, n_samples)
+
+    # ------------------------------------------------------------------ autocorrelation
+    _AC_METHODS = ("configure_autocorr", "accumulate_autocorr", "request_autocorr", "fetch_autocorr",
+                   "autocorr_set", "autocorr_reset", "autocorr_layout")
+
+    def _check_autocorr(self, spec):
+        """The `autocorr` option, parsed and refused by its name BEFORE the engine is created."""
+        self._ac = None
+        try:
+            cfg = autocorr_mod.parse_option(self.autocorr, spec.sampled)
+        except autocorr_mod.AutoCorrError as e:
+            self._fail("%s", str(e), cause=e)
+        if cfg is None:
+            return
+        if not all(hasattr(self._engine_factory, m) for m in self._AC_METHODS):
+            self._fail("autocorr: this engine has no lagged cross-products (its library predates "
+                       "mcmc_hip_autocorr_*)")
+        # one lag: the steps between two moment snapshots, fixed for the run
+        cfg["interval_steps"] = int(self.steps_per_launch) * max(1, int(self.moments_every))
+        self._ac = cfg
+
+    def _init_autocorr(self):
+        """Hand the configuration to the engine (which allocates the ring, or refuses it)."""
+        cfg = self._ac
+        if cfg is None:
+            return
+        try:
+            self.engine.configure_autocorr([self.spec.sampled.index(n) for n in cfg["params"]],
+                                           cfg["lags"])
+        except EngineError as e:
+            self._fail("autocorr: %s", str(e), cause=e)
+        lay = self.engine.autocorr_layout()
+        if (lay["n_dims"], lay["lags"]) != (len(cfg["params"]), cfg["lags"]):
+            self._fail("autocorr: the engine lays its sums out differently (%r) from the product", lay)
+        self._ac_open = self._autocorr_zero()
+
+    def _autocorr_zero(self):
+        cfg = self._ac
+        return (np.zeros((3, cfg["lags"] + 1, len(cfg["params"]))), np.zeros(cfg["lags"] + 1, np.int64))
+
+    def _autocorr_peek(self):
+        """The sums of the unfinished interval, read WITHOUT disturbing them: read out (which zeroes
+        them in stream order) and set back to the same values, so that the device goes on adding
+        to exactly the numbers it held.  A read-out still pending from a checkpoint request is
+        fetched first and kept for `_finish_checkpoint`."""
+        eng = self.engine
+        if eng is None:
+            return self._ac_open
+        if self._ckpt_pending and self._ac_fetched is None:
+            self._ac_fetched = eng.fetch_autocorr()
+        eng.request_autocorr()
+        sums, n_pairs = eng.fetch_autocorr()
+        eng.autocorr_set(sums, n_pairs)
+        self._ac_open = (sums, n_pairs)
+        return self._ac_open
+
+    def _autocorr_product(self, combined=False):
+        """Sum over the intervals of the window, in their order, plus the unfinished interval ->
+        `AutoCorr`."""
+        cfg = self._ac
+        sums, n_pairs = self._autocorr_zero()
+        parts = list(self._ac_ivs)
+        if self._ac_fetched is not None:   # (requested, not filed yet: the newest interval)
+            parts.append(self._ac_fetched)
+        parts.append(self._autocorr_peek())
+        for s_, n_ in parts:
+            sums = sums + s_
+            n_pairs = n_pairs + n_
+        n_walkers = int(self.n_walkers)
+        if combined and self.size > 1:
+            # ONE host all-reduce, here and not in the loop; every process has accumulated the same
+            # snapshots, so the pair counts must agree
+            buf = np.concatenate((sums.reshape(-1), n_pairs.astype(np.float64), [float(n_walkers)]))
+            dist.all_reduce_sum(buf)
+            L1 = cfg["lags"] + 1
+            if not np.array_equal(buf[-1 - L1:-1], n_pairs.astype(np.float64) * self.size):
+                self._fail("autocorr: the processes hold different pair counts (this one %r, the sum "
+                           "over %d processes %r)", n_pairs.tolist(), self.size, buf[-1 - L1:-1].tolist())
+            sums, n_walkers = buf[:-1 - L1].reshape(sums.shape), int(buf[-1])
+        return autocorr_mod.AutoCorr(cfg["params"], cfg["lags"], cfg["interval_steps"], n_walkers,
+                                     sums, n_pairs)
+
+    def _load_autocorr(self, z):
+        """Resume: the configuration must be the one the sums were formed with; the sums of the
+        window's intervals and of the unfinished one come back, the ring does not (it refills: the
+        pairs that bridge the resume point are missing)."""
+        cfg = self._ac
+        if "ac_iv" not in z:
+            self._fail("autocorr: cannot resume -- the run was written without autocorr (the window "
+                       "of its sums cannot begin in mid-run)")
+        saved = ([str(p) for p in z["ac_params"]], int(z["ac_geometry"][0]), int(z["ac_geometry"][1]))
+        if saved != (cfg["params"], cfg["lags"], cfg["interval_steps"]):
+            self._fail("autocorr: cannot resume -- the run was written with params %r, lags %d and %d "
+                       "steps per lag, and now has %r, %d and %d (sums of different lags do not add "
+                       "up)", *saved, cfg["params"], cfg["lags"], cfg["interval_steps"])
+        self._ac_ivs = [(np.array(s_, dtype=np.float64), np.array(n_, dtype=np.int64))
+                        for s_, n_ in zip(z["ac_iv"], z["ac_iv_pairs"])]
+        if len(self._ac_ivs) != len(self._intervals):
+            self._fail("autocorr: the state file holds %d interval sums for %d intervals",
+                       len(self._ac_ivs), len(self._intervals))
+        # the unfinished interval goes back to the device, where the next accumulation adds to it
+        self.engine.autocorr_set(z["ac_open"], z["ac_open_pairs"])
+        self._ac_open = (np.array(z["ac_open"], dtype=np.float64), np.array(z["ac_open_pairs"], dtype=np.int64))
 
     def _init_bounds_ring(self):
         """`bounds_snapshots` ensemble snapshots on the device (mcmc_hip_bounds_configure)."""
@@ -826,6 +942,9 @@ class EnsembleMCMC:
         # marginals: the counts of every interval of `_intervals` (same index), the host's part of
         # the unfinished interval (counts, accumulations), a read-out fetched ahead of its checkpoint
         self._marg_ivs, self._marg_open, self._marg_fetched = [], None, None
+        # autocorr: the (sums, n_pairs) of every interval of `_intervals` (same index), a read-out
+        # fetched ahead of its checkpoint
+        self._ac_ivs, self._ac_fetched = [], None
         self._wsums = WindowSums()
         self._dropped_snapshots = 0
         self._progress_rows = {}  # i_learn -> row dict (DataFrame built on demand: `progress`)
@@ -969,6 +1088,21 @@ class EnsembleMCMC:
             m = self._marginals_product(combined=True)   # (collective: every process calls it)
             if self.rank == 0:
                 m.save(self._out_file(".marginals.npz"))
+        if self._ac:
+            ac = self._autocorr_product(combined=True)   # (collective: every process calls it)
+            if self.output and self.rank == 0:
+                ac.save(self._out_file(".autocorr.npz"))
+            worst = ac.worst()
+            if worst is None:
+                self.log.info("Autocorrelation: no lag beyond 0 was accumulated.")
+            elif worst[2]:
+                self.log.info("Autocorrelation: largest tau = %.4g steps (%s); a snapshot every %d "
+                              "steps decorrelates the rows.", worst[1] * ac.interval_steps, worst[0],
+                              ac.thin()[1])
+            else:
+                self.log.info("Autocorrelation: the window was not reached within %d lags of %d steps "
+                              "(%s: tau > %.4g steps); raise lags or moments_every.", ac.lags,
+                              ac.interval_steps, worst[0], worst[1] * ac.interval_steps)
 
     def advance(self):
         """One pass of the hot loop (the body of mcmc.py:451-528 for every walker): a fused
@@ -1008,6 +1142,8 @@ class EnsembleMCMC:
             eng.accumulate_moments()
             if self._marg:
                 eng.accumulate_marginals()
+            if self._ac:
+                eng.accumulate_autocorr()
             self._snaps_in_interval += 1
             self._bounds_take()
         snap_every = int(self.snapshot_every) if self.snapshot_every else None
@@ -1039,6 +1175,8 @@ class EnsembleMCMC:
             self.engine.request_moments()
         if self._marg:
             self.engine.request_marginals()
+        if self._ac:
+            self.engine.request_autocorr()
         self._ckpt_on_device = False
         if self._device_ckpt and self._snaps_in_interval > 0:
             self._begin_device_checkpoint()
@@ -1086,6 +1224,8 @@ class EnsembleMCMC:
                    else None)
         if self._marg and self._marg_fetched is None:
             self._marg_fetched = self.engine.fetch_marginals()
+        if self._ac and self._ac_fetched is None:
+            self._ac_fetched = self.engine.fetch_autocorr()
         dev = payload = None
         if self._ckpt_on_device and self._ckpt_solve_on_device:
             dev = self.engine.checkpoint_fetch()
@@ -1170,6 +1310,16 @@ class EnsembleMCMC:
                     len(self._marg_ivs), self._marg["n_counters"])
                 st["marg_open"] = self._marg_open[0]
                 st["marg_open_n"] = np.int64(self._marg_open[1])
+            if self._ac:
+                open_s, open_n = self._autocorr_peek()
+                L1, n_par = self._ac["lags"] + 1, len(self._ac["params"])
+                st["ac_params"] = np.array(self._ac["params"], dtype=str)
+                st["ac_geometry"] = np.array([self._ac["lags"], self._ac["interval_steps"]], dtype=np.int64)
+                st["ac_iv"] = np.array([s_ for s_, _ in self._ac_ivs], dtype=np.float64).reshape(
+                    len(self._ac_ivs), 3, L1, n_par)
+                st["ac_iv_pairs"] = np.array([n_ for _, n_ in self._ac_ivs], dtype=np.int64).reshape(
+                    len(self._ac_ivs), L1)
+                st["ac_open"], st["ac_open_pairs"] = open_s, open_n
             # the bounds ring: its books always, its snapshots while they are small (a resumed run
             # then forms the same Rminus1_cl; a large ring restarts empty)
             held = [k for k, j in enumerate(self._bslots) if j >= 0]
@@ -1310,6 +1460,8 @@ class EnsembleMCMC:
         self._iv0 = int(z["iv0"]) if "iv0" in z else 0
         if self._marg:
             self._load_marginals(z)
+        if self._ac:
+            self._load_autocorr(z)
         self._wsums = WindowSums()
         (self.n_steps_raw, self.i_learn, self._acc_last, self._steps_last, self._launches,
          self._dropped_snapshots, self._accepted_total) = (int(v) for v in book[:7])
@@ -1538,6 +1690,8 @@ class EnsembleMCMC:
         self._intervals = ivs = ivs[k:]
         if getattr(self, "_marg", None):
             self._marg_ivs = self._marg_ivs[k:]
+        if getattr(self, "_ac", None):
+            self._ac_ivs = self._ac_ivs[k:]
         self._iv0 += k
         if k:
             self._wsums.forget_below(self._iv0)
@@ -1570,6 +1724,14 @@ class EnsembleMCMC:
             self._marg_open = (np.zeros_like(counts), 0)
             if n_snap:
                 self._marg_ivs.append(counts)
+        if getattr(self, "_ac", None):
+            # the interval's sums: what the request at this checkpoint read out
+            fetched, self._ac_fetched = self._ac_fetched, None
+            if fetched is None:    # (an engine without queued read-outs: read them now)
+                eng.request_autocorr()
+                fetched = eng.fetch_autocorr()
+            if n_snap:
+                self._ac_ivs.append(fetched)
         if n_snap:
             self._intervals.append((n_snap, gs, S))
         if not self._intervals:
@@ -1771,6 +1933,8 @@ class EnsembleMCMC:
             # the window of the covariance and of R-1 (the later half of the run) plus the
             # unfinished interval, counted from every walker of every moment snapshot
             out["marginals"] = self._marginals_product(combined)
+        if getattr(self, "_ac", None):
+            out["autocorr"] = self._autocorr_product(combined)
         return out
 
     # ------------------------------------------------------------------ reference-style views
@@ -1835,6 +1999,8 @@ class EnsembleMCMC:
         if self.engine is not None:
             if self._marg and self._marg_open is not None:
                 self._marginals_drain()     # (the device's part of the unfinished interval)
+            if self._ac and self._ac_open is not None:
+                self._autocorr_peek()       # (kept for products() after close)
             self._materialise_row_views()   # products()/samples() stay valid after close
             self.engine.close()
             self.engine = None
@@ -1897,7 +2063,7 @@ class MCMCHip(EnsembleMCMC):
             return [], []
         head = re.escape(prefix) + (r"[\._]" if prefix else "")
         chain = re.compile(head + r"\d+\.txt$")
-        rest = re.compile(head + r"(checkpoint|progress|covmat|marginals\.npz|\d+\.(state\.npz|bounds\.npy|bounds_tags\.npy))$")
+        rest = re.compile(head + r"(checkpoint|progress|covmat|marginals\.npz|autocorr\.npz|\d+\.(state\.npz|bounds\.npy|bounds_tags\.npy))$")
         names = sorted(os.listdir(folder))
         return ([os.path.join(folder, n) for n in names if chain.match(n)],
                 [os.path.join(folder, n) for n in names if rest.match(n)])

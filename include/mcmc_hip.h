@@ -371,6 +371,41 @@ MCMC_HIP_API int mcmc_hip_marginals_set(mcmc_hip_ctx* h, const uint64_t* counts,
 MCMC_HIP_API int mcmc_hip_marginals_layout(const mcmc_hip_ctx* h, int64_t* n_counters, int32_t* n1, int32_t* bins1,
                               int32_t* n2, int32_t* bins2, int64_t* offset_pairs);
 
+/* Lagged cross-products of the ensemble for the integrated autocorrelation time
+ * (autocorr_kernels.hip).  Same life cycle as the marginals.  The engine keeps a ring of the last
+ * lags + 1 accumulated snapshots of the configured parameters and, per slot, the slot's group sums.
+ * The rule ("Autocorrelation"), all in float64 with separate roundings: with
+ * a[l,i] = x_t[i][l] - shift_i (the moment shift) and b[l,i] = x_{t-k}[i][l] - shift_i, per group g and
+ * configured dimension i, S_t[g,i] = sum_l a and P[g,k,i] = sum_l a*b are chains over the group's
+ * walkers in ascending order from +0.0; for every lag k = 0 .. min(lags, held - 1) the accumulators
+ * add the groups in ascending order from their current value: accP[k,i] += P[g,k,i],
+ * accA[k,i] += S_t[g,i], accB[k,i] += S_{t-k}[g,i], and n_pairs[k] += 1 once per accumulation.
+ * Lags not yet held are left untouched.
+ * configure: dims[n_dims] distinct sampler indices, 1 <= lags <= 64; allocates the ring
+ * ((lags + 1) n_dims W doubles) and zeroes the accumulators; n_dims = 0 frees them (the feature is
+ * off).  A bad call returns MCMC_HIP_ERR_ARG and names the argument; a ring that does not fit the
+ * free device memory names `lags` and the bytes needed.
+ * accumulate: two launches on the engine's stream (the group chains, the pooling), right after
+ * mcmc_hip_accumulate_moments on the same population; no host synchronisation, no allocation.
+ * MCMC_HIP_ERR_STATE without a state or before configure.
+ * request / fetch: `request` queues the copy of the accumulators to pinned host memory and their
+ * zeroing in stream order and keeps the ring, `fetch` waits for that copy only; sums[n] with
+ * n = n_doubles of `layout`, laid out [3][lags + 1][n_dims] (P, A, B), n_pairs[lags + 1].  One request
+ * may be pending.
+ * set: restores open accumulators (resume); synchronous.  The ring is not restored: it refills.
+ * reset: empties the ring (the accumulators stay).  The ring is otherwise emptied only by
+ * configure and by a change of the moment shift, which also zeroes the accumulators;
+ * mcmc_hip_set_state / set_full_state keep it.
+ * layout: n_dims, lags, n_doubles, snapshots held -- all zero: off; any pointer may be NULL. */
+MCMC_HIP_API int mcmc_hip_autocorr_configure(mcmc_hip_ctx* h, int32_t n_dims, const int32_t* dims, int32_t lags);
+MCMC_HIP_API int mcmc_hip_autocorr_accumulate(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_autocorr_request(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_autocorr_fetch(mcmc_hip_ctx* h, double* sums, int64_t n, int64_t* n_pairs);
+MCMC_HIP_API int mcmc_hip_autocorr_set(mcmc_hip_ctx* h, const double* sums, int64_t n, const int64_t* n_pairs);
+MCMC_HIP_API int mcmc_hip_autocorr_reset(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_autocorr_layout(const mcmc_hip_ctx* h, int32_t* n_dims, int32_t* lags, int64_t* n_doubles,
+                             int32_t* held);
+
 /* The learn / convergence checkpoint ON THE DEVICE (MCMC.check_convergence_and_learn_proposal,
  * mcmc.py:773-1032; checkpoint_kernels.hip): the intervals between checkpoints are kept in a
  * device ring, the statistics of the window (the later half of the run, mcmc.py:787-790) are

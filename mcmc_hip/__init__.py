@@ -57,6 +57,7 @@ else:
         checkpoint_lag: int | None = HIP_DEFAULTS["checkpoint_lag"]
         emit_thin: int | None = HIP_DEFAULTS["emit_thin"]
         marginals: bool | dict | None = HIP_DEFAULTS["marginals"]
+        autocorr: bool | dict | None = HIP_DEFAULTS["autocorr"]
 
         def _export_collection(self, coll):
             """Our table -> `cobaya.collection.SampleCollection` (same columns,
@@ -84,6 +85,8 @@ else:
                                 None))
                 # the histograms of `marginals` (written once, at the end of the run)
                 regexps.append((re.compile(output.prefix_regexp_str + r"marginals\.npz$"), None))
+                # the autocorrelation sums of `autocorr` (written once, at the end of the run)
+                regexps.append((re.compile(output.prefix_regexp_str + r"autocorr\.npz$"), None))
             return regexps
 
 
