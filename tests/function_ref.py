@@ -93,7 +93,8 @@ class FunctionRef:
         cyc, col = divmod(self.step, d)
         if cyc != self._cycle:
             g0 = self.walker0 // gs
-            self._V = np.array([self.p.basis(g0 + g, cyc) for g in range(self.W // gs)])
+            # (the cycle index is kept modulo 2^32: oracle, orc_run)
+            self._V = np.array([self.p.basis(g0 + g, cyc & 0xFFFFFFFF) for g in range(self.W // gs)])
             self._cycle = cyc
         return np.ascontiguousarray(self._V[:, col, :])
 

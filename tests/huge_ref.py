@@ -52,7 +52,8 @@ def run(prob, state, n_steps, walker0=0, step0=0, anchor=True):
     V = np.empty((G, ncyc, d, d))
     for g in range(G):
         for c in range(ncyc):
-            V[g, c] = np.asarray(prob.basis(walker0 // gs + g, c0 + c)).reshape(d, d)
+            # (the cycle index is kept modulo 2^32: oracle, orc_run)
+            V[g, c] = np.asarray(prob.basis(walker0 // gs + g, (c0 + c) & 0xFFFFFFFF)).reshape(d, d)
     inv = np.where(prob.kind == 1, 1.0 / prob.scale, 0.0)
     mls = np.where(prob.kind == 1, prob.mls, 0.0)
     arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in
