@@ -329,6 +329,14 @@ int mcmc_hip_create(const mcmc_hip_config* cfg, mcmc_hip_ctx** out)
         if (const char* e = getenv("MCMC_HIP_LOOKAHEAD")) h->lookahead = std::max(1, atoi(e));
         // MCMC_HIP_DUO (developer switch): 0 = the four-lane kernels always, 1 = the two-lane ones wherever they serve
         if (const char* e = getenv("MCMC_HIP_DUO")) h->duo = (e[0] && e[0] != '0') ? 1 : 0;
+        // MCMC_HIP_ACCEPT_SLACK (test switch): how far the accept variate's estimate must be from delta to
+        // decide a step of the two-lane kernels; inf = every step takes the exact branch
+        // (never below kAcceptSlack, what the proof at accept_lanes needs: a smaller or unparsable value is
+        // the default; a NaN makes every step exact like inf)
+        if (const char* e = getenv("MCMC_HIP_ACCEPT_SLACK")) {
+            const double v = strtod(e, nullptr);
+            h->accept_slack = v < mcmc::kAcceptSlack ? mcmc::kAcceptSlack : v;
+        }
         for (auto& D : h->dirs) acc(hipEventCreateWithFlags(&D.ready, hipEventDisableTiming));
         // MCMC_HIP_NO_PREFETCH (developer switch): directions on the main stream, in line
         h->prefetch = !getenv("MCMC_HIP_NO_PREFETCH");

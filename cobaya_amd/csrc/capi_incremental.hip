@@ -329,6 +329,7 @@ mcmc::IncStepArgs fill_inc_args(const mcmc_hip_ctx* h, const IncChoice& C, const
     a.mean = h->inc_mean.p;
     a.VW = C.carry_prior ? D.VW.p : nullptr;
     a.NL = C.carry_prior ? D.NL.p : nullptr;
+    a.accept_slack = h->accept_slack;
     for (int i = 0; i < d; ++i)
         if (h->periodic[i]) a.periodic_mask4[i >> 5] |= 1u << (i & 31);
     return a;
@@ -656,6 +657,31 @@ int mcmc_hip_set_whitened(mcmc_hip_ctx* h, const double* y)
 int mcmc_hip_incremental_carries_periodic(const mcmc_hip_ctx* h)
 {
     return h && inc_choice_of(h).carry_periodic ? 1 : 0;
+}
+
+int mcmc_hip_accept_estimate_error(double* max_err, uint32_t* ka_at_max)
+{
+    if (!max_err || !ka_at_max) return MCMC_HIP_ERR_ARG;
+    if (!mcmc_hip_launch_accept_estimate_error) return MCMC_HIP_ERR_ARG;   // (a build without incremental_duo.hip)
+    constexpr int nb = 4096;
+    double* derr = nullptr;
+    uint32_t* dka = nullptr;
+    std::vector<double> err(nb);
+    std::vector<uint32_t> ka(nb);
+    hipError_t r = hipMalloc(&derr, sizeof(double) * nb);
+    if (r == hipSuccess) r = hipMalloc(&dka, sizeof(uint32_t) * nb);
+    if (r == hipSuccess) r = mcmc_hip_launch_accept_estimate_error(derr, dka, nb, nullptr);
+    if (r == hipSuccess) r = hipMemcpy(err.data(), derr, sizeof(double) * nb, hipMemcpyDeviceToHost);
+    if (r == hipSuccess) r = hipMemcpy(ka.data(), dka, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost);
+    if (derr) (void)hipFree(derr);
+    if (dka) (void)hipFree(dka);
+    if (r != hipSuccess) return MCMC_HIP_ERR_DEVICE;
+    int at = 0;
+    for (int b = 1; b < nb; ++b)
+        if (err[b] > err[at] || err[b] != err[b]) at = b;   // (a NaN wins)
+    *max_err = err[at];
+    *ka_at_max = ka[at];
+    return MCMC_HIP_OK;
 }
 
 int mcmc_hip_incremental_carries_modes(const mcmc_hip_ctx* h)

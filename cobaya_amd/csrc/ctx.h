@@ -201,6 +201,8 @@ struct mcmc_hip_ctx {
     // incremental_duo.hip (two lanes per walker): -1 = where the ensemble fills the chip with it
     // (kDuoMinWalkers), 0 = never, 1 = wherever the kernel serves the model (MCMC_HIP_DUO)
     int duo = -1;
+    // IncStepArgs::accept_slack of the one-mode two-lane kernel (MCMC_HIP_ACCEPT_SLACK; inf: every step exact)
+    double accept_slack = mcmc::kAcceptSlack;
     hipEvent_t T_event = nullptr;            // main stream: behind the last write of dT
     bool T_fresh = false;                    // ... which no direction set has been ordered behind yet
     // asynchronous checkpoint (mcmc_hip_request_moments / mcmc_hip_fetch_moments) and

@@ -45,7 +45,10 @@ __device__ __forceinline__ u32x4 philox4x32_10(uint32_t k0, uint32_t k1, uint32_
 {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
-        // v_mul_hi_u32 + v_mul_lo_u32 (full rate each) beat one v_mad_u64_u32 (half rate, measured)
+        // v_mul_hi_u32 + v_mul_lo_u32 per product, not one v_mad_u64_u32: tools/probes/valu_op_cost.hip
+        // (profiles/r02_probe_valu_op_cost.log) has the pair at 8.8 clocks against 5.7 at four waves per SIMD,
+        // but in the two-lane step kernel (two waves per SIMD) the 64-bit form, 14 vector instructions fewer per
+        // block, measured 0.9 % slower in bench.py (profiles/r12_lazy_accept.txt)
         const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
         const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
         const uint32_t n0 = hi1 ^ c1 ^ k0;
@@ -174,7 +177,10 @@ struct StepRng {
     }
     __device__ __forceinline__ void round()
     {
-        // v_mul_hi_u32 + v_mul_lo_u32 (full rate each) beat one v_mad_u64_u32 (half rate, measured)
+        // v_mul_hi_u32 + v_mul_lo_u32 per product, not one v_mad_u64_u32: tools/probes/valu_op_cost.hip
+        // (profiles/r02_probe_valu_op_cost.log) has the pair at 8.8 clocks against 5.7 at four waves per SIMD,
+        // but in the two-lane step kernel (two waves per SIMD) the 64-bit form, 14 vector instructions fewer per
+        // block, measured 0.9 % slower in bench.py (profiles/r12_lazy_accept.txt)
         const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
         const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
         const uint32_t n0 = hi1 ^ c1 ^ k0;
@@ -375,10 +381,76 @@ __device__ __attribute__((noinline)) double pair_tail(uint32_t key0, uint32_t ke
     return fma(bits, LN2, -dlog(u52(((uint64_t)q.w0 << 20) | (q.w1 >> 12))));
 }
 
+// The accept variate, LAZILY exact (the one-mode two-lane kernel, incremental_duo.hip: step_inc_duo_kernel).  Ea is used for one thing,
+// the comparison Ea > delta, and a comparison needs all 53 bits only where its sides nearly meet.  The
+// burst therefore stages, instead of Ea = neg_log_short(2 ka + 1, 29), the integer ka and a single-precision
+// estimate ea_f = (29 - log2 n) ln 2, n = 2 ka + 1: v_cvt_f32_u32, v_log_f32 and one multiply-add -- 6
+// instructions with the NaN of the lowest bin against 21 --, packed into the 8 bytes Ea had (low word ea_f,
+// high word ka: a staged entry stays 16 bytes).  accept_lanes() below decides the step from it and computes
+// the exact Ea only for a wave that holds a lane in doubt.
+//     |ea_f - Ea| <= kAcceptSlack / 4 for every ka in [1, 2^28) ON THE DEVICE
+// is what the decision rests on (measured over all of them by accept_estimate_error_kernel,
+// tests/test_gpu_lazy_accept.py: 2.29e-6 on an MI355X -- the conversion's 2^-25 n, one ulp of a log2 below 29
+// and the rounding of a result below 21 add up to 2.5e-6 --; kAcceptSlack / 4 = 1.5e-5).
+// (kAcceptSlack = 2^-14: kernels.h, beside IncStepArgs::accept_slack)
+__device__ __forceinline__ float accept_estimate(uint32_t ka)
+{
+    constexpr float LN2F = (float)6.93147180559945286227e-01;            // RN(ln 2)
+    constexpr float B_LN2F = (float)(29.0 * 6.93147180559945286227e-01);   // RN(29 ln 2)
+    const float l = __builtin_amdgcn_logf((float)(2u * ka + 1u));
+    return __builtin_fmaf(-l, LN2F, B_LN2F);
+}
+// (ea_f, ka) in the place of Ea; ka == 0 (the lowest bin, redrawn at full width: pair_tail) -> NaN
+__device__ __forceinline__ double accept_pack(uint32_t ka)
+{
+    const int e = sel(lanes(ka == 0u), 0x7FC00000, __float_as_int(accept_estimate(ka)));
+    return __hiloint2double((int)ka, e);
+}
+// the exact accept variate of `step` from its ka (oracle: walker_variates_pair)
+__device__ __forceinline__ double accept_exact(uint32_t ka, uint32_t key0, uint32_t key1, uint32_t gid,
+                                               unsigned long long step, short_log_tab tab)
+{
+    double Ea = neg_log_short(2u * ka + 1u, 29, tab);
+    if (lanes(ka == 0u) != 0ull) {   // wave-uniform, rare: the lowest bin
+        const double ta = pair_tail(key0, key1, gid, step, 1u, 28.0);
+        Ea = ka == 0u ? ta : Ea;
+    }
+    return Ea;
+}
+// The lanes with Ea > delta, bit for bit the exact comparison's.  dd = RN(ea_f - delta) (ea_f converts to
+// double exactly).  A lane is CERTAIN when |dd| > slack, and a wave of certain lanes answers dd > 0.
+// Proof that this is Ea > delta, for slack >= kAcceptSlack: let D = ea_f - delta in real numbers.  The one
+// rounding keeps the sign and moves the magnitude by a factor within 1 +- 2^-53 (delta is finite here, see
+// below; a difference of doubles does not underflow to zero), so |D| >= |dd| (1 - 2^-53) > slack (1 - 2^-53) >
+// slack / 4 >= |ea_f - Ea|, and Ea - delta = D - (ea_f - Ea) has the sign of D, which is the sign of dd, and
+// is not zero.  delta is whatever double the caller formed -- lpost - lt, or the quotient (lpost - lt) / T at
+// a temperature other than one: the comparison is with THAT double in both forms, so its own rounding does
+// not enter.  delta = +-inf gives dd = -+inf, certain, and dd > 0 is Ea > delta for every finite Ea.  A NaN
+// -- delta's, or the ea_f of ka == 0 -- makes |dd| > slack false: not certain.  If any lane is not certain
+// the whole wave (a wave-uniform branch, ~2 slack x 32 walkers = 0.4 % of the wave-steps) computes the
+// exact Ea and compares as the oracle does.  slack = inf (MCMC_HIP_ACCEPT_SLACK=inf): every step is exact.
+__device__ __forceinline__ unsigned long long accept_lanes(double ea_ka, double delta, double slack,
+                                                           uint32_t key0, uint32_t key1, uint32_t gid,
+                                                           unsigned long long step, short_log_tab tab)
+{
+    const double dd = (double)__int_as_float(__double2loint(ea_ka)) - delta;
+    // (both compares before the branch: the certain path is then straight-line code.  With dd > 0 taken
+    // behind the test of the doubt the compiler laid the certain path over two taken branches, and the
+    // headline kernel gained 0.4 % instead of 2.2 %: profiles/r12_lazy_accept.txt)
+    unsigned long long up = lanes(dd > 0.0);
+    if (__builtin_expect(lanes(fabs(dd) > slack) != lanes(true), 0)) {
+        const double Ea = accept_exact((uint32_t)__double2hiint(ea_ka), key0, key1, gid, step, tab);
+        up = lanes(Ea > delta);
+    }
+    return up;
+}
+
 struct PairRng {
+    // Ea: the exact accept variates (run), or accept_pack() of their ka (run_lazy)
     double r[2], Ea[2];
-    __device__ __forceinline__ void run(uint32_t key0, uint32_t key1, uint32_t gid,
-                                        unsigned long long pair, short_log_tab tab)
+    template <bool LAZY>
+    __device__ __forceinline__ void draw(uint32_t key0, uint32_t key1, uint32_t gid,
+                                         unsigned long long pair, short_log_tab tab)
     {
         StepRng g;
         g.begin(key0, key1, gid, pair);
@@ -392,13 +464,15 @@ struct PairRng {
             const uint32_t kr = ((a & 0xFFFFFu) << 4) | (b >> 28);
             const uint32_t ka = b & 0x0FFFFFFFu;
             double Er = neg_log_short(2u * kr + 1u, 25, tab);
-            double Eah = neg_log_short(2u * ka + 1u, 29, tab);
-            if (lanes((kr == 0u) | (ka == 0u)) != 0ull) {   // wave-uniform, rare: the lowest bins
+            double Eah = LAZY ? accept_pack(ka) : neg_log_short(2u * ka + 1u, 29, tab);
+            if (lanes(LAZY ? kr == 0u : ((kr == 0u) | (ka == 0u))) != 0ull) {   // wave-uniform, rare: the lowest bins
                 const unsigned long long step = 2ull * pair + (unsigned long long)h;
                 const double tr = pair_tail(key0, key1, gid, step, 0u, 24.0);
-                const double ta = pair_tail(key0, key1, gid, step, 1u, 28.0);
                 Er = kr == 0u ? tr : Er;
-                Eah = ka == 0u ? ta : Eah;
+                if (!LAZY) {
+                    const double ta = pair_tail(key0, key1, gid, step, 1u, 28.0);
+                    Eah = ka == 0u ? ta : Eah;
+                }
             }
             // (2 E_r lies in [2^-24, 35], or up to ~110 after a redraw of the tail)
             const double rr = sel(lanes(((a >> 20) & 0x7FFu) < 676u), Er, sqrt_midrange(2.0 * Er));
@@ -407,6 +481,18 @@ struct PairRng {
                                         ((long long)(~a & 0x80000000u) << 32));
             Ea[h] = Eah;
         }
+    }
+    // the exact mode (step_duo_mix_kernel and the kernels that keep their own staging:
+    // incremental_kernels.hip, incremental_any.hip, huge_kernels.hip)
+    __device__ __forceinline__ void run(uint32_t key0, uint32_t key1, uint32_t gid,
+                                        unsigned long long pair, short_log_tab tab)
+    {
+        draw<false>(key0, key1, gid, pair, tab);
+    }
+    __device__ __forceinline__ void run_lazy(uint32_t key0, uint32_t key1, uint32_t gid,
+                                             unsigned long long pair, short_log_tab tab)
+    {
+        draw<true>(key0, key1, gid, pair, tab);
     }
 };
 

@@ -37,6 +37,13 @@
 // steps (bench.py: 0.902 -> 0.856), 20 % fewer vector instructions; chains {2 h, 2 h + 1} (16 rows,
 // two padded) 4 % slower than {h, h + 2}; the next step's pairs requested a step ahead 22 % slower.
 // Below 65 536 walkers the four-lane kernel is as fast or faster (inc_choice.h: kDuo1MinWalkers).
+// The accept variate of the one-mode kernel is lazily exact (round 12; det_math.h: PairRng::run_lazy, accept_lanes):
+// the burst stages a single-precision estimate of Ea and its 28-bit integer, the step takes the exact logarithm only
+// for a wave with a lane within 2^-14 of delta.  Measured (profiles/r12_lazy_accept.txt, same box, parent / new
+// alternated four times): step kernel 0.8579 -> 0.8387 ms (-2.2 %), bench.py 8.483e10 -> 8.664e10 (+2.1 %; the
+// parent's spread was 0.59 %); 3.2 % fewer vector instructions per launch.  With the certain path laid over two
+// taken branches the same instructions gained 0.4 %.  step_duo_mix_kernel keeps the exact staging: at K = 2 the
+// lazy form measured 1.881 -> 1.850 ms per 1 200 steps, inside three times the parent's spread (1.2 %).
 //
 // Served: Metropolis steps, no periodic parameter, no emitted rows, no block of one parameter, whole
 // workgroups of 128 walkers inside one basis group -- for ensembles that fill the chip with it
@@ -92,6 +99,8 @@ struct DuoVariates {
         off = base;
     }
     // the two pairs of the step pair 4 * octet + 2 h + q (q = 0, 1), as soon as they are drawn
+    // (step_inc_duo_kernel draws with PairRng::run_lazy: the second half of a pair is then accept_pack(ka), what
+    // accept_lanes takes; step_duo_mix_kernel keeps the exact Ea of PairRng::run)
     __device__ __forceinline__ void put(pair_t* sRE, int wave, int lane, int h, int q, const PairRng& p)
     {
         pair_t* const mine = sRE + ((wave * 8 + 4 * h + 2 * q) * kDuoRow + (lane >> 1));
@@ -676,7 +685,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
 #pragma unroll 1
                 for (int q = 0; q < 2; ++q) {   // (rolled: one Philox block's registers at a time)
                     PairRng pr;
-                    pr.run(s.key0, s.key1, gid, (cur_oct << 2) + (unsigned long long)(2 * h + q), slog);
+                    pr.run_lazy(s.key0, s.key1, gid, (cur_oct << 2) + (unsigned long long)(2 * h + q), slog);
                     sv.put(sRE, wave, lane, h, q, pr);
                 }
                 sv.seek(S);
@@ -719,7 +728,11 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
             const double ll = fma(mhr, fma(r, uu, yu + yu), llik);
             const double lt = lp + ll;
             const double delta = UNIT_T ? (lpost - lt) : (lpost - lt) / s.temperature;
-            const unsigned long long acc_m = inside_m & (lanes(lt > lpost) | lanes(Ea > delta));
+            // (Ea > delta from the staged estimate, exact where in doubt: det_math.h accept_lanes.  At T = 1
+            // lt > lpost is delta = lpost - lt < 0 < Ea, already in it; at other temperatures the compare stays)
+            const unsigned long long up_m = UNIT_T ? 0ull : lanes(lt > lpost);
+            const unsigned long long acc_m =
+                inside_m & (up_m | accept_lanes(Ea, delta, a.accept_slack, s.key0, s.key1, gid, S, slog));
             const bool accept = __builtin_amdgcn_inverse_ballot_w64(acc_m);
             llik = accept ? ll : llik;
             int lim = lim1;
@@ -764,6 +777,34 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
         s.n_accept[we] = nacc0 + nacc;
     }
     wave_add_accepts(s.accept_total, (h == 0) ? nacc : 0);
+}
+
+// max |ea_f - Ea| over this block's share of ka = 1 .. 2^28 - 1 (Ea = neg_log_short(2 ka + 1, 29), the
+// value the estimate stands for): the condition on the hardware's log2 that accept_lanes rests on
+__global__ void __launch_bounds__(256) accept_estimate_error_kernel(double* err, uint32_t* at)
+{
+    __shared__ dpair_t short_log_lds[SHORT_LOG_TABLE_SIZE];
+    const short_log_tab slog = short_log_load(short_log_lds);
+    __shared__ double serr[256];
+    __shared__ uint32_t sat[256];
+    __syncthreads();
+    const unsigned long long n = 1ull << 28, stride = (unsigned long long)gridDim.x * 256ull;
+    double worst = -1.0;
+    uint32_t where = 0u;
+    for (unsigned long long k = 1ull + blockIdx.x * 256ull + threadIdx.x; k < n; k += stride) {
+        const uint32_t ka = (uint32_t)k;
+        const double e = fabs((double)accept_estimate(ka) - neg_log_short(2u * ka + 1u, 29, slog));
+        if (e > worst || e != e) { worst = e; where = ka; }   // (a NaN stays and fails the check)
+    }
+    serr[threadIdx.x] = worst;
+    sat[threadIdx.x] = where;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < 256; ++i)
+            if (serr[i] > worst || serr[i] != serr[i]) { worst = serr[i]; where = sat[i]; }
+        err[blockIdx.x] = worst;
+        at[blockIdx.x] = where;
+    }
 }
 
 template <int DQ, int NE, bool SPLIT>
@@ -835,5 +876,12 @@ extern "C" hipError_t mcmc_hip_launch_inc_duo1(const mcmc::IncStepArgs* a, hipSt
     for (int q = 0; q < 4; ++q)
         if (a->periodic_mask4[q]) return hipErrorInvalidValue;
     return mcmc::dispatch_duo1<1>(*a, st);
+}
+
+extern "C" hipError_t mcmc_hip_launch_accept_estimate_error(double* err, uint32_t* ka, int n_blocks, hipStream_t st)
+{
+    if (n_blocks < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mcmc::accept_estimate_error_kernel, dim3(n_blocks), dim3(256), 0, st, err, ka);
+    return hipGetLastError();
 }
 #endif

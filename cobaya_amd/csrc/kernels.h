@@ -275,7 +275,12 @@ struct IncStepArgs {
     // and NL[G][n_steps][2] = (v.w, loc.w) in the four-chain pattern; re-anchored with `anchor`
     const double* VW;
     const double* NL;
+    // the one-mode two-lane kernel (incremental_duo.hip) decides a step from a single-precision estimate of the
+    // accept variate where it is further than this from delta, and from the exact one elsewhere
+    // (det_math.h: accept_lanes); kAcceptSlack, or MCMC_HIP_ACCEPT_SLACK (inf: every step exact)
+    double accept_slack;
 };
+constexpr double kAcceptSlack = 0x1p-14;
 
 struct IncDirArgs {
     const double* V;       // the basis kernels' buffer [G][ncyc][slab], column stride ld
@@ -366,6 +371,10 @@ extern "C" int mcmc_hip_inc_any_fits(int d, int n_modes, int n_periodic, int n_w
 extern "C" hipError_t mcmc_hip_launch_inc_duo_1(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
 extern "C" hipError_t mcmc_hip_launch_inc_duo_9(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
 extern "C" hipError_t mcmc_hip_launch_inc_duo1(const mcmc::IncStepArgs*, hipStream_t) MCMC_HIP_OPTIONAL;
+// max |ea_f - Ea| of the accept variate's estimate over ka in [1, 2^28): err[n_blocks], ka[n_blocks]
+// (the largest of block b's share and where it is); incremental_duo.hip
+extern "C" hipError_t mcmc_hip_launch_accept_estimate_error(double* err, uint32_t* ka, int n_blocks,
+                                                            hipStream_t) MCMC_HIP_OPTIONAL;
 
 #define MCMC_DECLARE_BIG(DP) extern "C" const mcmc::BigKernels* mcmc_hip_big_##DP() __attribute__((weak));
 #define MCMC_DECLARE_PAIR(D) extern "C" const mcmc::PairKernels* mcmc_hip_pair_##D() __attribute__((weak));

@@ -541,6 +541,12 @@ MCMC_HIP_API int mcmc_hip_incremental_carries_modes(const mcmc_hip_ctx* h);
  * moved residual at a step that wraps; 0: the coordinate passes through the wrap at every step
  * (the general kernels).  The specification (oracle: carry_periodic) takes the rule from here. */
 MCMC_HIP_API int mcmc_hip_incremental_carries_periodic(const mcmc_hip_ctx* h);
+/* test entry: the two-lane incremental kernels decide `Ea > delta` from a single-precision estimate
+ * ea_f of the accept variate Ea = -log((2 ka + 1) 2^-29) wherever the two are further apart than
+ * 2^-14, which is right as long as |ea_f - Ea| <= 2^-16 for every 28-bit ka.  Runs a small kernel
+ * over ka = 1 .. 2^28 - 1 on the current device (milliseconds): the largest |ea_f - Ea| and the ka
+ * that attains it. */
+MCMC_HIP_API int mcmc_hip_accept_estimate_error(double* max_err, uint32_t* ka_at_max);
 MCMC_HIP_API int mcmc_hip_get_mode_logdensities(mcmc_hip_ctx* h, double* a);
 MCMC_HIP_API int mcmc_hip_set_mode_logdensities(mcmc_hip_ctx* h, const double* a);
 
