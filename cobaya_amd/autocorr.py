@@ -1,5 +1,5 @@
-"""Integrated autocorrelation times of the ensemble: the product (`AutoCorr`) and the sampler option
-behind it (`parse_option`).
+"""Integrated autocorrelation times of the ensemble: the product (`AutoCorr`), the sampler option
+behind it (`parse_option`) and what the sampler holds of it while it runs (`AutoCorrAccumulator`).
 
 The sums come from the engine (mcmc_hip_autocorr_*; autocorr_kernels.hip), which multiplies every
 moment snapshot of the window with the previous `lags` snapshots, walker by walker.  The rule
@@ -19,6 +19,8 @@ from __future__ import annotations
 import math
 
 import numpy as np
+
+from .engine import EngineError
 
 MAX_LAGS = 64               # autocorr_args.h: kAcMaxLags
 DEFAULT_LAGS = 16
@@ -137,6 +139,19 @@ class AutoCorr:
                 best = (n, t, ok)
         return best
 
+    def summary(self, c=5.0):
+        """One line for the log at the end of a run."""
+        worst = self.worst(c)
+        if worst is None:
+            return "Autocorrelation: no lag beyond 0 was accumulated."
+        if worst[2]:
+            return ("Autocorrelation: largest tau = %.4g steps (%s); a snapshot every %d "
+                    "steps decorrelates the rows." % (worst[1] * self.interval_steps, worst[0],
+                                                      self.thin(c=c)[1]))
+        return ("Autocorrelation: the window was not reached within %d lags of %d steps "
+                "(%s: tau > %.4g steps); raise lags or moments_every." % (
+                    self.lags, self.interval_steps, worst[0], worst[1] * self.interval_steps))
+
     # -- arithmetic, files
     def __add__(self, other):
         if not isinstance(other, AutoCorr):
@@ -205,3 +220,145 @@ def parse_option(opt, sampled):
             or not 1 <= int(lags) <= MAX_LAGS:
         raise AutoCorrError(f"autocorr: lags must be an integer in 1..{MAX_LAGS}, got {lags!r}")
     return {"params": params, "lags": int(lags)}
+
+
+# ---------------------------------------------------------------------------------- the sampler's side
+ENGINE_METHODS = ("configure_autocorr", "accumulate_autocorr", "request_autocorr", "fetch_autocorr",
+                  "autocorr_set", "autocorr_reset", "autocorr_layout")
+
+
+class AutoCorrAccumulator:
+    """What the sampler holds of the sums while it runs: a device product, with the methods
+    `marginals.MarginalsAccumulator` states.
+
+    HERE the sums are floats and the unfinished interval is NEVER split: it stays on the device,
+    `_peek` reads it without disturbing it, and an interval's sums are the requested read-out alone
+    (a host part would change the order of the additions, hence the bits).  `open`: the open sums
+    as last read, which is what a product is formed from once the engine is gone."""
+
+    name, reports = "autocorr", True
+
+    def __init__(self, cfg, spec, host):
+        self.cfg, self.spec, self.host, self.engine = cfg, spec, host, None
+        self.ivs, self.open, self.fetched = [], None, None
+
+    @classmethod
+    def from_option(cls, opt, spec, engine_factory, host):
+        try:
+            cfg = parse_option(opt, spec.sampled)
+        except AutoCorrError as e:
+            host.fail("%s", str(e), cause=e)
+        if cfg is None:
+            return None
+        if not all(hasattr(engine_factory, m) for m in ENGINE_METHODS):
+            host.fail("autocorr: this engine has no lagged cross-products (its library predates "
+                      "mcmc_hip_autocorr_*)")
+        cfg["interval_steps"] = int(host.snapshot_steps)   # one lag, fixed for the run
+        return cls(cfg, spec, host)
+
+    def attach(self, engine, resumed=False, centre=None, covmat=None):
+        """Hand the configuration to the engine (which allocates the ring, or refuses it)."""
+        cfg, self.engine = self.cfg, engine
+        self.accumulate, self.request = engine.accumulate_autocorr, engine.request_autocorr
+        try:
+            engine.configure_autocorr([self.spec.sampled.index(n) for n in cfg["params"]], cfg["lags"])
+        except EngineError as e:
+            self.host.fail("autocorr: %s", str(e), cause=e)
+        lay = engine.autocorr_layout()
+        if (lay["n_dims"], lay["lags"]) != (len(cfg["params"]), cfg["lags"]):
+            self.host.fail("autocorr: the engine lays its sums out differently (%r) from the product", lay)
+        self.open = self._zero()
+
+    def _zero(self):
+        L1 = self.cfg["lags"] + 1
+        return np.zeros((3, L1, len(self.cfg["params"]))), np.zeros(L1, np.int64)
+
+    def fetch_requested(self):
+        if self.fetched is None:
+            self.fetched = self.engine.fetch_autocorr()
+
+    def _peek(self, pending):
+        """The sums of the unfinished interval, read WITHOUT disturbing them: read out (which zeroes
+        them in stream order) and set back to the same values, so that the device goes on adding
+        to exactly the numbers it held."""
+        eng = self.engine
+        if eng is not None:
+            if pending:
+                self.fetch_requested()
+            eng.request_autocorr()
+            self.open = eng.fetch_autocorr()
+            eng.autocorr_set(*self.open)
+        return self.open
+
+    def file(self, n_snap):
+        """The interval's sums: what the request at this checkpoint read out."""
+        fetched, self.fetched = self.fetched, None
+        if fetched is None:    # (no read-out was queued: request and fetch now)
+            self.engine.request_autocorr()
+            fetched = self.engine.fetch_autocorr()
+        if n_snap:
+            self.ivs.append(fetched)
+
+    def drop(self, k):
+        self.ivs = self.ivs[k:]
+
+    def product(self, intervals, combined=False, pending=False):
+        """The intervals of the window, in their order, plus the unfinished interval."""
+        cfg, host = self.cfg, self.host
+        sums, n_pairs = self._zero()
+        parts = list(self.ivs)
+        if self.fetched is not None:   # (requested, not filed yet: the newest interval)
+            parts.append(self.fetched)
+        parts.append(self._peek(pending))
+        for s_, n_ in parts:
+            sums = sums + s_
+            n_pairs = n_pairs + n_
+        n_walkers = int(host.n_walkers)
+        if combined and host.size > 1:
+            # ONE host all-reduce, here and not in the loop; every process has accumulated the same
+            # snapshots, so the pair counts must agree
+            buf = np.concatenate((sums.reshape(-1), n_pairs.astype(np.float64), [float(n_walkers)]))
+            host.all_reduce_sum(buf)
+            L1 = cfg["lags"] + 1
+            if not np.array_equal(buf[-1 - L1:-1], n_pairs.astype(np.float64) * host.size):
+                host.fail("autocorr: the processes hold different pair counts (this one %r, the sum "
+                          "over %d processes %r)", n_pairs.tolist(), host.size, buf[-1 - L1:-1].tolist())
+            sums, n_walkers = buf[:-1 - L1].reshape(sums.shape), int(buf[-1])
+        return AutoCorr(cfg["params"], cfg["lags"], cfg["interval_steps"], n_walkers, sums, n_pairs)
+
+    def save(self, pending):
+        cfg, n = self.cfg, len(self.ivs)
+        open_s, open_n = self._peek(pending)
+        L1, n_par = cfg["lags"] + 1, len(cfg["params"])
+        return {"ac_params": np.array(cfg["params"], dtype=str),
+                "ac_geometry": np.array([cfg["lags"], cfg["interval_steps"]], dtype=np.int64),
+                "ac_iv": np.array([s_ for s_, _ in self.ivs], dtype=np.float64).reshape(n, 3, L1, n_par),
+                "ac_iv_pairs": np.array([n_ for _, n_ in self.ivs], dtype=np.int64).reshape(n, L1),
+                "ac_open": open_s, "ac_open_pairs": open_n}
+
+    def load(self, z, n_intervals):
+        """Resume: the configuration must be the one the sums were formed with; the sums of the
+        window's intervals and of the unfinished one come back, the ring does not (it refills: the
+        pairs that bridge the resume point are missing)."""
+        cfg, fail = self.cfg, self.host.fail
+        if "ac_iv" not in z:
+            fail("autocorr: cannot resume -- the run was written without autocorr (the window "
+                 "of its sums cannot begin in mid-run)")
+        saved = ([str(p) for p in z["ac_params"]], int(z["ac_geometry"][0]), int(z["ac_geometry"][1]))
+        if saved != (cfg["params"], cfg["lags"], cfg["interval_steps"]):
+            fail("autocorr: cannot resume -- the run was written with params %r, lags %d and %d "
+                 "steps per lag, and now has %r, %d and %d (sums of different lags do not add "
+                 "up)", *saved, cfg["params"], cfg["lags"], cfg["interval_steps"])
+        self.ivs = [(np.array(s_, dtype=np.float64), np.array(n_, dtype=np.int64))
+                    for s_, n_ in zip(z["ac_iv"], z["ac_iv_pairs"])]
+        if len(self.ivs) != n_intervals:
+            fail("autocorr: the state file holds %d interval sums for %d intervals",
+                 len(self.ivs), n_intervals)
+        # the unfinished interval goes back to the device, where the next accumulation adds to it
+        self.engine.autocorr_set(z["ac_open"], z["ac_open_pairs"])
+        self.open = (np.array(z["ac_open"], dtype=np.float64), np.array(z["ac_open_pairs"], dtype=np.int64))
+
+    def detach(self, pending=False):
+        if self.open is not None:
+            self._peek(pending)       # (kept for product() after the engine is gone)
+        self.engine = self.accumulate = self.request = None

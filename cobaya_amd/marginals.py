@@ -1,5 +1,6 @@
-"""Streaming marginal histograms of the ensemble: the product (`Marginals`) and the sampler
-option behind it (`parse_option`, `resolve_ranges`).
+"""Streaming marginal histograms of the ensemble: the product (`Marginals`), the sampler option
+behind it (`parse_option`, `resolve_ranges`) and what the sampler holds of it while it runs
+(`MarginalsAccumulator`, which also states the methods every device product has).
 
 The counts come from the engine (mcmc_hip_marginals_*; marginal_kernels.hip), which adds every
 walker of every moment snapshot of the window -- not only the rows `max_rows` retains.  The rule
@@ -10,6 +11,8 @@ falls in the last bin, a value on an interior edge in the upper one.
 from __future__ import annotations
 
 import numpy as np
+
+from .engine import EngineError
 
 MAX_BINS_1D = 1024          # marginal_args.h: kMargMaxBins1
 MAX_BINS_2D = 64            # marginal_args.h: kMargMaxBins2
@@ -298,3 +301,183 @@ def resolve_ranges(cfg, spec, centre=None, covmat=None):
                                  "an explicit range")
         out[n] = (lo, hi)
     return out
+
+
+# ---------------------------------------------------------------------------------- the sampler's side
+ENGINE_METHODS = ("configure_marginals", "accumulate_marginals", "request_marginals",
+                  "fetch_marginals", "marginals_set")
+
+
+class MarginalsAccumulator:
+    """What the sampler holds of the histograms while it runs.  A DEVICE PRODUCT is a class with
+    these methods, listed in `EnsembleMCMC.PRODUCT_CLASSES` (the other one: `AutoCorrAccumulator`):
+
+      from_option(opt, spec, engine_factory, host) -> the object, or None where the option is off;
+          refuses by the option's name BEFORE the engine is created.  `host` is what the sampler hands
+          in: fail(msg, *args, cause=None), n_walkers, size, all_reduce_sum, temperature,
+          snapshot_steps (the steps between two moment snapshots)
+      attach(engine, resumed, centre, covmat): configure the engine, cross-check its layout
+      accumulate(), request(): beside every moment snapshot; beside every checkpoint request
+      fetch_requested(): the requested read-out, kept in `fetched` until file(n_snap) closes the
+          interval (an entry of `ivs` if n_snap is non-zero: one per interval of the window)
+      drop(k): the window moved forward by k intervals
+      save(pending) -> arrays for the state file, load(z, n_intervals): from it
+      product(intervals, combined, pending); detach(pending): the engine goes, product() still works
+      name, reports: the option, the key in products() and the file `prefix.<name>.npz`; whether the
+          product has a summary() for the log
+    `pending`: a checkpoint is requested and not processed yet -- its read-out is then fetched before
+    anything else is read, and a product counts it as the newest interval.
+
+    HERE the counts are integers and the unfinished interval is split: `open` is the host's part
+    (counts, accumulations), the device holds the rest, and `_drain` moves that over (which zeroes
+    it on the device).  Where the counts are held changes no sum."""
+
+    name, reports = "marginals", False
+
+    def __init__(self, cfg, spec, host):
+        self.cfg, self.spec, self.host, self.engine = cfg, spec, host, None
+        self.ivs, self.open, self.fetched = [], None, None
+
+    @classmethod
+    def from_option(cls, opt, spec, engine_factory, host):
+        try:
+            cfg = parse_option(opt, spec.sampled)
+        except MarginalsError as e:
+            host.fail("%s", str(e), cause=e)
+        if cfg is None:
+            return None
+        if host.temperature != 1:
+            host.fail("marginals: the histograms count the walkers as they are, which at temperature %g "
+                      "follow the tempered law, not the posterior; use temperature: 1 or turn "
+                      "marginals off", host.temperature)
+        if not all(hasattr(engine_factory, m) for m in ENGINE_METHODS):
+            host.fail("marginals: this engine has no marginal histograms (its library predates "
+                      "mcmc_hip_marginals_*)")
+        return cls(cfg, spec, host)
+
+    def attach(self, engine, resumed=False, centre=None, covmat=None):
+        """Fix the ranges and hand the layout to the engine.  A resumed run repeats the ranges of
+        the state file: `load` configures the engine."""
+        self.engine = engine
+        self.accumulate, self.request = engine.accumulate_marginals, engine.request_marginals
+        if resumed:
+            return
+        try:
+            ranges = resolve_ranges(self.cfg, self.spec, centre, covmat)
+        except MarginalsError as e:
+            self.host.fail("%s", str(e), cause=e)
+        self._configure(ranges)
+
+    def _configure(self, ranges):
+        cfg, fail, ix = self.cfg, self.host.fail, self.spec.sampled.index
+        cfg["resolved"] = dict(ranges)
+        lo, hi = np.full(self.spec.d, np.nan), np.full(self.spec.d, np.nan)
+        for n, (a, b) in cfg["resolved"].items():
+            lo[ix(n)], hi[ix(n)] = a, b
+        try:
+            self.engine.configure_marginals([ix(n) for n in cfg["params"]], cfg["bins"],
+                                            [(ix(a), ix(b)) for a, b in cfg["pairs"]], cfg["bins2d"], lo, hi)
+        except EngineError as e:
+            fail("marginals: %s", str(e), cause=e)
+        cfg["n_counters"] = slab_size(len(cfg["params"]), cfg["bins"], len(cfg["pairs"]), cfg["bins2d"])
+        if hasattr(self.engine, "marginals_layout"):
+            # the engine's slab is the authority: the product must read it the way it is written
+            lay = self.engine.marginals_layout()
+            if (lay["n_counters"], lay["offset_pairs"]) != (
+                    cfg["n_counters"], slab_size(len(cfg["params"]), cfg["bins"], 0, 0)):
+                fail("marginals: the engine lays its counters out differently (%r) from the "
+                     "product (%d counters)", lay, cfg["n_counters"])
+        self.open = (np.zeros(cfg["n_counters"], np.uint64), 0)
+
+    def fetch_requested(self):
+        if self.fetched is None:
+            self.fetched = self.engine.fetch_marginals()
+
+    def _drain(self, pending):
+        """Move what the device holds of the unfinished interval into `open`."""
+        if pending:
+            self.fetch_requested()
+        self.engine.request_marginals()
+        c, n = self.engine.fetch_marginals()
+        self.open = (self.open[0] + c, self.open[1] + n)
+
+    def file(self, n_snap):
+        """The interval's counts: what the request read out plus what the host held of it."""
+        counts = self.open[0] + (self.fetched[0] if self.fetched is not None else 0)
+        self.fetched = None
+        self.open = (np.zeros_like(counts), 0)
+        if n_snap:
+            self.ivs.append(counts)
+
+    def drop(self, k):
+        self.ivs = self.ivs[k:]
+
+    def product(self, intervals, combined=False, pending=False):
+        cfg = self.cfg
+        if self.engine is not None:
+            self._drain(pending)
+        slab, n_acc = self.open[0].copy(), int(self.open[1])
+        if self.fetched is not None:   # (requested, not filed yet: the newest interval)
+            slab += self.fetched[0]
+            n_acc += int(self.fetched[1])
+        for (n_snap, _, _), c in zip(intervals, self.ivs):
+            slab += c
+            n_acc += int(n_snap)
+        n_samples = n_acc * int(self.host.n_walkers)
+        if combined and self.host.size > 1:
+            # ONE host all-reduce of integers (exact in float64 below 2^53), here and not in the loop
+            buf = np.concatenate((slab.astype(np.float64), [float(n_samples)]))
+            if buf.max() >= 2.0 ** 53:
+                self.host.fail("marginals: a count above 2^53 cannot be summed over processes exactly")
+            self.host.all_reduce_sum(buf)
+            slab, n_samples = buf[:-1].astype(np.uint64), int(buf[-1])
+        return Marginals(cfg["params"], cfg["pairs"], cfg["bins"], cfg["bins2d"], cfg["resolved"],
+                         slab, n_acc, n_samples)
+
+    def save(self, pending):
+        """What a resumed run must repeat (names, bins and ranges) and the counts it goes on from."""
+        cfg = self.cfg
+        self._drain(pending)
+        names = list(cfg["resolved"])
+        return {"marg_params": np.array(cfg["params"], dtype=str),
+                "marg_pairs": np.array(cfg["pairs"], dtype=str).reshape(-1, 2),
+                "marg_bins": np.array([cfg["bins"], cfg["bins2d"]], dtype=np.int64),
+                "marg_range_names": np.array(names, dtype=str),
+                "marg_ranges": np.array([cfg["resolved"][n] for n in names], dtype=np.float64).reshape(-1, 2),
+                "marg_iv": np.array(self.ivs, dtype=np.uint64).reshape(len(self.ivs), cfg["n_counters"]),
+                "marg_open": self.open[0], "marg_open_n": np.int64(self.open[1])}
+
+    def load(self, z, n_intervals):
+        """Resume: the ranges are part of the geometry -- the saved ones are taken where the option
+        derives them from the run's start (`covmat`) and must be repeated where it states them."""
+        cfg, fail = self.cfg, self.host.fail
+        if "marg_iv" not in z:
+            fail("marginals: cannot resume -- the run was written without marginals (the window "
+                 "of a histogram cannot begin in mid-run)")
+        saved = {str(n): (float(r[0]), float(r[1])) for n, r in zip(z["marg_range_names"], z["marg_ranges"])}
+        same = ([str(p) for p in z["marg_params"]] == cfg["params"]
+                and [(str(a), str(b)) for a, b in z["marg_pairs"]] == cfg["pairs"]
+                and [int(v) for v in z["marg_bins"]] == [cfg["bins"], cfg["bins2d"]])
+        if same and cfg["ranges"] != "covmat":
+            try:
+                same = resolve_ranges(cfg, self.spec) == saved
+            except MarginalsError as e:
+                fail("%s", str(e), cause=e)
+        elif same:
+            explicit = cfg["ranges"] if isinstance(cfg["ranges"], dict) else {}
+            same = all(saved.get(n) == r for n, r in explicit.items() if n in saved)
+        if not same:
+            fail("marginals: cannot resume -- the run was written with other parameters, pairs, "
+                 "bins or ranges (the counts of different bins do not add up); saved ranges: %r", saved)
+        self._configure(saved)
+        self.ivs = [np.array(c, dtype=np.uint64) for c in z["marg_iv"]]
+        if len(self.ivs) != n_intervals:
+            fail("marginals: the state file holds %d interval histograms for %d intervals",
+                 len(self.ivs), n_intervals)
+        # the unfinished interval goes back to the device, where the next accumulation adds to it
+        self.engine.marginals_set(z["marg_open"], int(z["marg_open_n"]))
+
+    def detach(self, pending=False):
+        if self.engine is not None and self.open is not None:
+            self._drain(pending)     # (the device's part of the unfinished interval)
+        self.engine = self.accumulate = self.request = None

@@ -28,19 +28,30 @@ import logging
 import math
 import os
 import re
+from functools import partial
+from types import SimpleNamespace
 
 import numpy as np
 import pandas as pd
 
 from . import dist
-from . import autocorr as autocorr_mod
-from . import marginals as marginals_mod
+from .autocorr import AutoCorrAccumulator
+from .bounds_ring import BoundsRing
 from .collection import SampleCollection
 from .engine import (ChainStuck, Engine, EngineError, NotPositiveDefinite, gelman_rubin,
                      incremental_supported)
+from .marginals import MarginalsAccumulator
 from .model import ProblemSpec, UnsupportedModel
 
 log = logging.getLogger("mcmc_hip")
+
+
+def log_and_raise(error, logger, msg, *args, cause=None):
+    """Log, then raise `error`: a LoggedError of the host (log.py:22-46)."""
+    err = error(logger, msg, *args)
+    if cause is not None:
+        raise err from cause
+    raise err
 
 
 class LoggedError(Exception):
@@ -227,10 +238,11 @@ class EnsembleMCMC:
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
     MAX_DIM = 128    # ctx.h: kMaxDimBig, every path (mixtures: at most 64 modes, model.py)
     HUGE_MAX_MODES = 4   # 128 < d <= max_dim(): huge_kernels.hip (huge_args.h: kHugeMaxModes)
-    marginals = None     # (the option's default: off)
-    _marg = _marg_fetched = None   # the parsed option (None: off); a read-out fetched ahead
-    autocorr = None      # (the option's default: off)
-    _ac = _ac_fetched = _ac_open = None   # as `_marg`; the open sums as last read (kept past close)
+    marginals = autocorr = None     # (the options' default: off)
+    # What is accumulated on the device beside every moment snapshot (marginals.py states the
+    # methods): a new product is one such class, appended here.  `_products`: those that are on
+    PRODUCT_CLASSES = (MarginalsAccumulator, AutoCorrAccumulator)
+    _products = ()
 
     def _max_dim(self):
         """The cap of the engine behind the seam: its max_dim() where it has one, else 128 (the
@@ -240,11 +252,7 @@ class EnsembleMCMC:
 
     # ------------------------------------------------------------------ host seams
     def _fail(self, msg, *args, cause=None):
-        """Log, then raise the host's LoggedError (log.py:22-46)."""
-        err = self._LoggedError(self.log, msg, *args)
-        if cause is not None:
-            raise err from cause
-        raise err
+        log_and_raise(self._LoggedError, self.log, msg, *args, cause=cause)
 
     def _out_parts(self):
         """(folder, file prefix) of the output, or None: from a `cobaya.output.Output`
@@ -446,8 +454,15 @@ class EnsembleMCMC:
         if int(self.basis_group_size) != int(self.group_size) and not self.incremental:
             self._fail("basis_group_size (%s) differs from group_size (%s): this needs "
                        "incremental evaluation", self.basis_group_size, self.group_size)
-        self._check_marginals(spec)
-        self._check_autocorr(spec)
+        # the device products: parsed and refused by their option's name BEFORE the engine is created
+        # (they must not hold the sampler, not even through `self._fail`: an engine that nobody
+        # closed is freed with the sampler's last reference, not by the cycle collector)
+        host = SimpleNamespace(fail=partial(log_and_raise, self._LoggedError, self.log), n_walkers=W,
+                               size=self.size, all_reduce_sum=dist.all_reduce_sum, temperature=self.temperature,
+                               snapshot_steps=int(self.steps_per_launch) * max(1, int(self.moments_every)))
+        made = [c.from_option(getattr(self, c.name), spec, self._engine_factory, host)
+                for c in self.PRODUCT_CLASSES]
+        self._products = [p for p in made if p is not None]
         try:
             self.engine = self._engine_factory(d, W, group_size=int(self.group_size), device=int(device),
                                  seed=self.seed, walker_offset=self.rank * W,
@@ -498,8 +513,7 @@ class EnsembleMCMC:
         self._last_state_dump = 0.0
         if self._is_resuming() and self.output and os.path.exists(self._state_file()):
             self._init_bookkeeping()
-            self._init_bounds_ring()
-            self._init_autocorr()
+            self._attach_products(resumed=True)
             self._load_checkpoint()
             self._init_device_checkpoint()
             return
@@ -530,242 +544,17 @@ class EnsembleMCMC:
         self._shift = shift[:d] / shift[d]
         self.engine.set_moment_shift(self._shift)
         self._init_bookkeeping()
-        self._init_bounds_ring()
-        self._init_marginals(centre=self._shift, covmat=self._initial_covmat)
-        self._init_autocorr()
+        self._attach_products(centre=self._shift, covmat=self._initial_covmat)
         self._init_device_checkpoint()
 
-    # ------------------------------------------------------------------ marginals
-    def _check_marginals(self, spec):
-        """The `marginals` option, parsed and refused by its name BEFORE the engine is created."""
-        self._marg = None
-        try:
-            cfg = marginals_mod.parse_option(self.marginals, spec.sampled)
-        except marginals_mod.MarginalsError as e:
-            self._fail("%s", str(e), cause=e)
-        if cfg is None:
-            return
-        if self.temperature != 1:
-            self._fail("marginals: the histograms count the walkers as they are, which at "
-                       "temperature %g follow the tempered law, not the posterior; use temperature: 1 "
-                       "or turn marginals off", self.temperature)
-        if not all(hasattr(self._engine_factory, m) for m in
-                   ("configure_marginals", "accumulate_marginals", "request_marginals",
-                    "fetch_marginals", "marginals_set")):
-            self._fail("marginals: this engine has no marginal histograms (its library predates "
-                       "mcmc_hip_marginals_*)")
-        self._marg = cfg
-
-    def _init_marginals(self, centre=None, covmat=None, ranges=None):
-        """Fix the ranges (given: those of the state file) and hand the layout to the engine."""
-        cfg = self._marg
-        if cfg is None:
-            return
-        spec = self.spec
-        try:
-            cfg["resolved"] = dict(ranges) if ranges is not None else marginals_mod.resolve_ranges(
-                cfg, spec, centre, covmat)
-        except marginals_mod.MarginalsError as e:
-            self._fail("%s", str(e), cause=e)
-        lo, hi = np.full(spec.d, np.nan), np.full(spec.d, np.nan)
-        for n, (a, b) in cfg["resolved"].items():
-            lo[spec.sampled.index(n)], hi[spec.sampled.index(n)] = a, b
-        try:
-            self.engine.configure_marginals(
-                [spec.sampled.index(n) for n in cfg["params"]], cfg["bins"],
-                [(spec.sampled.index(a), spec.sampled.index(b)) for a, b in cfg["pairs"]],
-                cfg["bins2d"], lo, hi)
-        except EngineError as e:
-            self._fail("marginals: %s", str(e), cause=e)
-        cfg["n_counters"] = marginals_mod.slab_size(len(cfg["params"]), cfg["bins"],
-                                                    len(cfg["pairs"]), cfg["bins2d"])
-        if hasattr(self.engine, "marginals_layout"):
-            # the engine's slab is the authority: the product must read it the way it is written
-            lay = self.engine.marginals_layout()
-            if (lay["n_counters"], lay["offset_pairs"]) != (
-                    cfg["n_counters"], marginals_mod.slab_size(len(cfg["params"]), cfg["bins"], 0, 0)):
-                self._fail("marginals: the engine lays its counters out differently (%r) from the "
-                           "product (%d counters)", lay, cfg["n_counters"])
-        self._marg_open = (np.zeros(cfg["n_counters"], np.uint64), 0)
-
-    def _marginals_geometry(self):
-        """What a resumed run must repeat: names, bins and ranges, as arrays for the state file."""
-        cfg = self._marg
-        names = list(cfg["resolved"])
-        return {"marg_params": np.array(cfg["params"], dtype=str),
-                "marg_pairs": np.array(cfg["pairs"], dtype=str).reshape(-1, 2),
-                "marg_bins": np.array([cfg["bins"], cfg["bins2d"]], dtype=np.int64),
-                "marg_range_names": np.array(names, dtype=str),
-                "marg_ranges": np.array([cfg["resolved"][n] for n in names], dtype=np.float64).reshape(-1, 2)}
-
-    def _marginals_drain(self):
-        """Move what the device holds of the unfinished interval into the host's copy of it
-        (`_marg_open`); a read-out still pending from a checkpoint request is fetched first and
-        kept for `_finish_checkpoint`.  Integers: where the counts are held changes no sum."""
-        eng = self.engine
-        if self._ckpt_pending and self._marg_fetched is None:
-            self._marg_fetched = eng.fetch_marginals()
-        eng.request_marginals()
-        c, n = eng.fetch_marginals()
-        self._marg_open = (self._marg_open[0] + c, self._marg_open[1] + n)
-
-    def _marginals_product(self, combined=False):
-        """Sum over the intervals of the window plus the unfinished interval -> `Marginals`."""
-        cfg = self._marg
-        if self.engine is not None:
-            self._marginals_drain()
-        slab, n_acc = self._marg_open[0].copy(), int(self._marg_open[1])
-        if self._marg_fetched is not None:   # (requested, not filed yet: the newest interval)
-            slab += self._marg_fetched[0]
-            n_acc += int(self._marg_fetched[1])
-        ivs = self._intervals
-        for (n_snap, _, _), c in zip(ivs, self._marg_ivs):
-            slab += c
-            n_acc += int(n_snap)
-        n_samples = n_acc * int(self.n_walkers)
-        if combined and self.size > 1:
-            # ONE host all-reduce of integers (exact in float64 below 2^53), here and not in the loop
-            buf = np.concatenate((slab.astype(np.float64), [float(n_samples)]))
-            if buf.max() >= 2.0 ** 53:
-                self._fail("marginals: a count above 2^53 cannot be summed over processes exactly")
-            dist.all_reduce_sum(buf)
-            slab, n_samples = buf[:-1].astype(np.uint64), int(buf[-1])
-        return marginals_mod.Marginals(cfg["params"], cfg["pairs"], cfg["bins"], cfg["bins2d"],
-                                       cfg["resolved"], slab, n_acc, n_samples)
-
-    # ------------------------------------------------------------------ autocorrelation
-    _AC_METHODS = ("configure_autocorr", "accumulate_autocorr", "request_autocorr", "fetch_autocorr",
-                   "autocorr_set", "autocorr_reset", "autocorr_layout")
-
-    def _check_autocorr(self, spec):
-        """The `autocorr` option, parsed and refused by its name BEFORE the engine is created."""
-        self._ac = None
-        try:
-            cfg = autocorr_mod.parse_option(self.autocorr, spec.sampled)
-        except autocorr_mod.AutoCorrError as e:
-            self._fail("%s", str(e), cause=e)
-        if cfg is None:
-            return
-        if not all(hasattr(self._engine_factory, m) for m in self._AC_METHODS):
-            self._fail("autocorr: this engine has no lagged cross-products (its library predates "
-                       "mcmc_hip_autocorr_*)")
-        # one lag: the steps between two moment snapshots, fixed for the run
-        cfg["interval_steps"] = int(self.steps_per_launch) * max(1, int(self.moments_every))
-        self._ac = cfg
-
-    def _init_autocorr(self):
-        """Hand the configuration to the engine (which allocates the ring, or refuses it)."""
-        cfg = self._ac
-        if cfg is None:
-            return
-        try:
-            self.engine.configure_autocorr([self.spec.sampled.index(n) for n in cfg["params"]],
-                                           cfg["lags"])
-        except EngineError as e:
-            self._fail("autocorr: %s", str(e), cause=e)
-        lay = self.engine.autocorr_layout()
-        if (lay["n_dims"], lay["lags"]) != (len(cfg["params"]), cfg["lags"]):
-            self._fail("autocorr: the engine lays its sums out differently (%r) from the product", lay)
-        self._ac_open = self._autocorr_zero()
-
-    def _autocorr_zero(self):
-        cfg = self._ac
-        return (np.zeros((3, cfg["lags"] + 1, len(cfg["params"]))), np.zeros(cfg["lags"] + 1, np.int64))
-
-    def _autocorr_peek(self):
-        """The sums of the unfinished interval, read WITHOUT disturbing them: read out (which zeroes
-        them in stream order) and set back to the same values, so that the device goes on adding
-        to exactly the numbers it held.  A read-out still pending from a checkpoint request is
-        fetched first and kept for `_finish_checkpoint`."""
-        eng = self.engine
-        if eng is None:
-            return self._ac_open
-        if self._ckpt_pending and self._ac_fetched is None:
-            self._ac_fetched = eng.fetch_autocorr()
-        eng.request_autocorr()
-        sums, n_pairs = eng.fetch_autocorr()
-        eng.autocorr_set(sums, n_pairs)
-        self._ac_open = (sums, n_pairs)
-        return self._ac_open
-
-    def _autocorr_product(self, combined=False):
-        """Sum over the intervals of the window, in their order, plus the unfinished interval ->
-        `AutoCorr`."""
-        cfg = self._ac
-        sums, n_pairs = self._autocorr_zero()
-        parts = list(self._ac_ivs)
-        if self._ac_fetched is not None:   # (requested, not filed yet: the newest interval)
-            parts.append(self._ac_fetched)
-        parts.append(self._autocorr_peek())
-        for s_, n_ in parts:
-            sums = sums + s_
-            n_pairs = n_pairs + n_
-        n_walkers = int(self.n_walkers)
-        if combined and self.size > 1:
-            # ONE host all-reduce, here and not in the loop; every process has accumulated the same
-            # snapshots, so the pair counts must agree
-            buf = np.concatenate((sums.reshape(-1), n_pairs.astype(np.float64), [float(n_walkers)]))
-            dist.all_reduce_sum(buf)
-            L1 = cfg["lags"] + 1
-            if not np.array_equal(buf[-1 - L1:-1], n_pairs.astype(np.float64) * self.size):
-                self._fail("autocorr: the processes hold different pair counts (this one %r, the sum "
-                           "over %d processes %r)", n_pairs.tolist(), self.size, buf[-1 - L1:-1].tolist())
-            sums, n_walkers = buf[:-1 - L1].reshape(sums.shape), int(buf[-1])
-        return autocorr_mod.AutoCorr(cfg["params"], cfg["lags"], cfg["interval_steps"], n_walkers,
-                                     sums, n_pairs)
-
-    def _load_autocorr(self, z):
-        """Resume: the configuration must be the one the sums were formed with; the sums of the
-        window's intervals and of the unfinished one come back, the ring does not (it refills: the
-        pairs that bridge the resume point are missing)."""
-        cfg = self._ac
-        if "ac_iv" not in z:
-            self._fail("autocorr: cannot resume -- the run was written without autocorr (the window "
-                       "of its sums cannot begin in mid-run)")
-        saved = ([str(p) for p in z["ac_params"]], int(z["ac_geometry"][0]), int(z["ac_geometry"][1]))
-        if saved != (cfg["params"], cfg["lags"], cfg["interval_steps"]):
-            self._fail("autocorr: cannot resume -- the run was written with params %r, lags %d and %d "
-                       "steps per lag, and now has %r, %d and %d (sums of different lags do not add "
-                       "up)", *saved, cfg["params"], cfg["lags"], cfg["interval_steps"])
-        self._ac_ivs = [(np.array(s_, dtype=np.float64), np.array(n_, dtype=np.int64))
-                        for s_, n_ in zip(z["ac_iv"], z["ac_iv_pairs"])]
-        if len(self._ac_ivs) != len(self._intervals):
-            self._fail("autocorr: the state file holds %d interval sums for %d intervals",
-                       len(self._ac_ivs), len(self._intervals))
-        # the unfinished interval goes back to the device, where the next accumulation adds to it
-        self.engine.autocorr_set(z["ac_open"], z["ac_open_pairs"])
-        self._ac_open = (np.array(z["ac_open"], dtype=np.float64), np.array(z["ac_open_pairs"], dtype=np.int64))
-
-    def _init_bounds_ring(self):
-        """`bounds_snapshots` ensemble snapshots on the device (mcmc_hip_bounds_configure)."""
-        n = int(self.bounds_snapshots or 0)
-        if n < 0:
-            self._fail("bounds_snapshots must be >= 0, got %r", self.bounds_snapshots)
-        if n and hasattr(self.engine, "bounds_configure"):
-            n = min(n, getattr(self.engine, "BOUNDS_MAX_SLOTS", 64), 16384 // int(self.group_size))
-            self.engine.bounds_configure(n)
-            self._bslots = [-1] * n
-
-    def _bounds_take(self):
-        """Called with every moment snapshot (index i): the ring keeps every `stride`-th one of
-        the later half of the run -- the window of mcmc.py:787-790, `use_first = n / 2`.  A slot
-        is free once its snapshot has left that window; when none is, the record is thinned
-        (stride doubled, every other kept snapshot dropped)."""
-        i = self._bsnap_idx
-        self._bsnap_idx += 1
-        if not self._bslots or i % self._bstride:
-            return
-        start = (i + 1) / 2.0
-        free = [k for k, j in enumerate(self._bslots) if j < start]
-        if not free:
-            self._bstride *= 2
-            self._bslots = [j if j % self._bstride == 0 else -1 for j in self._bslots]
-            if i % self._bstride:
-                return
-            free = [k for k, j in enumerate(self._bslots) if j < 0]
-        k = min(free, key=lambda k_: self._bslots[k_])
-        self._bslots[k] = i
-        self.engine.bounds_snapshot(k)
+    def _attach_products(self, **kw):
+        """The bounds ring and the device products, configured on the engine."""
+        self._bounds = BoundsRing.from_option(
+            self.bounds_snapshots, self.engine, int(self.group_size), self._fail,
+            (int(self.n_walkers), self.spec.d),
+            [self._chain_file(f) for f in BoundsRing.FILES] if self.output else None)
+        for p in self._products:
+            p.attach(self.engine, **kw)
 
     def _check_huge(self, spec, d):
         """128 < d <= 256 (huge_kernels.hip) serves incremental evaluation of one parameter block
@@ -939,12 +728,6 @@ class EnsembleMCMC:
         self._carried = None     # table rows of earlier legs, read back at resume
         self._intervals = []     # per checkpoint: (n_snapshots, group_sum[G,d], pooled_S[d,d])
         self._iv0 = 0            # absolute index of _intervals[0] (intervals dropped so far)
-        # marginals: the counts of every interval of `_intervals` (same index), the host's part of
-        # the unfinished interval (counts, accumulations), a read-out fetched ahead of its checkpoint
-        self._marg_ivs, self._marg_open, self._marg_fetched = [], None, None
-        # autocorr: the (sums, n_pairs) of every interval of `_intervals` (same index), a read-out
-        # fetched ahead of its checkpoint
-        self._ac_ivs, self._ac_fetched = [], None
         self._wsums = WindowSums()
         self._dropped_snapshots = 0
         self._progress_rows = {}  # i_learn -> row dict (DataFrame built on demand: `progress`)
@@ -963,9 +746,6 @@ class EnsembleMCMC:
         self._ckpt_on_device = False   # the pending checkpoint was solved on the device
         self._snaps_in_interval = 0    # moment snapshots since the last checkpoint request
         self._ckpt_steps_last = 0      # steps per walker at the last request
-        # the device ring behind R-1 of the bounds: slot -> index of the moment snapshot it holds
-        # (-1: free), the stride of the thinned record, moment snapshots taken so far
-        self._bslots, self._bstride, self._bsnap_idx = [], 1, 0
 
     # ------------------------------------------------------------------ a17
     def initial_proposal_covmat(self):
@@ -1084,25 +864,15 @@ class EnsembleMCMC:
         self.log.info("Sampling complete after %d accepted steps.", self._accepted_total)
         if self.output:
             self.write_checkpoint(force_state=True)
-        if self.output and self._marg:
-            m = self._marginals_product(combined=True)   # (collective: every process calls it)
-            if self.rank == 0:
-                m.save(self._out_file(".marginals.npz"))
-        if self._ac:
-            ac = self._autocorr_product(combined=True)   # (collective: every process calls it)
+        for p in self._products:
+            if not self.output and not p.reports:   # (nothing to write, nothing to say)
+                continue
+            # (collective: every process calls it)
+            out = p.product(self._intervals, combined=True, pending=self._ckpt_pending)
             if self.output and self.rank == 0:
-                ac.save(self._out_file(".autocorr.npz"))
-            worst = ac.worst()
-            if worst is None:
-                self.log.info("Autocorrelation: no lag beyond 0 was accumulated.")
-            elif worst[2]:
-                self.log.info("Autocorrelation: largest tau = %.4g steps (%s); a snapshot every %d "
-                              "steps decorrelates the rows.", worst[1] * ac.interval_steps, worst[0],
-                              ac.thin()[1])
-            else:
-                self.log.info("Autocorrelation: the window was not reached within %d lags of %d steps "
-                              "(%s: tau > %.4g steps); raise lags or moments_every.", ac.lags,
-                              ac.interval_steps, worst[0], worst[1] * ac.interval_steps)
+                out.save(self._out_file("." + p.name + ".npz"))
+            if p.reports:
+                self.log.info("%s", out.summary())
 
     def advance(self):
         """One pass of the hot loop (the body of mcmc.py:451-528 for every walker): a fused
@@ -1140,12 +910,10 @@ class EnsembleMCMC:
                 self._finish_checkpoint()
         if self._launches % max(1, int(self.moments_every)) == 0:
             eng.accumulate_moments()
-            if self._marg:
-                eng.accumulate_marginals()
-            if self._ac:
-                eng.accumulate_autocorr()
+            for p in self._products:
+                p.accumulate()
             self._snaps_in_interval += 1
-            self._bounds_take()
+            self._bounds.take()
         snap_every = int(self.snapshot_every) if self.snapshot_every else None
         if self.emit == "chains":
             if hasattr(eng, "drain_samples_view"):
@@ -1173,10 +941,8 @@ class EnsembleMCMC:
             return
         if hasattr(self.engine, "request_moments"):
             self.engine.request_moments()
-        if self._marg:
-            self.engine.request_marginals()
-        if self._ac:
-            self.engine.request_autocorr()
+        for p in self._products:
+            p.request()
         self._ckpt_on_device = False
         if self._device_ckpt and self._snaps_in_interval > 0:
             self._begin_device_checkpoint()
@@ -1222,10 +988,8 @@ class EnsembleMCMC:
         self._ckpt_pending = False
         moments = (self.engine.fetch_moments() if hasattr(self.engine, "fetch_moments")
                    else None)
-        if self._marg and self._marg_fetched is None:
-            self._marg_fetched = self.engine.fetch_marginals()
-        if self._ac and self._ac_fetched is None:
-            self._ac_fetched = self.engine.fetch_autocorr()
+        for p in self._products:
+            p.fetch_requested()
         dev = payload = None
         if self._ckpt_on_device and self._ckpt_solve_on_device:
             dev = self.engine.checkpoint_fetch()
@@ -1259,8 +1023,6 @@ class EnsembleMCMC:
     # ------------------------------------------------------------------ checkpoint / resume
     def _state_file(self):
         return self._chain_file("state.npz")
-
-    BOUNDS_RING_SAVE_BYTES = 1 << 26   # snapshots of the bounds ring kept in the state file
 
     # the options whose change re-opens a converged run (mcmc.py:1080-1088)
     CONVERGE_OPTIONS = ("Rminus1_stop", "Rminus1_cl_stop", "Rminus1_cl_level", "max_samples")
@@ -1303,33 +1065,9 @@ class EnsembleMCMC:
             acc_n, acc_gs, acc_S = self.engine.read_moments(reset=False)
             st.update(acc_n=np.int64(acc_n), acc_gs=acc_gs, acc_S=acc_S)
             ivs = self._intervals
-            if self._marg:
-                self._marginals_drain()
-                st.update(self._marginals_geometry())
-                st["marg_iv"] = np.array(self._marg_ivs, dtype=np.uint64).reshape(
-                    len(self._marg_ivs), self._marg["n_counters"])
-                st["marg_open"] = self._marg_open[0]
-                st["marg_open_n"] = np.int64(self._marg_open[1])
-            if self._ac:
-                open_s, open_n = self._autocorr_peek()
-                L1, n_par = self._ac["lags"] + 1, len(self._ac["params"])
-                st["ac_params"] = np.array(self._ac["params"], dtype=str)
-                st["ac_geometry"] = np.array([self._ac["lags"], self._ac["interval_steps"]], dtype=np.int64)
-                st["ac_iv"] = np.array([s_ for s_, _ in self._ac_ivs], dtype=np.float64).reshape(
-                    len(self._ac_ivs), 3, L1, n_par)
-                st["ac_iv_pairs"] = np.array([n_ for _, n_ in self._ac_ivs], dtype=np.int64).reshape(
-                    len(self._ac_ivs), L1)
-                st["ac_open"], st["ac_open_pairs"] = open_s, open_n
-            # the bounds ring: its books always, its snapshots while they are small (a resumed run
-            # then forms the same Rminus1_cl; a large ring restarts empty)
-            held = [k for k, j in enumerate(self._bslots) if j >= 0]
-            ring_bytes = 8 * len(held) * int(self.n_walkers) * self.spec.d
-            if held and ring_bytes <= self.BOUNDS_RING_SAVE_BYTES:
-                st["bring"] = np.array([self.engine.bounds_get_slot(k) for k in held])
-            elif held:
-                self._save_bounds_sidecar()
-            st["bslots"] = np.array(self._bslots, dtype=np.int64)
-            st["bbook"] = np.array([self._bstride, self._bsnap_idx], dtype=np.int64)
+            for p in self._products:
+                st.update(p.save(self._ckpt_pending))
+            st.update(self._bounds.save())
             tmp = self._state_file() + ".tmp.npz"
             np.savez(tmp, **st,
                      proposal_cov=self.engine.get_proposal_cov(), shift=self._shift,
@@ -1347,68 +1085,6 @@ class EnsembleMCMC:
                                     + [float(getattr(self, k)) for k in self.CONVERGE_OPTIONS]),
                      progress=self.progress.to_numpy(dtype=object).astype(str))
             os.replace(tmp, self._state_file())   # never leave a half-written state behind
-
-    def _bounds_sidecar(self):
-        return self._chain_file("bounds.npy"), self._chain_file("bounds_tags.npy")
-
-    def _save_bounds_sidecar(self):
-        """A bounds ring too large for the state file (251 MB at BASELINE config 2: 16 slots of
-        65 536 x 30 doubles) lives in a sidecar `prefix.<n>.bounds.npy` of fixed shape
-        [slots][W][d], written IN PLACE and only where a slot's snapshot changed since the last
-        dump; `prefix.<n>.bounds_tags.npy` (replaced atomically, after the data) says which
-        snapshot each slot of the file holds.  A resumed run restores exactly the slots whose tag
-        equals the state file's book -- after a crash between the two writes a slot is dropped,
-        never mixed up -- so Rminus1_cl after a resume is the uninterrupted run's."""
-        data_f, tags_f = self._bounds_sidecar()
-        n, shape = len(self._bslots), (len(self._bslots), int(self.n_walkers), self.spec.d)
-        tags = np.full(n, -1, dtype=np.int64)
-        mm = None
-        if os.path.exists(data_f) and os.path.exists(tags_f):
-            try:
-                mm = np.load(data_f, mmap_mode="r+")
-                old = np.load(tags_f)
-                if mm.shape == shape and old.shape == tags.shape:
-                    tags = old
-                else:
-                    mm = None
-            except Exception:
-                mm = None
-        if mm is None:
-            mm = np.lib.format.open_memmap(data_f, mode="w+", dtype=np.float64, shape=shape)
-            tags[:] = -1
-        dirty = [k for k, j in enumerate(self._bslots) if j >= 0 and tags[k] != j]
-        if dirty:   # (the tags of the slots being rewritten are invalid until the data is down)
-            tags[dirty] = -1
-            np.save(tags_f + ".tmp.npy", tags)
-            os.replace(tags_f + ".tmp.npy", tags_f)
-            for k in dirty:
-                mm[k] = self.engine.bounds_get_slot(k)
-            mm.flush()
-        for k, j in enumerate(self._bslots):
-            tags[k] = j if j >= 0 else -1
-        del mm
-        np.save(tags_f + ".tmp.npy", tags)
-        os.replace(tags_f + ".tmp.npy", tags_f)
-
-    def _load_bounds_sidecar(self, saved):
-        """-> the slot books after restoring what the sidecar vouches for (see above)."""
-        data_f, tags_f = self._bounds_sidecar()
-        out = [-1] * len(saved)
-        if not (os.path.exists(data_f) and os.path.exists(tags_f)):
-            return out, 0
-        try:
-            mm, tags = np.load(data_f, mmap_mode="r"), np.load(tags_f)
-        except Exception:
-            return out, 0
-        if mm.shape != (len(saved), int(self.n_walkers), self.spec.d) or len(tags) != len(saved):
-            return out, 0
-        n = 0
-        for k, j in enumerate(saved):
-            if j >= 0 and int(tags[k]) == j:
-                self.engine.bounds_set_slot(k, np.array(mm[k]))
-                out[k] = j
-                n += 1
-        return out, n
 
     def _load_checkpoint(self):
         """Resume (sampler.py:291-310, mcmc.py:131-139, 189-214): same number of processes and
@@ -1439,29 +1115,11 @@ class EnsembleMCMC:
         if "acc_n" in z:   # snapshots accumulated on the device since the last read-out
             self.engine.set_moments(int(z["acc_n"]), z["acc_gs"], z["acc_S"])
             self._snaps_in_interval = int(z["acc_n"])   # (snapshots since the last request)
-        if "bbook" in z and self._bslots:
-            self._bstride, self._bsnap_idx = (int(v) for v in z["bbook"])
-            saved = [int(j) for j in z["bslots"]]
-            held = [k for k, j in enumerate(saved) if j >= 0]
-            if "bring" in z and len(saved) == len(self._bslots):
-                self._bslots = saved
-                for k, x in zip(held, z["bring"]):
-                    self.engine.bounds_set_slot(k, x)
-            elif held and len(saved) == len(self._bslots):
-                self._bslots, n_back = self._load_bounds_sidecar(saved)
-                if n_back < len(held):
-                    self.log.info("%d of the %d snapshots behind R-1 of the bounds were not found "
-                                  "beside the state file: those slots restart empty.",
-                                  len(held) - n_back, len(held))
-            elif held:
-                self.log.info("bounds_snapshots changed since the checkpoint: the ring behind R-1 "
-                              "of the bounds restarts empty.")
+        self._bounds.load(z, self.log)
         self._intervals = [(int(n), gs, S) for n, gs, S in zip(z["iv_n"], z["iv_gs"], z["iv_S"])]
         self._iv0 = int(z["iv0"]) if "iv0" in z else 0
-        if self._marg:
-            self._load_marginals(z)
-        if self._ac:
-            self._load_autocorr(z)
+        for p in self._products:
+            p.load(z, len(self._intervals))
         self._wsums = WindowSums()
         (self.n_steps_raw, self.i_learn, self._acc_last, self._steps_last, self._launches,
          self._dropped_snapshots, self._accepted_total) = (int(v) for v in book[:7])
@@ -1489,38 +1147,6 @@ class EnsembleMCMC:
         self._load_chain_file(txt_rows)
         self.log.info("Resumed from %s at %d steps per walker (%d stored rows).",
                       self._state_file(), self.n_steps_raw, self._txt_rows)
-
-    def _load_marginals(self, z):
-        """Resume: the ranges are part of the geometry -- the saved ones are taken where the option
-        derives them from the run's start (`covmat`) and must be repeated where it states them."""
-        cfg = self._marg
-        if "marg_iv" not in z:
-            self._fail("marginals: cannot resume -- the run was written without marginals (the window "
-                       "of a histogram cannot begin in mid-run)")
-        saved = {str(n): (float(r[0]), float(r[1]))
-                 for n, r in zip(z["marg_range_names"], z["marg_ranges"])}
-        same = ([str(p) for p in z["marg_params"]] == cfg["params"]
-                and [(str(a), str(b)) for a, b in z["marg_pairs"]] == cfg["pairs"]
-                and [int(v) for v in z["marg_bins"]] == [cfg["bins"], cfg["bins2d"]])
-        if same and cfg["ranges"] != "covmat":
-            try:
-                same = marginals_mod.resolve_ranges(cfg, self.spec) == saved
-            except marginals_mod.MarginalsError as e:
-                self._fail("%s", str(e), cause=e)
-        elif same:
-            explicit = cfg["ranges"] if isinstance(cfg["ranges"], dict) else {}
-            same = all(saved.get(n) == r for n, r in explicit.items() if n in saved)
-        if not same:
-            self._fail("marginals: cannot resume -- the run was written with other parameters, pairs, "
-                       "bins or ranges (the counts of different bins do not add up); saved ranges: %r",
-                       saved)
-        self._init_marginals(ranges=saved)
-        self._marg_ivs = [np.array(c, dtype=np.uint64) for c in z["marg_iv"]]
-        if len(self._marg_ivs) != len(self._intervals):
-            self._fail("marginals: the state file holds %d interval histograms for %d intervals",
-                       len(self._marg_ivs), len(self._intervals))
-        # the unfinished interval goes back to the device, where the next accumulation adds to it
-        self.engine.marginals_set(z["marg_open"], int(z["marg_open_n"]))
 
     def _load_chain_file(self, n_rows):
         """The first `n_rows` rows of this process' chain file become the head of the
@@ -1688,10 +1314,8 @@ class EnsembleMCMC:
             k += 1
         self._dropped_snapshots += sum(counts[:k])
         self._intervals = ivs = ivs[k:]
-        if getattr(self, "_marg", None):
-            self._marg_ivs = self._marg_ivs[k:]
-        if getattr(self, "_ac", None):
-            self._ac_ivs = self._ac_ivs[k:]
+        for p in self._products:
+            p.drop(k)
         self._iv0 += k
         if k:
             self._wsums.forget_below(self._iv0)
@@ -1716,22 +1340,8 @@ class EnsembleMCMC:
             c = eng.counters()
         else:
             n_snap, gs, S, c = moments
-        if getattr(self, "_marg", None):
-            # the interval's counts: what the request read out plus what the host held of it
-            fetched = self._marg_fetched[0] if self._marg_fetched is not None else 0
-            counts = self._marg_open[0] + fetched
-            self._marg_fetched = None
-            self._marg_open = (np.zeros_like(counts), 0)
-            if n_snap:
-                self._marg_ivs.append(counts)
-        if getattr(self, "_ac", None):
-            # the interval's sums: what the request at this checkpoint read out
-            fetched, self._ac_fetched = self._ac_fetched, None
-            if fetched is None:    # (an engine without queued read-outs: read them now)
-                eng.request_autocorr()
-                fetched = eng.fetch_autocorr()
-            if n_snap:
-                self._ac_ivs.append(fetched)
+        for p in self._products:
+            p.file(n_snap)
         if n_snap:
             self._intervals.append((n_snap, gs, S))
         if not self._intervals:
@@ -1798,8 +1408,8 @@ class EnsembleMCMC:
                       self._accepted_total)
         # means criterion twice in a row (mcmc.py:908), then the bounds criterion (918-1002)
         if max(Rminus1, self.Rminus1_last) < self.Rminus1_stop:
-            Rcl = self._rminus1_of_bounds(mean_of_covs) if self._bslots else None
-            if Rcl is None and not self._bslots:
+            Rcl = self._rminus1_of_bounds(mean_of_covs) if self._bounds.slots else None
+            if Rcl is None and not self._bounds.slots:
                 self.log.info("bounds_snapshots: 0 -- no bounds criterion: convergence judged on "
                               "the means only.")
                 self.converged = True
@@ -1849,8 +1459,7 @@ class EnsembleMCMC:
         oracle restates its published `confidence`, oracle/ref_numpy.py).  Returns None when the
         ring holds no snapshot of the window."""
         d, eng = self.spec.d, self.engine
-        start = self._bsnap_idx / 2.0
-        window = sorted((j, k) for k, j in enumerate(self._bslots) if j >= start)
+        window = self._bounds.window()
         if not window:
             return None
         stats = eng.bounds_statistics([k for _, k in window], self.Rminus1_cl_level / 2.0)
@@ -1929,12 +1538,10 @@ class EnsembleMCMC:
         """mcmc.py:1150-1184: {"sample": SampleCollection, "progress": DataFrame}."""
         self.collection = self.samples(combined, skip_samples, to_getdist)
         out = {"sample": self.collection, "progress": self.progress}
-        if getattr(self, "_marg", None):
+        for p in self._products:
             # the window of the covariance and of R-1 (the later half of the run) plus the
-            # unfinished interval, counted from every walker of every moment snapshot
-            out["marginals"] = self._marginals_product(combined)
-        if getattr(self, "_ac", None):
-            out["autocorr"] = self._autocorr_product(combined)
+            # unfinished interval, from every walker of every moment snapshot
+            out[p.name] = p.product(self._intervals, combined, self._ckpt_pending)
         return out
 
     # ------------------------------------------------------------------ reference-style views
@@ -1997,10 +1604,9 @@ class EnsembleMCMC:
 
     def close(self):
         if self.engine is not None:
-            if self._marg and self._marg_open is not None:
-                self._marginals_drain()     # (the device's part of the unfinished interval)
-            if self._ac and self._ac_open is not None:
-                self._autocorr_peek()       # (kept for products() after close)
+            for p in self._products:    # (products() stays valid after close)
+                p.detach(self._ckpt_pending)
+            self._bounds.engine = None
             self._materialise_row_views()   # products()/samples() stay valid after close
             self.engine.close()
             self.engine = None
@@ -2063,7 +1669,9 @@ class MCMCHip(EnsembleMCMC):
             return [], []
         head = re.escape(prefix) + (r"[\._]" if prefix else "")
         chain = re.compile(head + r"\d+\.txt$")
-        rest = re.compile(head + r"(checkpoint|progress|covmat|marginals\.npz|autocorr\.npz|\d+\.(state\.npz|bounds\.npy|bounds_tags\.npy))$")
+        products = "|".join(re.escape(c.name + ".npz") for c in self.PRODUCT_CLASSES)
+        ring = "|".join(re.escape(f) for f in BoundsRing.FILES)
+        rest = re.compile(head + r"(checkpoint|progress|covmat|%s|\d+\.(state\.npz|%s))$" % (products, ring))
         names = sorted(os.listdir(folder))
         return ([os.path.join(folder, n) for n in names if chain.match(n)],
                 [os.path.join(folder, n) for n in names if rest.match(n)])

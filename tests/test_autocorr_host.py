@@ -27,6 +27,11 @@ def make(prefix=None, max_samples=30000, resume=False, **opts):
     return OnDouble(o, ProblemSpec.from_info(QUICK), output=prefix, resume=resume)
 
 
+def acc(s):
+    """The sampler's `AutoCorrAccumulator` (None: the option is off)."""
+    return next((p for p in s._products if p.name == "autocorr"), None)
+
+
 # ------------------------------------------------------------------------------- the option
 def test_every_shorthand_of_the_option():
     names = ["a", "b", "c"]
@@ -37,12 +42,12 @@ def test_every_shorthand_of_the_option():
     assert parse_option({"params": "all", "lags": 64}, names) == {"params": names, "lags": 64}
     assert parse_option({"params": ["c", "a"], "lags": 1}, names) == {"params": ["c", "a"], "lags": 1}
     s = make(autocorr=True)
-    assert s._ac == {"params": ["a", "b"], "lags": 16, "interval_steps": 40}
+    assert acc(s).cfg == {"params": ["a", "b"], "lags": 16, "interval_steps": 40}
     assert s.engine.autocorr_layout() == {"n_dims": 2, "lags": 16, "n_doubles": 3 * 17 * 2, "held": 0}
     s = make(autocorr={"params": ["b"], "lags": 5}, moments_every=3)
-    assert s._ac["interval_steps"] == 120 and s.engine._acr.dims == [1]
+    assert acc(s).cfg["interval_steps"] == 120 and s.engine._acr.dims == [1]
     off = make(autocorr=None)
-    assert off._ac is None and off.engine._acr is None
+    assert acc(off) is None and off.engine._acr is None
     off.run()
     assert "autocorr" not in off.products() and not hasattr(off.engine, "ac_snapshots")
 
@@ -222,7 +227,7 @@ def test_products_hold_the_window_of_the_moments_and_nothing_older():
     s = make(max_samples=60000)
     s.run()
     assert len(s.progress) >= 5 and s._dropped_snapshots > 0 and s._iv0 > 0   # intervals were dropped
-    assert len(s._ac_ivs) == len(s._intervals)
+    assert len(acc(s).ivs) == len(s._intervals)
     ac = s.products()["autocorr"]
     snaps = s.engine.ac_snapshots
     n_window = sum(iv[0] for iv in s._intervals) + s._snaps_in_interval
@@ -237,7 +242,7 @@ def test_products_hold_the_window_of_the_moments_and_nothing_older():
     again = s.products(combined=True)["autocorr"]     # reading the open sums does not disturb them
     assert again == ac
     s.close()
-    assert s._autocorr_product() == ac     # (the open sums were kept at close)
+    assert acc(s).product(s._intervals) == ac     # (the open sums were kept at close)
 
 
 def test_a_resume_in_mid_interval_restores_the_sums_and_refills_the_ring(tmp_path):

@@ -324,7 +324,7 @@ def test_run_holds_the_window_exactly_as_the_rule_on_the_stored_rows():
         assert np.isfinite(ac.tau(name)) and (ac.converged(name) or ac.window(name) == 16)
     assert ac.thin()[1] == ac.thin()[0] * 40
     s.close()
-    assert s._autocorr_product() == ac           # the sums outlive the engine
+    assert s._products[-1].product(s._intervals) == ac           # the sums outlive the engine
 
 
 def test_without_the_option_nothing_exists_and_the_chain_is_the_same():

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from cobaya_amd import engine as E
+from cobaya_amd.bounds_ring import BoundsRing
 from cobaya_amd.collection import SampleCollection
 from cobaya_amd.model import ProblemSpec, UnsupportedModel
 from cobaya_amd.sampler import MCMCHip, LoggedError, _number_with_units
@@ -371,7 +372,8 @@ def test_rminus1_of_bounds_statistic():
             x[:64] += shift_group0
             ring.append(x)
         eng._bring = ring
-        s._bslots, s._bsnap_idx = list(range(n_snap)), n_snap
+        s._bounds = BoundsRing(eng, n_snap)
+        s._bounds.slots, s._bounds.n_taken = list(range(n_snap)), n_snap
 
     fill()
     got = s._rminus1_of_bounds(np.eye(d))
@@ -386,34 +388,33 @@ def test_rminus1_of_bounds_statistic():
     assert s._rminus1_of_bounds(np.eye(d)) > 0.5
     fill(same=True)
     assert s._rminus1_of_bounds(np.eye(d)) < 1e-7    # (sqrt of the rounding of E b^2 - (E b)^2)
-    s._bslots = [-1] * 8
+    s._bounds.slots = [-1] * 8
     assert s._rminus1_of_bounds(np.eye(d)) is None
 
 
 @pytest.mark.parametrize("C", [4, 16])
 def test_bounds_ring_follows_the_later_half_of_the_run(C):
-    """`_bounds_take`: at any time the ring holds only snapshots of the window (index >= n / 2),
+    """`BoundsRing.take`: at any time the ring holds only snapshots of the window (index >= n / 2),
     all multiples of the current stride, no index twice -- and, once the run is long enough,
     at least C / 4 of them, spread over the whole window."""
-    spec = ProblemSpec.from_info({"likelihood": {"one": None}, "params": {"p": {"prior": [-1, 1]}}})
-    s = bare_sampler(spec)
     taken = []
 
     class Eng:
         def bounds_snapshot(self, k):
             taken.append(k)
 
-    s.engine = Eng()
-    s._bslots, s._bstride, s._bsnap_idx = [-1] * C, 1, 0
+    r = BoundsRing(Eng(), C)
+    assert (r.slots, r.stride, r.n_taken) == ([-1] * C, 1, 0)
     for n in range(1, 2000):
-        s._bounds_take()
-        assert s._bsnap_idx == n
-        held = sorted(j for j in s._bslots if j >= n / 2.0)
-        assert len(set(held)) == len(held) and all(j % s._bstride == 0 for j in held)
-        assert all(j < n for j in s._bslots)
+        r.take()
+        assert r.n_taken == n
+        held = sorted(j for j in r.slots if j >= n / 2.0)
+        assert held == [j for j, _ in r.window()]
+        assert len(set(held)) == len(held) and all(j % r.stride == 0 for j in held)
+        assert all(j < n for j in r.slots)
         if n >= 8 * C:
-            assert len(held) >= C // 4, (n, s._bslots, s._bstride)
-            assert held[0] < n / 2.0 + 2.5 * s._bstride and held[-1] >= n - 2 * s._bstride
+            assert len(held) >= C // 4, (n, r.slots, r.stride)
+            assert held[0] < n / 2.0 + 2.5 * r.stride and held[-1] >= n - 2 * r.stride
     assert all(0 <= k < C for k in taken)
 
 

@@ -93,6 +93,11 @@ class OnDouble(MCMCHip):
     _engine_factory = staticmethod(MargOracleEngine)
 
 
+def acc(s):
+    """The sampler's `MarginalsAccumulator` (None: the option is off)."""
+    return next((p for p in s._products if p.name == "marginals"), None)
+
+
 def make(prefix=None, max_samples=30000, resume=False, **opts):
     o = {"seed": 21, "n_walkers": 128, "group_size": 64, "steps_per_launch": 40,
          "max_samples": max_samples, "Rminus1_stop": 0.0, "learn_every": "20d",
@@ -180,24 +185,24 @@ def test_every_shorthand_of_the_option():
     one = parse_option({"params": ["c"], "pairs": [["c", "a"]], "bins": 1024, "bins2d": 64,
                         "ranges": {"c": [0, 2]}}, names)
     assert one["params"] == ["c"] and one["pairs"] == [("c", "a")] and one["ranges"] == {"c": (0.0, 2.0)}
-    s = make(marginals=True)
-    assert s._marg["params"] == ["a", "b"] and s._marg["pairs"] == [] and s._marg["bins"] == 128
-    assert make(marginals=None)._marg is None and not hasattr(make(marginals=None).engine, "_mg")
+    cfg = acc(make(marginals=True)).cfg
+    assert cfg["params"] == ["a", "b"] and cfg["pairs"] == [] and cfg["bins"] == 128
+    assert acc(make(marginals=None)) is None and not hasattr(make(marginals=None).engine, "_mg")
 
 
 def test_the_three_range_modes():
     s = make()       # "prior": the uniform prior's bounds, loc +- 5 scale of the normal one
-    assert s._marg["resolved"] == {"a": (-0.5, 3.0), "b": (-5.0, 5.0)}
+    assert acc(s).cfg["resolved"] == {"a": (-0.5, 3.0), "b": (-5.0, 5.0)}
     mg = s.engine._mg
     assert mg["dims1"] == [0, 1] and mg["pairs"] == [(1, 0)] and (mg["bins1"], mg["bins2"]) == (16, 4)
     assert np.array_equal(mg["lo"], [-0.5, -5.0]) and np.array_equal(mg["hi"], [3.0, 5.0])
     s = make(marginals={"params": ["a", "b"], "ranges": {"b": [-1, 1.5]}})   # an explicit entry wins
-    assert s._marg["resolved"] == {"a": (-0.5, 3.0), "b": (-1.0, 1.5)}
+    assert acc(s).cfg["resolved"] == {"a": (-0.5, 3.0), "b": (-1.0, 1.5)}
     s = make(marginals={"params": ["a", "b"], "ranges": "covmat"})
     centre, sig = s._shift, np.sqrt(np.diag(s._initial_covmat))
     want_a = (max(centre[0] - 5 * sig[0], -0.5), min(centre[0] + 5 * sig[0], 3.0))   # clipped to the support
-    assert s._marg["resolved"]["a"] == want_a
-    assert s._marg["resolved"]["b"] == (centre[1] - 5 * sig[1], centre[1] + 5 * sig[1])
+    assert acc(s).cfg["resolved"]["a"] == want_a
+    assert acc(s).cfg["resolved"]["b"] == (centre[1] - 5 * sig[1], centre[1] + 5 * sig[1])
     assert sig[1] == 0.5 and want_a[0] == -0.5      # (`proposal: 0.5`; the lower clip acts)
 
 
@@ -263,7 +268,7 @@ def test_products_hold_the_window_of_the_moments_and_nothing_older():
     s = make(max_samples=60000)
     s.run()
     assert len(s.progress) >= 5 and s._dropped_snapshots > 0 and s._iv0 > 0   # intervals were dropped
-    assert len(s._marg_ivs) == len(s._intervals)
+    assert len(acc(s).ivs) == len(s._intervals)
     m = s.products()["marginals"]
     slab, n = _expected(s)
     assert n == sum(iv[0] for iv in s._intervals) + s._snaps_in_interval < len(s.engine.snapshots)
