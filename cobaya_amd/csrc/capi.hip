@@ -395,6 +395,9 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     h->ac.dims.release();
     if (h->ac.pin) (void)hipHostFree(h->ac.pin);
     if (h->ac.ev) (void)hipEventDestroy(h->ac.ev);
+    h->bf.slab.release(); h->bf.records.release(); h->bf.cand.release(); h->bf.entries.release();
+    if (h->bf.pin) (void)hipHostFree(h->bf.pin);
+    if (h->bf.ev) (void)hipEventDestroy(h->bf.ev);
     if (h->ck.ev) (void)hipEventDestroy(h->ck.ev);
     if (h->pin_mom) (void)hipHostFree(h->pin_mom);
     if (h->pin_T) (void)hipHostFree(h->pin_T);

@@ -23,6 +23,7 @@
 #include "checkpoint_args.h"
 #include "marginal_args.h"
 #include "autocorr_args.h"
+#include "bestfit_args.h"
 #include "comm.h"
 #include "inc_choice.h"
 
@@ -288,6 +289,21 @@ struct mcmc_hip_ctx {
         hipEvent_t ev = nullptr;
         bool pending = false;
     } ac;
+    // best fit, MAP and profile likelihoods (mcmc_hip_bestfit_*; bestfit_kernels.hip): the uint64
+    // slab of keys [n][bins], the two records [2][6 + d] (key, walker, step, logpost, logprior,
+    // loglike, x[d] as 64-bit words), the slices' candidates, and the pinned read-out of slab + records
+    struct BestFit {
+        DevBuf<unsigned long long> slab, records, cand;
+        DevBuf<mcmc::BfEntry> entries;
+        unsigned long long* pin = nullptr;     // [n_slab + n_rec]
+        size_t n_slab = 0, n_rec = 0;
+        int n = 0, bins = 0, quantity = 0;
+        bool on = false;
+        int64_t n_acc = 0;                     // accumulations since the last request / set
+        int64_t pend_n = 0;                    // ... of the pending read-out
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+    } bf;
     // the walker shards' communicator (comm.hip; not owned): the device checkpoint all-reduces
     // its payload over it in stream order
     mcmc_hip_comm* comm = nullptr;

@@ -20,6 +20,7 @@ c_uint64_p = C.POINTER(C.c_uint64)
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOT_PD, ERR_STATE, ERR_STUCK = 0, -1, -2, -3, -4, -5
 ERR_TARGET, ERR_CALLBACK = -6, -7
+BESTFIT_QUANTITIES = ("loglike", "logpost")   # mcmc_hip.h: MCMC_HIP_BESTFIT_LOGLIKE / _LOGPOST
 
 
 class EngineError(RuntimeError):
@@ -157,6 +158,14 @@ SYMBOLS = [
     ("mcmc_hip_autocorr_set", C.c_int, [_H, c_double_p, C.c_int64, c_int64_p]),
     ("mcmc_hip_autocorr_reset", C.c_int, [_H]),
     ("mcmc_hip_autocorr_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int64_p, c_int32_p]),
+    ("mcmc_hip_bestfit_configure", C.c_int, [_H, C.c_int32, c_int32_p, C.c_int32, c_double_p, c_double_p,
+                                             C.c_int32]),
+    ("mcmc_hip_bestfit_accumulate", C.c_int, [_H]),
+    ("mcmc_hip_bestfit_request", C.c_int, [_H]),
+    ("mcmc_hip_bestfit_fetch", C.c_int, [_H, c_uint64_p, C.c_int64, c_uint64_p, C.c_int64, c_int64_p]),
+    ("mcmc_hip_bestfit_set", C.c_int, [_H, c_uint64_p, C.c_int64, c_uint64_p, C.c_int64, C.c_int64]),
+    ("mcmc_hip_bestfit_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p,
+                                          c_int64_p]),
     ("mcmc_hip_gelman_rubin", C.c_int, [C.c_int32, C.c_double, C.c_double, c_double_p,
                                         c_double_p, c_double_p, c_double_p, c_double_p]),
     ("mcmc_hip_enable_timing", C.c_int, [_H, C.c_int32]),
@@ -897,6 +906,63 @@ class Engine:
     def autocorr_reset(self):
         """Empty the ring: the next accumulation pairs with itself only."""
         self._check(self._lib.mcmc_hip_autocorr_reset(self._h))
+
+    # -- best fit, MAP and profile likelihoods
+    def configure_bestfit(self, dims=(), bins=64, lo=None, hi=None, quantity="loglike"):
+        """The two records (map, bestfit) and the profiles every `accumulate_bestfit` takes the
+        ensemble into (mcmc_hip_bestfit_configure): `dims` sampler indices with `bins` bins each
+        over `lo` / `hi` [d], the profiled `quantity` "loglike" or "logpost".  No dims: the records
+        only."""
+        if quantity not in BESTFIT_QUANTITIES:
+            raise EngineError(ERR_ARG, "configure_bestfit: quantity must be one of %r, got %r"
+                              % (BESTFIT_QUANTITIES, quantity))
+        dims = np.ascontiguousarray(dims, dtype=np.int32).reshape(-1)
+        n = len(dims)
+        lo = _f64(lo, (self.d,)) if n else None
+        hi = _f64(hi, (self.d,)) if n else None
+        self._check(self._lib.mcmc_hip_bestfit_configure(
+            self._h, n, _ip(dims) if n else None, int(bins), _dp(lo) if n else None,
+            _dp(hi) if n else None, BESTFIT_QUANTITIES.index(quantity)))
+
+    def bestfit_layout(self):
+        """{"on", "n", "bins", "quantity", "n_slab", "n_records"} (mcmc_hip_bestfit_layout);
+        on == 0: the feature is off."""
+        v = [C.c_int32() for _ in range(4)]
+        ns, nr = C.c_int64(), C.c_int64()
+        self._check(self._lib.mcmc_hip_bestfit_layout(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]),
+                                                      C.byref(v[3]), C.byref(ns), C.byref(nr)))
+        return {"on": v[0].value, "n": v[1].value, "bins": v[2].value,
+                "quantity": BESTFIT_QUANTITIES[v[3].value], "n_slab": ns.value, "n_records": nr.value}
+
+    def accumulate_bestfit(self):
+        """Queue one accumulation: every walker of this process, once, into the profiles and the
+        two records."""
+        self._check(self._lib.mcmc_hip_bestfit_accumulate(self._h))
+
+    def request_bestfit(self):
+        """Queue the read-out and the emptying of slab and records behind the work already in the
+        stream."""
+        self._check(self._lib.mcmc_hip_bestfit_request(self._h))
+
+    def fetch_bestfit(self):
+        """(slab[n, bins] uint64 keys, records[2, 6 + d] uint64 words, n_accumulations) of the
+        pending request; waits for its copy only."""
+        lay = self.bestfit_layout()
+        slab = np.zeros((lay["n"], lay["bins"]), np.uint64)
+        rec = np.zeros((2, lay["n_records"] // 2), np.uint64)
+        k = C.c_int64()
+        self._check(self._lib.mcmc_hip_bestfit_fetch(
+            self._h, slab.ctypes.data_as(c_uint64_p), slab.size, rec.ctypes.data_as(c_uint64_p), rec.size,
+            C.byref(k)))
+        return slab, rec, k.value
+
+    def bestfit_set(self, slab, records, n_accumulations):
+        """Restore slab and records of an unfinished interval (resume)."""
+        s = np.ascontiguousarray(slab, dtype=np.uint64).reshape(-1)
+        r = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1)
+        self._check(self._lib.mcmc_hip_bestfit_set(
+            self._h, s.ctypes.data_as(c_uint64_p), len(s), r.ctypes.data_as(c_uint64_p), len(r),
+            int(n_accumulations)))
 
     # -- the checkpoint on the device
     def checkpoint_set_ring(self, intervals=(), min_capacity=16, first_index=0):

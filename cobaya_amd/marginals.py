@@ -310,11 +310,12 @@ ENGINE_METHODS = ("configure_marginals", "accumulate_marginals", "request_margin
 
 class MarginalsAccumulator:
     """What the sampler holds of the histograms while it runs.  A DEVICE PRODUCT is a class with
-    these methods, listed in `EnsembleMCMC.PRODUCT_CLASSES` (the other one: `AutoCorrAccumulator`):
+    these methods, listed in `EnsembleMCMC.PRODUCT_CLASSES` (the others:
+    `AutoCorrAccumulator`, `BestFitAccumulator`):
 
       from_option(opt, spec, engine_factory, host) -> the object, or None where the option is off;
           refuses by the option's name BEFORE the engine is created.  `host` is what the sampler hands
-          in: fail(msg, *args, cause=None), n_walkers, size, all_reduce_sum, temperature,
+          in: fail(msg, *args, cause=None), n_walkers, size, rank, all_reduce_sum, temperature,
           snapshot_steps (the steps between two moment snapshots)
       attach(engine, resumed, centre, covmat): configure the engine, cross-check its layout
       accumulate(), request(): beside every moment snapshot; beside every checkpoint request

@@ -36,6 +36,7 @@ import pandas as pd
 
 from . import dist
 from .autocorr import AutoCorrAccumulator
+from .bestfit import BestFitAccumulator
 from .bounds_ring import BoundsRing
 from .collection import SampleCollection
 from .engine import (ChainStuck, Engine, EngineError, NotPositiveDefinite, gelman_rubin,
@@ -158,6 +159,15 @@ HIP_DEFAULTS = {
                               # size, a thinning suggestion).  None: off.  True: every sampled
                               # parameter, 16 lags.  Or {"params": [names] | "all", "lags": 1..64};
                               # one lag is steps_per_launch x moments_every steps
+    "bestfit": None,          # best fit, MAP and profile likelihoods of the ensemble, kept on the device
+                              # from EVERY walker of every moment snapshot of the window (the
+                              # snapshot populations, not every trial between them) --
+                              # products()["bestfit"], a `cobaya_amd.bestfit.BestFit` (`map`,
+                              # `bestfit`, profile(name), delta_chi2(name), interval(name)).  None:
+                              # off.  True: both records and the profile of every sampled
+                              # parameter.  Or {"params": [names] | "all" | None (records only),
+                              # "bins": 64, "ranges": {name: [lo, hi]} | "prior" | "covmat",
+                              # "quantity": "loglike" | "logpost"}
     "shared_basis": True,     # True: the walkers of a group share one Haar basis per cycle;
                               # False: every walker draws its own (proposal.py:59-69 to the
                               # letter: the reference-faithful control, much slower)
@@ -238,10 +248,10 @@ class EnsembleMCMC:
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
     MAX_DIM = 128    # ctx.h: kMaxDimBig, every path (mixtures: at most 64 modes, model.py)
     HUGE_MAX_MODES = 4   # 128 < d <= max_dim(): huge_kernels.hip (huge_args.h: kHugeMaxModes)
-    marginals = autocorr = None     # (the options' default: off)
+    marginals = autocorr = bestfit = None     # (the options' default: off)
     # What is accumulated on the device beside every moment snapshot (marginals.py states the
     # methods): a new product is one such class, appended here.  `_products`: those that are on
-    PRODUCT_CLASSES = (MarginalsAccumulator, AutoCorrAccumulator)
+    PRODUCT_CLASSES = (MarginalsAccumulator, AutoCorrAccumulator, BestFitAccumulator)
     _products = ()
 
     def _max_dim(self):
@@ -458,7 +468,7 @@ class EnsembleMCMC:
         # (they must not hold the sampler, not even through `self._fail`: an engine that nobody
         # closed is freed with the sampler's last reference, not by the cycle collector)
         host = SimpleNamespace(fail=partial(log_and_raise, self._LoggedError, self.log), n_walkers=W,
-                               size=self.size, all_reduce_sum=dist.all_reduce_sum, temperature=self.temperature,
+                               size=self.size, rank=self.rank, all_reduce_sum=dist.all_reduce_sum, temperature=self.temperature,
                                snapshot_steps=int(self.steps_per_launch) * max(1, int(self.moments_every)))
         made = [c.from_option(getattr(self, c.name), spec, self._engine_factory, host)
                 for c in self.PRODUCT_CLASSES]

@@ -406,6 +406,39 @@ MCMC_HIP_API int mcmc_hip_autocorr_reset(mcmc_hip_ctx* h);
 MCMC_HIP_API int mcmc_hip_autocorr_layout(const mcmc_hip_ctx* h, int32_t* n_dims, int32_t* lags, int64_t* n_doubles,
                              int32_t* held);
 
+/* Best fit, MAP and profile likelihoods of the ensemble (bestfit_kernels.hip).  Same life cycle as
+ * the marginals.  The rule ("Best fit and profiles"): the ordering key of a
+ * double v is b ^ ((b >> 63) ? ~0 : 1 << 63) with b = bits(v), an unsigned 64-bit integer whose order
+ * is the order of the doubles (-0.0 < +0.0; -inf is the smallest non-empty key; NaN is skipped;
+ * 0 = empty).  An accumulation reads x, logpost, logprior and loglike as the state holds them
+ * between two launches.
+ * records[2][6 + d] as 64-bit words -- 0: map (maximum of logpost), 1: bestfit (maximum of loglike):
+ * key, global walker id (walker_offset + w), step counter at the accumulation, bits of logpost,
+ * logprior, loglike, bits of x[d].  Within an accumulation ties on the key go to the lowest walker
+ * id; a later accumulation replaces a record only with a strictly greater key.
+ * slab[n][bins]: bin k of configured parameter dims[e] holds the largest key of the profiled
+ * `quantity` among the walkers whose x[dims[e]] is in range (lo <= x <= hi) and falls in that bin --
+ * the marginals' rule, k = min((int)floor((x - lo) * s), bins - 1), s = bins / (hi - lo).
+ * configure: n >= 0 parameters (n = 0: the records only; dims, lo, hi may then be NULL), bins in
+ * 1..1024, lo / hi [d] the fixed range of every parameter in use; empties everything.
+ * request / fetch / set: as for the marginals, for slab and records together; the read-out leaves
+ * slab and records empty in stream order.  One request may be pending.  Before configure,
+ * accumulate / request / set answer MCMC_HIP_ERR_STATE and nothing is allocated or launched.
+ * layout: on (0 before configure), n, bins, quantity, n_slab = n * bins, n_records = 2 (6 + d); any
+ * pointer may be NULL. */
+#define MCMC_HIP_BESTFIT_LOGLIKE 0
+#define MCMC_HIP_BESTFIT_LOGPOST 1
+MCMC_HIP_API int mcmc_hip_bestfit_configure(mcmc_hip_ctx* h, int32_t n, const int32_t* dims, int32_t bins,
+                               const double* lo, const double* hi, int32_t quantity);
+MCMC_HIP_API int mcmc_hip_bestfit_accumulate(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_bestfit_request(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_bestfit_fetch(mcmc_hip_ctx* h, uint64_t* slab, int64_t n_slab, uint64_t* records,
+                           int64_t n_records, int64_t* n_accumulations);
+MCMC_HIP_API int mcmc_hip_bestfit_set(mcmc_hip_ctx* h, const uint64_t* slab, int64_t n_slab, const uint64_t* records,
+                         int64_t n_records, int64_t n_accumulations);
+MCMC_HIP_API int mcmc_hip_bestfit_layout(const mcmc_hip_ctx* h, int32_t* on, int32_t* n, int32_t* bins,
+                            int32_t* quantity, int64_t* n_slab, int64_t* n_records);
+
 /* The learn / convergence checkpoint ON THE DEVICE (MCMC.check_convergence_and_learn_proposal,
  * mcmc.py:773-1032; checkpoint_kernels.hip): the intervals between checkpoints are kept in a
  * device ring, the statistics of the window (the later half of the run, mcmc.py:787-790) are

@@ -58,6 +58,7 @@ else:
         emit_thin: int | None = HIP_DEFAULTS["emit_thin"]
         marginals: bool | dict | None = HIP_DEFAULTS["marginals"]
         autocorr: bool | dict | None = HIP_DEFAULTS["autocorr"]
+        bestfit: bool | dict | None = HIP_DEFAULTS["bestfit"]
 
         def _export_collection(self, coll):
             """Our table -> `cobaya.collection.SampleCollection` (same columns,
@@ -87,6 +88,8 @@ else:
                 regexps.append((re.compile(output.prefix_regexp_str + r"marginals\.npz$"), None))
                 # the autocorrelation sums of `autocorr` (written once, at the end of the run)
                 regexps.append((re.compile(output.prefix_regexp_str + r"autocorr\.npz$"), None))
+                # the records and profiles of `bestfit` (written once, at the end of the run)
+                regexps.append((re.compile(output.prefix_regexp_str + r"bestfit\.npz$"), None))
             return regexps
 
 
