@@ -126,6 +126,41 @@ __device__ __forceinline__ lds_doubles relaunder(const double* p)
     return (lds_doubles)(unsigned long long)off;
 }
 
+// 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4: lane l of the wave
+// writes lds_byte_addr + 16 l; M0 = the wave-uniform LDS byte address), issued where the compiler does
+// not count it (round 14).  While a __builtin_amdgcn_global_load_lds is in flight hipcc's wait
+// bookkeeping takes the LGKM counter as out of order: every wait for an LDS read of the chunk -- a whole
+// chunk of steps runs beside the DMA of the next -- becomes s_waitcnt lgkmcnt(0), and a step that
+// issues its sixteen ds_read_b128 up front starts its first fma when the LAST has landed.  The hardware
+// counts an LDS-DMA on vmcnt alone and returns a wave's LDS reads in order; with the DMA inside an asm
+// statement the compiler waits for each read by its count (lgkmcnt(14), (13), ...: tools/check_lds_waits.py).
+//   - No register is written (M0 is saved and restored inside the statement), so nothing the compiler
+//     does with its registers can come too early.
+//   - The data is waited for BY HAND: `s_waitcnt vmcnt(0)` (dma_wait) in front of the barrier that
+//     publishes a staged buffer; __syncthreads() no longer waits for it.
+//   - The compiler's own counted vmcnt waits stay safe: a wave's loads retire in order.  A DMA OLDER than
+//     the load the compiler waits for has landed when that load has -- the compiler's count, which leaves
+//     the DMA out, names a load at least as young --, and a YOUNGER one it did not count only makes the
+//     wait longer: vmcnt(N) then asks for more than was needed, never for less.
+//   - Keep no scalar load in flight across a run of LDS reads: SMEM answers truly out of order on the same
+//     counter, and lgkmcnt(0) is back.
+// hidden = false is the builtin (kernels that did not gain: profiles/r14_lds_wait_ladder.txt).
+template <bool hidden>
+__device__ __forceinline__ void stage16_dma(void* lds_dst, const void* gsrc)   // lds_dst: wave-uniform, in LDS
+{
+    if constexpr (hidden) {
+        const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_offset(lds_dst));
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
+    } else {
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                         (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+    }
+}
+// every DMA of this wave has landed (in front of the barrier that publishes the buffer)
+__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
 // The (r, Ea) variates of an OCTET of steps, staged in LDS (round 4).  Lane class c of a walker draws
 // the Philox block of the step pair 4 * octet + c (PairRng) and leaves its two pairs in the wave's
 // corner of a workgroup array sRE[kStagedPairs] = [wave][step of the octet][walker of the wave];

@@ -59,6 +59,14 @@
 #ifndef MCMC_DUO_KEEPV
 #define MCMC_DUO_KEEPV(tuned) (tuned)
 #endif
+// the staging DMA of step_inc_duo_kernel where the compiler does not count it (incremental_common.h: stage16_dma;
+// measured: profiles/r14_lds_wait_ladder.txt; step_duo_mix_kernel was measured with it at K = 2 and keeps the builtin)
+#ifndef MCMC_DUO1_DMA_HIDDEN
+#define MCMC_DUO1_DMA_HIDDEN 1
+#endif
+#ifndef MCMC_DUO1_LADDER
+#define MCMC_DUO1_LADDER 4   // (pairs per counted LDS wait of the one-mode step, >= 1: see its step loop)
+#endif
 
 namespace mcmc {
 namespace {
@@ -173,9 +181,7 @@ __global__ void __launch_bounds__(256, 2) step_duo_mix_kernel(const IncStepArgs 
         char* dst = (char*)(smem + (k & 1) * CHUNK);
         for (int kb = wave; kb * 1024 < bytes; kb += 4) {
             if (kb * 1024 + lane * 16 < bytes)
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void*)(src + kb * 1024 + lane * 16),
-                    (__attribute__((address_space(3))) void*)(dst + kb * 1024), 16, 0, 0);
+                stage16_dma<false>(dst + kb * 1024, src + kb * 1024 + lane * 16);
         }
     };
     stage(0);
@@ -223,7 +229,7 @@ __global__ void __launch_bounds__(256, 2) step_duo_mix_kernel(const IncStepArgs 
     const short_log_tab slog = short_log_load(short_log_lds);
     __shared__ double exp64_lds[64];   // 2^(j / 64): the log-sum-exp's table-driven exponential
     const exp_tab etab = exp_tab_load(exp64_lds);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dma_wait();   // chunk 0 has landed
     __syncthreads();
     const unsigned long long half1 = 0xAAAAAAAAAAAAAAAAull;   // the lanes with h = 1
     auto lse = [&](const double (&ak)[KM]) {
@@ -450,7 +456,7 @@ __global__ void __launch_bounds__(256, 2) step_duo_mix_kernel(const IncStepArgs 
             nacc += sel(acc_m, 1, 0);
             if (wt - prej > lim && h == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        dma_wait();   // the next chunk has landed
         __syncthreads();
     }
     // (the walker index passes through an empty asm: the addresses of the stores below are then
@@ -589,9 +595,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
         char* dst = (char*)(smem2 + (k & 1) * CHUNK);
         for (int kb = wave; kb * 1024 < bytes; kb += 4) {
             if (kb * 1024 + lane * 16 < bytes)
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void*)(src + kb * 1024 + lane * 16),
-                    (__attribute__((address_space(3))) void*)(dst + kb * 1024), 16, 0, 0);
+                stage16_dma<MCMC_DUO1_DMA_HIDDEN != 0>(dst + kb * 1024, src + kb * 1024 + lane * 16);
         }
     };
     const bool refresh_y = (a.anchor & 2) != 0;   // wave-uniform
@@ -654,7 +658,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
         lpost = lpri + llik;
     }
     int wt = s.weight[w], prej = s.prior_rej[w], burn = s.burn_left[w];
-    const long long nacc0 = s.n_accept[w];
+    long long nacc0 = s.n_accept[w];
     int nacc = 0;
     const cdoubles gUU = (cdoubles)(unsigned long long)(a.UU + (size_t)g * set_cols + (size_t)a.col0);
     const uint32_t gid = s.walker0 + (uint32_t)w;
@@ -663,8 +667,15 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
     const int lim10 = mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff;
     __shared__ dpair_t short_log_lds[SHORT_LOG_TABLE_SIZE];
     const short_log_tab slog = short_log_load(short_log_lds);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dma_wait();   // chunk 0 has landed
     __syncthreads();
+    // (the walker's own loads have landed with it, and the compiler is told so: it does not see the wait above, and
+    // with one of them pending by its books it drains vmcnt in front of every chunk's steps -- the DMA just issued)
+    if constexpr (MCMC_DUO1_DMA_HIDDEN != 0) {
+        asm volatile("" : "+v"(lpost), "+v"(lpri), "+v"(llik), "+v"(wt), "+v"(prej), "+v"(burn), "+v"(nacc0));
+#pragma unroll
+        for (int e = 0; e < NE; ++e) asm volatile("" : "+v"(x[e]), "+v"(y[e]));
+    }
     bool burning = lanes(burn > 0) != 0ull;   // wave-uniform
     unsigned long long cur_oct = ~0ull;
     DuoVariates sv;
@@ -693,7 +704,6 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
             double r, Ea;
             sv.fetch(r, Ea);
             sv.next();
-            const double uu = gUU[base + sl];   // (wave-uniform address: a scalar load)
             // the step's pairs stay in registers from the trial to the commit (requesting the next
             // step's behind the commit, over the bookkeeping, was measured slower: 1.24 against 1.02 ms)
             pair_t pk[NE];
@@ -703,14 +713,36 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
             // the support test on the high words of the trial coordinates (step_inc_kernel MODE 0)
             unsigned hmx = 0u;
             double pc0 = 0.0, pc1 = 0.0;
+            // The reads land in order and each is waited for by its count (stage16_dma), so the arithmetic runs
+            // underneath their return: groups of G = MCMC_DUO1_LADDER pairs (1 <= G <= NE; measured at dq = 8 only:
+            // G = 4 against G = 1 and the compiler's own order, profiles/r14_lds_wait_ladder.txt; the smaller dq
+            // take the same G unmeasured) pinned in this order: the trial of the group's LAST pair first -- one rung
+            // retires the group's reads --, then the others, then the group's y . u in ascending order (the sums'
+            // order is the specification's).
+            {
+                constexpr int G = MCMC_DUO1_LADDER;
+                static_assert(G >= 1, "pairs per rung");
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                const double t = fma(r, pk[e].x, x[e]);
-                const unsigned hw = (unsigned)__double2hiint(t);
-                hmx = hmx > hw ? hmx : hw;
-                if (e & 1) pc1 = fma(y[e], pk[e].y, pc1);   // (y . u: the log-likelihood is carried)
-                else pc0 = fma(y[e], pk[e].y, pc0);
+                for (int e0 = 0; e0 < NE; e0 += G) {
+                    const int e1 = e0 + G < NE ? e0 + G : NE;
+#pragma unroll
+                    for (int q = 0; q < e1 - e0; ++q) {
+                        const int e = q == 0 ? e1 - 1 : e0 + q - 1;
+                        const unsigned hw = (unsigned)__double2hiint(fma(r, pk[e].x, x[e]));
+                        hmx = hmx > hw ? hmx : hw;
+                    }
+#pragma unroll
+                    for (int e = e0; e < e1; ++e) {
+                        if (e & 1) pc1 = fma(y[e], pk[e].y, pc1);   // (y . u: the log-likelihood is carried)
+                        else pc0 = fma(y[e], pk[e].y, pc0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                asm volatile("" : "+v"(pc0), "+v"(pc1));   // (here, not sunk behind the support test's branch)
             }
+            // (behind the last rung: a scalar load in flight across the reads puts LGKM truly out of order)
+            const double uu = gUU[base + sl];   // (wave-uniform address: a scalar load)
             unsigned long long inside_m = lanes(pair_max_u32(hmx) < bhi_word);
             if (inside_m != lanes(true)) {   // (wave-uniform, rare) the exact test
                 unsigned long long inb = ~0ull;
@@ -756,7 +788,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
             }
             if (wt - prej > lim && h == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next chunk has landed
+        dma_wait();   // the next chunk has landed
         __syncthreads();
     }
     // (the walker index passes through an empty asm: the store addresses are formed here, not kept

@@ -26,6 +26,14 @@
 
 #include "incremental_common.h"
 
+// step_inc_kernel stages its chunks where the compiler does not count the DMA (incremental_common.h: stage16_dma) and
+// requests |u|^2 behind the pair reads in the instantiations measured to gain by it: one box (MODE 0) from dq = 25 on,
+// measured at d = 100 (bench.py --dim 100 +1.2 %, profiles/r14_lds_wait_ladder.txt); dq = 26 .. 32 take it unmeasured,
+// every other instantiation keeps the builtin, unmeasured
+#ifndef MCMC_INC_DMA_HIDDEN
+#define MCMC_INC_DMA_HIDDEN(dq, mode) ((dq) >= 25 && (mode) == 0)
+#endif
+
 namespace mcmc {
 namespace {
 
@@ -232,6 +240,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
     const double* __restrict__ gW =
         NORMP ? a.VW + ((size_t)g * set_cols + (size_t)a.col0) * COLB : nullptr;
 
+    constexpr bool DMAH = MCMC_INC_DMA_HIDDEN(DQ, MODE);
     // chunk k of the launch -> buffer k & 1, by DMA: every wave moves every fourth KiB
     auto stage = [&](int k) {
         const int first = k * C;
@@ -242,9 +251,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
         char* dst = (char*)(sVU + (k & 1) * CHUNK);
         for (int kb = wave; kb * 1024 < bytes; kb += 4) {
             if (kb * 1024 + lane * 16 < bytes)
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void*)(src + kb * 1024 + lane * 16),
-                    (__attribute__((address_space(3))) void*)(dst + kb * 1024), 16, 0, 0);
+                stage16_dma<DMAH>(dst + kb * 1024, src + kb * 1024 + lane * 16);
         }
         if (NORMP) {   // the chunk's w (8 bytes per dimension and column), dealt from the last wave down
             const int wbytes = cols * COLB * 8;
@@ -252,9 +259,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
             char* wdst = (char*)(sW + (k & 1) * CHUNK);
             for (int kb = 3 - wave; kb * 1024 < wbytes; kb += 4) {
                 if (kb * 1024 + lane * 16 < wbytes)
-                    __builtin_amdgcn_global_load_lds(
-                        (const __attribute__((address_space(1))) void*)(wsrc + kb * 1024 + lane * 16),
-                        (__attribute__((address_space(3))) void*)(wdst + kb * 1024), 16, 0, 0);
+                    stage16_dma<DMAH>(wdst + kb * 1024, wsrc + kb * 1024 + lane * 16);
             }
         }
     };
@@ -462,6 +467,8 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
     const short_log_tab slog = short_log_load(short_log_lds);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if constexpr (DMAH)   // (the walker's own loads have landed by the compiler's books too)
+        asm volatile("" : "+v"(lpost), "+v"(lpri), "+v"(llik), "+v"(wt), "+v"(prej), "+v"(burn));
     bool burning = lanes(burn > 0) != 0ull;   // wave-uniform
     unsigned long long cur_oct = ~0ull;
     StagedVariates sv;
@@ -505,7 +512,8 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
                         sv.fetch(r, Ea);
                     }
                     sv.next();
-                    const double uu = gUU[base + sl];   // (wave-uniform address: a scalar load)
+                    double uu;
+                    if constexpr (!DMAH) uu = gUU[base + sl];   // (wave-uniform address: a scalar load)
                     const lds_pairs col = (lds_pairs)(unsigned long long)coff;
                     const lds_doubles wcol = (lds_doubles)(unsigned long long)woff;
                     double pc = 0.0, sc = 0.0;
@@ -590,6 +598,12 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
                             for (int j = 0; j < PIPE; ++j)
                                 if (b * PIPE + j < DQ) trial(b * PIPE + j, buf[b & 1][j]);
                         }
+                    }
+                    // (with the DMA hidden: behind the pair reads -- a scalar load in flight across them puts
+                    // LGKM out of order, see stage16_dma)
+                    if constexpr (DMAH) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        uu = gUU[base + sl];
                     }
                     // inside the prior support = all four lanes of the walker are: the AND over
                     // the quad is taken on the wave's lane mask (scalar unit, no vector work)
