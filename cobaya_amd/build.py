@@ -107,6 +107,7 @@ def translation_units(dims, big=True):
             ("marginal_kernels.hip", "marginal", []),   # streaming 1-D / 2-D marginal histograms
             ("autocorr_kernels.hip", "autocorr", []),   # lagged cross-products (autocorrelation time)
             ("bestfit_kernels.hip", "bestfit", []),     # best fit, MAP and profile likelihoods
+            ("evidence_kernels.hip", "evidence", []),   # the sums of the truncated harmonic mean (evidence)
             ("comm.hip", "comm", [])]   # the RCCL communicator (bound at run time)
     tus += [("incremental_kernels.hip", f"incremental_{lo}", [f"-DMCMC_DQ_LO={lo}", f"-DMCMC_DQ_HI={hi}"])
             for lo, hi in INC_DQ_RANGES]
@@ -128,7 +129,8 @@ def translation_units(dims, big=True):
             ("capi_checkpoint.hip", "capi_checkpoint", []),
             ("capi_marginals.hip", "capi_marginals", []),
             ("capi_autocorr.hip", "capi_autocorr", []),
-            ("capi_bestfit.hip", "capi_bestfit", [])]
+            ("capi_bestfit.hip", "capi_bestfit", []),
+            ("capi_evidence.hip", "capi_evidence", [])]
     return tus
 
 

@@ -398,6 +398,10 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     h->bf.slab.release(); h->bf.records.release(); h->bf.cand.release(); h->bf.entries.release();
     if (h->bf.pin) (void)hipHostFree(h->bf.pin);
     if (h->bf.ev) (void)hipEventDestroy(h->bf.ev);
+    h->evd.slab.release(); h->evd.ell.release(); h->evd.s.release();
+    if (h->evd.pin) (void)hipHostFree(h->evd.pin);
+    if (h->evd.pin_ell) (void)hipHostFree(h->evd.pin_ell);
+    if (h->evd.ev) (void)hipEventDestroy(h->evd.ev);
     if (h->ck.ev) (void)hipEventDestroy(h->ck.ev);
     if (h->pin_mom) (void)hipHostFree(h->pin_mom);
     if (h->pin_T) (void)hipHostFree(h->pin_T);

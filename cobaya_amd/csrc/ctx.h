@@ -24,6 +24,7 @@
 #include "marginal_args.h"
 #include "autocorr_args.h"
 #include "bestfit_args.h"
+#include "evidence_args.h"
 #include "comm.h"
 #include "inc_choice.h"
 
@@ -304,6 +305,25 @@ struct mcmc_hip_ctx {
         hipEvent_t ev = nullptr;
         bool pending = false;
     } bf;
+    // evidence of the run (mcmc_hip_evidence_*; evidence_kernels.hip): the slab of 64-bit words
+    // acc[G][n_r] doubles | cnt[G][n_r] uint64 | clamped uint64 | the key of c, the active ellipsoid
+    // m[d] | Linv[d][d] on the device, the staged one in pinned memory until a closing request
+    // uploads it in stream order; host copies of both travel with every read-out
+    struct Evidence {
+        DevBuf<double> slab, ell, s;           // [2 G n_r + 2], [d + d d], [W]
+        double* pin = nullptr;                 // the slab's read-out
+        double* pin_ell = nullptr;             // [d + d d] the ellipsoid on its way to the device
+        std::vector<double> active, staged;    // [d + d d] each (empty: none)
+        std::vector<double> pend_active, pend_staged;   // ... as they were at the pending request
+        double r2[mcmc::kEvMaxRadii] = {};
+        size_t n_words = 0;
+        int n_r = 0;
+        bool on = false;
+        int64_t n_acc = 0;                     // accumulations since the last closing request / set
+        int64_t pend_n = 0;                    // ... of the pending read-out
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+    } evd;
     // the walker shards' communicator (comm.hip; not owned): the device checkpoint all-reduces
     // its payload over it in stream order
     mcmc_hip_comm* comm = nullptr;

@@ -164,6 +164,16 @@ SYMBOLS = [
     ("mcmc_hip_bestfit_request", C.c_int, [_H]),
     ("mcmc_hip_bestfit_fetch", C.c_int, [_H, c_uint64_p, C.c_int64, c_uint64_p, C.c_int64, c_int64_p]),
     ("mcmc_hip_bestfit_set", C.c_int, [_H, c_uint64_p, C.c_int64, c_uint64_p, C.c_int64, C.c_int64]),
+    ("mcmc_hip_evidence_configure", C.c_int, [_H, C.c_int32, c_double_p]),
+    ("mcmc_hip_evidence_set_ellipsoid", C.c_int, [_H, c_double_p, c_double_p]),
+    ("mcmc_hip_evidence_accumulate", C.c_int, [_H]),
+    ("mcmc_hip_evidence_request", C.c_int, [_H, C.c_int32]),
+    ("mcmc_hip_evidence_fetch", C.c_int, [_H, c_double_p, c_uint64_p, C.c_int64, c_uint64_p, c_int64_p,
+                                          c_double_p, c_double_p, C.c_int64, c_int32_p, c_int32_p]),
+    ("mcmc_hip_evidence_set", C.c_int, [_H, c_double_p, c_uint64_p, C.c_int64, C.c_uint64, C.c_int64,
+                                        c_double_p, c_double_p, C.c_int64]),
+    ("mcmc_hip_evidence_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p, c_int64_p, c_int32_p,
+                                           c_int32_p, c_int64_p]),
     ("mcmc_hip_bestfit_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p,
                                           c_int64_p]),
     ("mcmc_hip_gelman_rubin", C.c_int, [C.c_int32, C.c_double, C.c_double, c_double_p,
@@ -963,6 +973,65 @@ class Engine:
         self._check(self._lib.mcmc_hip_bestfit_set(
             self._h, s.ctypes.data_as(c_uint64_p), len(s), r.ctypes.data_as(c_uint64_p), len(r),
             int(n_accumulations)))
+
+    # -- evidence: the sums of the ellipsoid-truncated harmonic mean
+    def configure_evidence(self, r2=()):
+        """The radii (R^2, ascending; 1..8 of them) whose sums every `accumulate_evidence` adds to
+        (mcmc_hip_evidence_configure).  None listed: off, everything is freed."""
+        r2 = np.ascontiguousarray(r2, dtype=np.float64).reshape(-1)
+        self._check(self._lib.mcmc_hip_evidence_configure(self._h, len(r2), _dp(r2) if len(r2) else None))
+
+    def evidence_layout(self):
+        """{"on", "n_radii", "n_groups", "n_ell", "active", "staged", "n_accumulations"}
+        (mcmc_hip_evidence_layout); all zero: off."""
+        v = [C.c_int32() for _ in range(5)]
+        ne, na = C.c_int64(), C.c_int64()
+        self._check(self._lib.mcmc_hip_evidence_layout(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]),
+                                                       C.byref(ne), C.byref(v[3]), C.byref(v[4]), C.byref(na)))
+        return {"on": v[0].value, "n_radii": v[1].value, "n_groups": v[2].value, "n_ell": ne.value,
+                "active": v[3].value, "staged": v[4].value, "n_accumulations": na.value}
+
+    def evidence_set_ellipsoid(self, centre, covmat):
+        """Hand in an ellipsoid as (m[d], C[d][d]); the library forms the inverse of chol(C).  The
+        first one becomes active at once, with c = the maximum of logpost; a later one is staged
+        until the next closing request."""
+        self._check(self._lib.mcmc_hip_evidence_set_ellipsoid(
+            self._h, _dp(_f64(centre, (self.d,))), _dp(_f64(covmat, (self.d, self.d)))))
+
+    def accumulate_evidence(self):
+        """Queue one accumulation: every walker of this process, once, under the active ellipsoid."""
+        self._check(self._lib.mcmc_hip_evidence_accumulate(self._h))
+
+    def request_evidence(self, close=True):
+        """Queue the read-out behind the work already in the stream.  `close`: also zero the sums
+        and activate a staged ellipsoid, in stream order (False: nothing is disturbed)."""
+        self._check(self._lib.mcmc_hip_evidence_request(self._h, 1 if close else 0))
+
+    def fetch_evidence(self):
+        """{"sums" [G, n_radii] float64, "counts" [G, n_radii] uint64, "clamped", "n",
+        "active", "staged"} of the pending request; an ellipsoid is the flat m[d] | Linv[d][d] | c
+        or None; waits for the copy only."""
+        lay = self.evidence_layout()
+        shape = (lay["n_groups"], lay["n_radii"])
+        sums, counts = np.zeros(shape), np.zeros(shape, np.uint64)
+        act, stg = np.zeros(lay["n_ell"]), np.zeros(lay["n_ell"])
+        cl, k, ha, hs = C.c_uint64(), C.c_int64(), C.c_int32(), C.c_int32()
+        self._check(self._lib.mcmc_hip_evidence_fetch(
+            self._h, _dp(sums), counts.ctypes.data_as(c_uint64_p), sums.size, C.byref(cl), C.byref(k),
+            _dp(act), _dp(stg), lay["n_ell"], C.byref(ha), C.byref(hs)))
+        return {"sums": sums, "counts": counts, "clamped": int(cl.value), "n": int(k.value),
+                "active": act if ha.value else None, "staged": stg if hs.value else None}
+
+    def evidence_set(self, sums, counts, clamped, n_accumulations, active=None, staged=None):
+        """Restore the sums of an unfinished interval and the ellipsoids (resume)."""
+        s = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1)
+        c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        n_ell = self.d * (self.d + 1) + 1
+        act = None if active is None else _f64(active, (n_ell,))
+        stg = None if staged is None else _f64(staged, (n_ell,))
+        self._check(self._lib.mcmc_hip_evidence_set(
+            self._h, _dp(s), c.ctypes.data_as(c_uint64_p), len(s) if len(s) == len(c) else -1, int(clamped),
+            int(n_accumulations), None if act is None else _dp(act), None if stg is None else _dp(stg), n_ell))
 
     # -- the checkpoint on the device
     def checkpoint_set_ring(self, intervals=(), min_capacity=16, first_index=0):

@@ -311,7 +311,7 @@ ENGINE_METHODS = ("configure_marginals", "accumulate_marginals", "request_margin
 class MarginalsAccumulator:
     """What the sampler holds of the histograms while it runs.  A DEVICE PRODUCT is a class with
     these methods, listed in `EnsembleMCMC.PRODUCT_CLASSES` (the others:
-    `AutoCorrAccumulator`, `BestFitAccumulator`):
+    `AutoCorrAccumulator`, `BestFitAccumulator`, `EvidenceAccumulator`):
 
       from_option(opt, spec, engine_factory, host) -> the object, or None where the option is off;
           refuses by the option's name BEFORE the engine is created.  `host` is what the sampler hands
@@ -326,6 +326,9 @@ class MarginalsAccumulator:
       product(intervals, combined, pending); detach(pending): the engine goes, product() still works
       name, reports: the option, the key in products() and the file `prefix.<name>.npz`; whether the
           product has a summary() for the log
+      learned(centre, covmat) -- OPTIONAL: after every checkpoint that yields a positive-definite
+          covariance, the window's pooled mean (None where the host does not know it) and
+          `mean_of_covs`
     `pending`: a checkpoint is requested and not processed yet -- its read-out is then fetched before
     anything else is read, and a product counts it as the newest interval.
 

@@ -41,6 +41,7 @@ from .bounds_ring import BoundsRing
 from .collection import SampleCollection
 from .engine import (ChainStuck, Engine, EngineError, NotPositiveDefinite, gelman_rubin,
                      incremental_supported)
+from .evidence import EvidenceAccumulator
 from .marginals import MarginalsAccumulator
 from .model import ProblemSpec, UnsupportedModel
 
@@ -168,6 +169,14 @@ HIP_DEFAULTS = {
                               # parameter.  Or {"params": [names] | "all" | None (records only),
                               # "bins": 64, "ranges": {name: [lo, hi]} | "prior" | "covmat",
                               # "quantity": "loglike" | "logpost"}
+    "evidence": None,         # ln Z of the run: Gelfand and Dey's harmonic mean truncated to an
+                              # ellipsoid (the window's mean and covariance, fixed before the
+                              # samples it is used on), summed on the device from every walker of
+                              # every `every`-th moment snapshot -- products()["evidence"], a
+                              # `cobaya_amd.evidence.Evidence` (`lnZ`, `stderr`, `radius`,
+                              # lnZ_by_radius(), clipped(), ...).  None: off.  True: the ladder
+                              # R^2 = (0.5, 0.75, 1, 1.5, 2) d.  Or {"radii": [1..8 ascending
+                              # positive f_r], "every": 1}.  Needs temperature: 1
     "shared_basis": True,     # True: the walkers of a group share one Haar basis per cycle;
                               # False: every walker draws its own (proposal.py:59-69 to the
                               # letter: the reference-faithful control, much slower)
@@ -248,10 +257,10 @@ class EnsembleMCMC:
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
     MAX_DIM = 128    # ctx.h: kMaxDimBig, every path (mixtures: at most 64 modes, model.py)
     HUGE_MAX_MODES = 4   # 128 < d <= max_dim(): huge_kernels.hip (huge_args.h: kHugeMaxModes)
-    marginals = autocorr = bestfit = None     # (the options' default: off)
+    marginals = autocorr = bestfit = evidence = None     # (the options' default: off)
     # What is accumulated on the device beside every moment snapshot (marginals.py states the
     # methods): a new product is one such class, appended here.  `_products`: those that are on
-    PRODUCT_CLASSES = (MarginalsAccumulator, AutoCorrAccumulator, BestFitAccumulator)
+    PRODUCT_CLASSES = (MarginalsAccumulator, AutoCorrAccumulator, BestFitAccumulator, EvidenceAccumulator)
     _products = ()
 
     def _max_dim(self):
@@ -1406,6 +1415,12 @@ class EnsembleMCMC:
                         "the samples does not contain enough information at this point. "
                         "Skipping learning a new covmat for now.")
             return
+        # the window's pooled mean (not known where the device solved the checkpoint) and covariance,
+        # for the products that follow the posterior's shape
+        for p in self._products:
+            learned = getattr(p, "learned", None)
+            if learned is not None:
+                learned(None if dev is not None else self._shift + sum_mean / n_chains, mean_of_covs)
         # A chain of the statistic is a GROUP of `gsz` walkers: the variance of its mean is
         # 1/gsz of a single walker's.  Expressed per walker (x gsz), R-1 keeps the reference's
         # meaning -- roughly one over the number of independent samples EACH chain has drawn

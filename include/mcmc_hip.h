@@ -439,6 +439,45 @@ MCMC_HIP_API int mcmc_hip_bestfit_set(mcmc_hip_ctx* h, const uint64_t* slab, int
 MCMC_HIP_API int mcmc_hip_bestfit_layout(const mcmc_hip_ctx* h, int32_t* on, int32_t* n, int32_t* bins,
                             int32_t* quantity, int64_t* n_slab, int64_t* n_records);
 
+/* Evidence of the run: the sums of the ellipsoid-truncated harmonic mean (evidence_kernels.hip).
+ * The rule ("Evidence").  An ellipsoid is m[d] | Linv[d][d] (row-major, lower
+ * triangular, the inverse of chol(C) formed on the host) | c, n_ell = d + d d + 1 doubles; c is
+ * taken ON THE DEVICE when the ellipsoid becomes active: the exact maximum of logpost over this
+ * process's walkers (0 if none is a number).  An accumulation reads x and logpost as the state
+ * holds them between two launches; per walker s = |Linv (x - m)|^2 (every sum one ascending chain
+ * from +0.0, products and additions rounded separately) and e = dexp(min(c - logpost, 700)); per
+ * group g of group_size walkers and radius r, S = the sum of e over the walkers with s <= r2[r] in
+ * ascending order from +0.0, then acc[g][r] = acc[g][r] + S and cnt[g][r] += the walkers inside;
+ * `clamped` counts the arguments above 700.
+ * configure: n_radii in 1..8 ascending finite positive r2 (n_radii = 0 frees everything: off),
+ * d <= 256; empties everything, no ellipsoid is active.
+ * set_ellipsoid: the FIRST one after configure becomes active at once (a state is needed); a later
+ * one is only staged (replacing an earlier staged one) and becomes active, with a fresh c, in
+ * stream order inside the next closing request.  MCMC_HIP_ERR_NOT_PD if cov has no Cholesky factor.
+ * request(close): queue the read-out of sums, counts, clamped and c behind the work already in
+ * the stream, with the ellipsoids as they are now; close != 0 also zeroes sums, counts and clamped
+ * and activates a staged ellipsoid, all in stream order (close = 0 disturbs nothing).  One request
+ * may be pending.
+ * fetch: waits for that copy only.  sums / counts [n = G n_radii]; active / staged [n_ell] each (c of
+ * the staged one is 0), *has_active / *has_staged say which exist.
+ * set: an unfinished interval goes back (resume): active with its c (NULL: none), staged (NULL:
+ * none); no maximum is taken.
+ * Before configure, accumulate / request / set / set_ellipsoid answer MCMC_HIP_ERR_STATE and
+ * nothing is allocated or launched.  layout: any pointer may be NULL; all zero: off. */
+MCMC_HIP_API int mcmc_hip_evidence_configure(mcmc_hip_ctx* h, int32_t n_radii, const double* r2);
+MCMC_HIP_API int mcmc_hip_evidence_set_ellipsoid(mcmc_hip_ctx* h, const double* m, const double* cov);
+MCMC_HIP_API int mcmc_hip_evidence_accumulate(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_evidence_request(mcmc_hip_ctx* h, int32_t close);
+MCMC_HIP_API int mcmc_hip_evidence_fetch(mcmc_hip_ctx* h, double* sums, uint64_t* counts, int64_t n,
+                            uint64_t* clamped, int64_t* n_accumulations, double* active, double* staged,
+                            int64_t n_ell, int32_t* has_active, int32_t* has_staged);
+MCMC_HIP_API int mcmc_hip_evidence_set(mcmc_hip_ctx* h, const double* sums, const uint64_t* counts, int64_t n,
+                          uint64_t clamped, int64_t n_accumulations, const double* active,
+                          const double* staged, int64_t n_ell);
+MCMC_HIP_API int mcmc_hip_evidence_layout(const mcmc_hip_ctx* h, int32_t* on, int32_t* n_radii, int32_t* n_groups,
+                             int64_t* n_ell, int32_t* has_active, int32_t* has_staged,
+                             int64_t* n_accumulations);
+
 /* The learn / convergence checkpoint ON THE DEVICE (MCMC.check_convergence_and_learn_proposal,
  * mcmc.py:773-1032; checkpoint_kernels.hip): the intervals between checkpoints are kept in a
  * device ring, the statistics of the window (the later half of the run, mcmc.py:787-790) are

@@ -59,6 +59,7 @@ else:
         marginals: bool | dict | None = HIP_DEFAULTS["marginals"]
         autocorr: bool | dict | None = HIP_DEFAULTS["autocorr"]
         bestfit: bool | dict | None = HIP_DEFAULTS["bestfit"]
+        evidence: bool | dict | None = HIP_DEFAULTS["evidence"]
 
         def _export_collection(self, coll):
             """Our table -> `cobaya.collection.SampleCollection` (same columns,
@@ -90,6 +91,8 @@ else:
                 regexps.append((re.compile(output.prefix_regexp_str + r"autocorr\.npz$"), None))
                 # the records and profiles of `bestfit` (written once, at the end of the run)
                 regexps.append((re.compile(output.prefix_regexp_str + r"bestfit\.npz$"), None))
+                # ln Z and its sums of `evidence` (written once, at the end of the run)
+                regexps.append((re.compile(output.prefix_regexp_str + r"evidence\.npz$"), None))
             return regexps
 
 
