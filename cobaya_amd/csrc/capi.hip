@@ -402,6 +402,10 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     if (h->evd.pin) (void)hipHostFree(h->evd.pin);
     if (h->evd.pin_ell) (void)hipHostFree(h->evd.pin_ell);
     if (h->evd.ev) (void)hipEventDestroy(h->evd.ev);
+    h->dv.z.release(); h->dv.Sg.release(); h->dv.shift.release(); h->dv.Ng.release(); h->dv.slab.release();
+    h->dv.cross.release();
+    if (h->dv.pin) (void)hipHostFree(h->dv.pin);
+    if (h->dv.ev) (void)hipEventDestroy(h->dv.ev);
     if (h->ck.ev) (void)hipEventDestroy(h->ck.ev);
     if (h->pin_mom) (void)hipHostFree(h->pin_mom);
     if (h->pin_T) (void)hipHostFree(h->pin_T);

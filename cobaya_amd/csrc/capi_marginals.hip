@@ -45,7 +45,7 @@ int mcmc_hip_marginals_configure(mcmc_hip_ctx* h, int32_t n1, const int32_t* dim
         return fail(h, MCMC_HIP_ERR_ARG, "bins1 = %d must lie in 1..%d", bins1, mcmc::kMargMaxBins1);
     if (n2 > 0 && (bins2 < 1 || bins2 > mcmc::kMargMaxBins2))
         return fail(h, MCMC_HIP_ERR_ARG, "bins2 = %d must lie in 1..%d", bins2, mcmc::kMargMaxBins2);
-    const int d = h->d;
+    const int d = h->d + h->dv.m;   // (the derived rows follow the sampled parameters)
     auto range_ok = [&](int i, int B, const char* what, int k) {
         if (!(std::isfinite(lo[i]) && std::isfinite(hi[i]) && lo[i] < hi[i]))
             return fail(h, MCMC_HIP_ERR_ARG, "lo / hi of parameter %d (%s[%d]): [%g, %g] is not a finite range with lo < hi",
@@ -126,7 +126,7 @@ int mcmc_hip_marginals_accumulate(mcmc_hip_ctx* h)
     if (!h->have_state) return fail(h, MCMC_HIP_ERR_STATE, "no state");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     mcmc::MargArgs a{};
-    a.x = h->x.p; a.entries = M.entries.p; a.slab = M.slab.p; a.W = h->W; a.n_entries = M.n_entries;
+    a.x = h->x.p; a.z = h->dv.z.p; a.d = h->d; a.entries = M.entries.p; a.slab = M.slab.p; a.W = h->W; a.n_entries = M.n_entries;
     // a slice of 4096 walkers (16 per thread) amortises the flush of the LDS histogram; with few
     // entries the slices shrink (to 1024) so that the launch still spreads over the chip.  The
     // counts do not depend on it.

@@ -25,6 +25,7 @@
 #include "autocorr_args.h"
 #include "bestfit_args.h"
 #include "evidence_args.h"
+#include "derived_args.h"
 #include "comm.h"
 #include "inc_choice.h"
 
@@ -324,6 +325,23 @@ struct mcmc_hip_ctx {
         hipEvent_t ev = nullptr;
         bool pending = false;
     } evd;
+    // derived parameters (mcmc_hip_derived_*; derived_kernels.hip): the rows z[m][W] the caller fills
+    // on the engine's stream, this accumulation's group chains, and the slab of 64-bit words
+    // N | S[m][n_col] doubles | bad[m] | kmax[m] | kmin[m] (derived_args.h) with its pinned read-out
+    struct Derived {
+        DevBuf<double> z, Sg, shift;           // [m][W], [G][m][n_col], [m]
+        DevBuf<unsigned long long> Ng, slab;   // [G], [n_words]
+        DevBuf<int> cross;                     // [n_cross]
+        unsigned long long* pin = nullptr;     // [n_words]
+        size_t n_words = 0;
+        int m = 0, n_cross = 0, n_col = 0;
+        int gs = 0, G = 0;                     // the groups of the sums (default: the engine's)
+        bool on = false;
+        int64_t n_acc = 0;                     // accumulations since the last request / set
+        int64_t pend_n = 0;                    // ... of the pending read-out
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+    } dv;
     // the walker shards' communicator (comm.hip; not owned): the device checkpoint all-reduces
     // its payload over it in stream order
     mcmc_hip_comm* comm = nullptr;

@@ -16,16 +16,18 @@ struct MargEntry {
     double lo_i, hi_i, s_i;
     double lo_j, hi_j, s_j;
     long long offset;      // of the entry's first counter in the slab
-    int i, j;              // sampler indices; j < 0: a 1-D entry
+    int i, j;              // sampler indices -- d + r: row r of the derived rows z; j < 0: a 1-D entry
     int B;                 // bins (per axis)
     int pad_;
 };
 
 struct MargArgs {
     const double* x;               // the ensemble's state, dimension-major [d][W]
+    const double* z;               // the derived rows [m][W] (derived_kernels.hip); null: none
     const MargEntry* entries;      // [n_entries]
     unsigned long long* slab;      // the counters of every entry
     int W;
+    int d;                         // an entry's index i >= d reads row i - d of z
     int n_entries;
     int slice;                     // walkers one workgroup bins (a multiple of kMargThreads)
     int n_slices;                  // ceil(W / slice)

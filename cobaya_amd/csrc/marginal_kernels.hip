@@ -4,6 +4,8 @@
 // k = min((int)floor((x - lo) * s), B - 1) with s = B / (hi - lo) formed on the host -- the
 // subtraction and the product are separate roundings (-ffp-contract=off).  Counters are uint64 in
 // global memory, so the statistic does not depend on the order of the atomics or on the launch.
+// An entry whose index is d + r reads row r of the derived rows z[m][W] instead of x.  A NaN compares
+// false with everything: in a 1-D entry it is counted nowhere, in a pair it is counted `outside`.
 //
 //   marginals_kernel   one workgroup per (entry, slice of walkers): the slice's row(s) of x are read
 //                      coalesced, binned into a uint32 histogram in LDS with LDS integer atomics,
@@ -44,8 +46,10 @@ __global__ void __launch_bounds__(kMargThreads) marginals_kernel(const MargArgs 
 
     const int w0 = sl * a.slice;
     const int w1 = min(w0 + a.slice, a.W);
-    const double* __restrict__ xi = a.x + (size_t)E.i * a.W;
-    const double* __restrict__ xj = a.x + (size_t)(pair ? E.j : E.i) * a.W;
+    // (an index from d up is a derived row; below d the entry reads x as it always did)
+    const int ej = pair ? E.j : E.i;
+    const double* __restrict__ xi = E.i < a.d ? a.x + (size_t)E.i * a.W : a.z + (size_t)(E.i - a.d) * a.W;
+    const double* __restrict__ xj = ej < a.d ? a.x + (size_t)ej * a.W : a.z + (size_t)(ej - a.d) * a.W;
     for (int wb = w0 + (int)threadIdx.x; wb < w1; wb += kMargThreads * kUnroll) {
         double vi[kUnroll], vj[kUnroll];
 #pragma unroll

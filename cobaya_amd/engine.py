@@ -176,6 +176,18 @@ SYMBOLS = [
                                            c_int32_p, c_int64_p]),
     ("mcmc_hip_bestfit_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p,
                                           c_int64_p]),
+    ("mcmc_hip_derived_configure", C.c_int, [_H, C.c_int32, C.c_int32, c_int32_p, c_double_p]),
+    ("mcmc_hip_derived_set_group_size", C.c_int, [_H, C.c_int32]),
+    ("mcmc_hip_derived_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p, c_int64_p]),
+    ("mcmc_hip_derived_buffers", C.c_int, [_H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("mcmc_hip_derived_set_values", C.c_int, [_H, c_double_p]),
+    ("mcmc_hip_derived_get_values", C.c_int, [_H, c_double_p]),
+    ("mcmc_hip_derived_accumulate", C.c_int, [_H]),
+    ("mcmc_hip_derived_request", C.c_int, [_H]),
+    ("mcmc_hip_derived_fetch", C.c_int, [_H, c_uint64_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                         c_double_p, c_uint64_p, c_double_p, c_double_p, c_int64_p]),
+    ("mcmc_hip_derived_set", C.c_int, [_H, C.c_uint64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                       c_double_p, c_uint64_p, c_double_p, c_double_p, C.c_int64]),
     ("mcmc_hip_gelman_rubin", C.c_int, [C.c_int32, C.c_double, C.c_double, c_double_p,
                                         c_double_p, c_double_p, c_double_p, c_double_p]),
     ("mcmc_hip_enable_timing", C.c_int, [_H, C.c_int32]),
@@ -432,6 +444,7 @@ class Engine:
 
     _fn_exc = None
     _fn_callback = None
+    n_derived = n_derived_cross = 0    # (configure_derived)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -825,12 +838,15 @@ class Engine:
     def configure_marginals(self, dims1=(), bins1=128, pairs=(), bins2=32, lo=None, hi=None):
         """The histograms every `accumulate_marginals` adds the ensemble to (mcmc_hip_marginals_configure):
         `dims1` sampler indices with `bins1` bins each, `pairs` ordered (i, j) with `bins2` x `bins2`
-        bins each, `lo` / `hi` [d] the fixed range of every parameter in use.  Nothing listed: off."""
+        bins each, `lo` / `hi` [d] the fixed range of every parameter in use.  Nothing listed: off.
+        With m derived rows configured an index d + r names row r of them, and `lo` / `hi` hold
+        d + m entries."""
         dims1 = np.ascontiguousarray(dims1, dtype=np.int32).reshape(-1)
         pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         n1, n2 = len(dims1), len(pairs)
-        lo = _f64(lo, (self.d,)) if (n1 or n2) else None
-        hi = _f64(hi, (self.d,)) if (n1 or n2) else None
+        n = self.d + self.n_derived     # (indices from d up name the derived rows: configure_derived first)
+        lo = _f64(lo, (n,)) if (n1 or n2) else None
+        hi = _f64(hi, (n,)) if (n1 or n2) else None
         self._check(self._lib.mcmc_hip_marginals_configure(
             self._h, n1, _ip(dims1) if n1 else None, int(bins1), n2, _ip(pairs) if n2 else None,
             int(bins2), _dp(lo) if lo is not None else None, _dp(hi) if hi is not None else None))
@@ -868,6 +884,103 @@ class Engine:
         c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
         self._check(self._lib.mcmc_hip_marginals_set(self._h, c.ctypes.data_as(c_uint64_p), len(c),
                                                      int(n_accumulations)))
+
+    # -- derived parameters
+    def configure_derived(self, m, cross_dims=(), shift=None):
+        """`m` derived rows z[m][W] and their moments (mcmc_hip_derived_configure): `cross_dims` the
+        sampler indices whose cross-moments are kept, `shift` [m] the conditioning vector (default
+        zeros).  m = 0: off.  Before `configure_marginals`, whose indices d .. d + m - 1 name the rows."""
+        m = int(m)
+        cross = np.ascontiguousarray(cross_dims, dtype=np.int32).reshape(-1)
+        sh = _f64(np.zeros(m) if shift is None else shift, (m,))
+        self._check(self._lib.mcmc_hip_derived_configure(self._h, m, len(cross), _ip(cross) if len(cross) else None,
+                                                         _dp(sh) if m else None))
+        self.n_derived, self.n_derived_cross = m, (len(cross) if m else 0)
+        self._derived_views = None
+
+    def derived_set_group_size(self, group_size):
+        """The groups of the derived sums (default: the engine's group_size): any divisor of W."""
+        self._check(self._lib.mcmc_hip_derived_set_group_size(self._h, int(group_size)))
+
+    def derived_layout(self):
+        """{"m", "n_cross", "group_size", "n_accumulations"} (mcmc_hip_derived_layout); m == 0: off."""
+        v = [C.c_int32() for _ in range(3)]
+        n = C.c_int64()
+        self._check(self._lib.mcmc_hip_derived_layout(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]),
+                                                      C.byref(n)))
+        return {"m": v[0].value, "n_cross": v[1].value, "group_size": v[2].value, "n_accumulations": n.value}
+
+    def derived_buffers(self):
+        """(device pointer of x[d][W], of z[m][W]): what a caller fills z from, on `stream_handle()`."""
+        x, z = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.mcmc_hip_derived_buffers(self._h, C.byref(x), C.byref(z)))
+        return x.value, z.value
+
+    def derived_row_views(self):
+        """(x rows, z rows, stream): zero-copy torch.float64 views of the d rows of x[d][W] and the m
+        rows of z[m][W], each of shape (W,), and the engine's stream as a `torch.cuda.ExternalStream`.
+        The views of x are for reading.  `import torch` before the first Engine is created."""
+        if getattr(self, "_derived_views", None) is None:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            try:
+                stream = torch.cuda.ExternalStream(self.stream_handle(), device=dev)
+            except RuntimeError as e:
+                raise EngineError(ERR_DEVICE,
+                                  f"PyTorch cannot use device {dev} in this process ({e}): `import torch` "
+                                  "before the first Engine is created (before libmcmc_hip.so is loaded), so "
+                                  "that both use one HIP runtime") from e
+            xp, zp = self.derived_buffers()
+
+            class _View:   # __cuda_array_interface__ of float64 at a device pointer: no copy
+                def __init__(self, ptr, shape):
+                    self.__cuda_array_interface__ = {"shape": shape, "typestr": "<f8", "data": (ptr, False),
+                                                     "version": 2, "strides": None}
+
+            x = torch.as_tensor(_View(xp, (self.d, self.W)), device=dev)
+            z = torch.as_tensor(_View(zp, (self.n_derived, self.W)), device=dev)
+            self._derived_views = (list(x.unbind(0)), list(z.unbind(0)), stream)
+        return self._derived_views
+
+    def derived_set_values(self, values):
+        """z from the host, point-major [W][m]."""
+        v = _f64(values, (self.W, self.n_derived))
+        self._check(self._lib.mcmc_hip_derived_set_values(self._h, _dp(v)))
+
+    def derived_get_values(self):
+        """z as it lies on the device (the stream is waited for), point-major [W][m]."""
+        v = np.empty((self.W, self.n_derived))
+        self._check(self._lib.mcmc_hip_derived_get_values(self._h, _dp(v)))
+        return v
+
+    def accumulate_derived(self):
+        """Queue one accumulation of the moments of z as it is (two launches)."""
+        self._check(self._lib.mcmc_hip_derived_accumulate(self._h))
+
+    def request_derived(self):
+        """Queue the read-out and the reset of the accumulators behind the work already in the stream."""
+        self._check(self._lib.mcmc_hip_derived_request(self._h))
+
+    def fetch_derived(self):
+        """{"N", "A"[m], "B"[m (m + 1) / 2], "C"[m, n_cross], "X"[n_cross], "V"[n_cross], "bad"[m], "min"[m], "max"[m],
+        "n"} of the pending request; waits for its copy only."""
+        m, nc = self.n_derived, self.n_derived_cross
+        N, n = C.c_uint64(), C.c_int64()
+        A, B, Cc, X, V = np.zeros(m), np.zeros(m * (m + 1) // 2), np.zeros((m, nc)), np.zeros(nc), np.zeros(nc)
+        bad, mn, mx = np.zeros(m, np.uint64), np.zeros(m), np.zeros(m)
+        self._check(self._lib.mcmc_hip_derived_fetch(self._h, C.byref(N), _dp(A), _dp(B), _dp(Cc) if nc else None,
+                                                     _dp(X) if nc else None, _dp(V) if nc else None, bad.ctypes.data_as(c_uint64_p), _dp(mn), _dp(mx), C.byref(n)))
+        return {"N": int(N.value), "A": A, "B": B, "C": Cc, "X": X, "V": V, "bad": bad, "min": mn, "max": mx, "n": int(n.value)}
+
+    def derived_set(self, part):
+        """Restore the accumulators of an unfinished interval (resume): what `fetch_derived` returns."""
+        m, nc = self.n_derived, self.n_derived_cross
+        A, B = _f64(part["A"], (m,)), _f64(part["B"], (m * (m + 1) // 2,))
+        Cc, X, V = _f64(part["C"], (m, nc)), _f64(part["X"], (nc,)), _f64(part["V"], (nc,))
+        bad = np.ascontiguousarray(part["bad"], dtype=np.uint64).reshape(m)
+        mn, mx = _f64(part["min"], (m,)), _f64(part["max"], (m,))
+        self._check(self._lib.mcmc_hip_derived_set(self._h, int(part["N"]), _dp(A), _dp(B), _dp(Cc) if nc else None,
+                                                   _dp(X) if nc else None, _dp(V) if nc else None, bad.ctypes.data_as(c_uint64_p), _dp(mn), _dp(mx), int(part["n"])))
 
     # -- lagged cross-products for the autocorrelation time
     def configure_autocorr(self, dims=(), lags=16):

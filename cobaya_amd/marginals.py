@@ -7,6 +7,11 @@ walker of every moment snapshot of the window -- not only the rows `max_rows` re
 ("Marginals"): on an axis of B bins over [lo, hi] a value is in range iff
 lo <= x <= hi and falls in bin min(floor((x - lo) * s), B - 1) with s = B / (hi - lo); x == hi
 falls in the last bin, a value on an interior edge in the upper one.
+
+Function-derived parameters (`cobaya_amd.derived`) are histogrammed like sampled ones, from the rows
+the engine keeps of them; each needs an explicit `ranges` entry (it has no prior).  Only they can be
+NaN: a NaN compares false with everything, so in a 1-D entry it is counted NOWHERE (neither in a bin
+nor under nor over), and in a pair it is counted `outside`.
 """
 from __future__ import annotations
 
@@ -187,15 +192,18 @@ class Marginals:
 
 
 # ---------------------------------------------------------------------------------- the option
-def parse_option(opt, sampled):
+def parse_option(opt, sampled, derived=()):
     """The sampler option `marginals` -> None (off) or a dict
     {"params": [names], "pairs": [(a, b)], "bins", "bins2d", "ranges": dict | "prior" | "covmat"}.
     `True` = every sampled parameter in 1-D, no pairs.  Refuses, by the option's name, unknown
     keys and parameter names, pairs of one parameter, bin counts out of range and a slab above
-    64 MiB."""
+    64 MiB.  `derived`: the names of function-derived parameters, which `params`, `pairs` and
+    `ranges` may list beside the sampled ones ("all" stays the sampled ones); each needs an explicit
+    `ranges` entry."""
     if opt is None or opt is False:
         return None
-    sampled = list(sampled)
+    sampled, derived = list(sampled), [str(n) for n in derived]
+    known = sampled + derived
     if opt is True:
         opt = {"params": "all"}
     if not isinstance(opt, dict):
@@ -219,8 +227,8 @@ def parse_option(opt, sampled):
         if isinstance(pr, str) or len(pr) != 2:
             raise MarginalsError(f"marginals: pairs holds [a, b] entries, got {pr!r}")
         out_pairs.append((str(pr[0]), str(pr[1])))
-    bad = sorted({n for n in params if n not in sampled}
-                 | {n for pr in out_pairs for n in pr if n not in sampled})
+    bad = sorted({n for n in params if n not in known}
+                 | {n for pr in out_pairs for n in pr if n not in known})
     if bad:
         raise MarginalsError(f"marginals: unknown parameter name(s) {bad}; the sampled parameters "
                              f"are {sampled}")
@@ -247,7 +255,7 @@ def parse_option(opt, sampled):
         if ranges not in ("prior", "covmat"):
             raise MarginalsError(f"marginals: ranges must be a dict, 'prior' or 'covmat', got {ranges!r}")
     elif isinstance(ranges, dict):
-        bad = sorted(str(n) for n in ranges if n not in sampled)
+        bad = sorted(str(n) for n in ranges if n not in known)
         if bad:
             raise MarginalsError(f"marginals: ranges names unknown parameter(s) {bad}")
         clean = {}
@@ -264,6 +272,11 @@ def parse_option(opt, sampled):
         ranges = clean
     else:
         raise MarginalsError(f"marginals: ranges must be a dict, 'prior' or 'covmat', got {ranges!r}")
+    in_use = params + [n for pr in out_pairs for n in pr]
+    unranged = sorted({n for n in in_use if n in derived and not (isinstance(ranges, dict) and n in ranges)})
+    if unranged:
+        raise MarginalsError(f"marginals: derived parameter(s) {unranged} need an explicit ranges entry "
+                             "(ranges: {name: [lo, hi]}): a derived parameter has no prior")
     return {"params": params, "pairs": out_pairs, "bins": bins, "bins2d": bins2d, "ranges": ranges}
 
 
@@ -282,6 +295,9 @@ def resolve_ranges(cfg, spec, centre=None, covmat=None):
         if n in explicit:
             out[n] = explicit[n]
             continue
+        if n not in spec.sampled:
+            raise MarginalsError(f"marginals: derived parameter {n!r} needs an explicit ranges entry: it "
+                                 "has no prior")
         i = spec.sampled.index(n)
         uniform = int(spec.kinds[i]) == 0
         a, b = float(spec.a[i]), float(spec.b[i])
@@ -345,7 +361,7 @@ class MarginalsAccumulator:
     @classmethod
     def from_option(cls, opt, spec, engine_factory, host):
         try:
-            cfg = parse_option(opt, spec.sampled)
+            cfg = parse_option(opt, spec.sampled, [f.name for f in getattr(spec, "derived_functions", ())])
         except MarginalsError as e:
             host.fail("%s", str(e), cause=e)
         if cfg is None:
@@ -373,9 +389,12 @@ class MarginalsAccumulator:
         self._configure(ranges)
 
     def _configure(self, ranges):
-        cfg, fail, ix = self.cfg, self.host.fail, self.spec.sampled.index
+        cfg, fail = self.cfg, self.host.fail
+        # (the rows of the function-derived parameters follow the sampled ones: index d + r)
+        names = list(self.spec.sampled) + [f.name for f in getattr(self.spec, "derived_functions", ())]
+        ix = names.index
         cfg["resolved"] = dict(ranges)
-        lo, hi = np.full(self.spec.d, np.nan), np.full(self.spec.d, np.nan)
+        lo, hi = np.full(len(names), np.nan), np.full(len(names), np.nan)
         for n, (a, b) in cfg["resolved"].items():
             lo[ix(n)], hi[ix(n)] = a, b
         try:

@@ -16,6 +16,8 @@ Reference behaviour mirrored here (paths relative to the reference checkout):
   gaussian / one           cobaya/likelihoods/gaussian/gaussian.py:30-112 ; likelihoods/one/one.py
   device_function          cobaya/likelihood.py:150-255 (LikelihoodExternalFunction), batched: the
                            function maps an (n, d) device tensor of points to n log-likelihoods
+  derived functions        cobaya/parameterization.py (`derived: "lambda a, b: ..."`), batched: every
+                           argument is a (n,) device tensor, one entry per walker (`DerivedFunction`)
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ import numpy as np
 
 
 OVERHEAD_TIME = 0.0003  # conventions.py:141
+MAX_DERIVED_FUNCTIONS = 32  # derived_args.h: kDvMaxNames
 
 
 def sort_parameter_blocks(blocks, speeds, footprints, oversample_power=0.0):
@@ -111,6 +114,70 @@ def _parse_1d(info, what, allow_number=False):
 
 
 @dataclass
+class DerivedFunction:
+    """A function-derived parameter: `function(*args)` with every argument bound to a 1-D
+    torch.float64 tensor of length n on the engine's device -- a zero-copy view of a row of the
+    dimension-major state x[d][W], or of an earlier derived row -- returns the (n,) float64 values
+    on that device.  It must be ELEMENTWISE in the walker index: entry l of the result depends on
+    entry l of the arguments only (this is not checked).  `args`: names of sampled parameters, or of
+    function-derived parameters defined earlier in `params`.  `source`: what the input gave."""
+    name: str
+    function: object
+    args: list
+    source: object = None
+
+
+def parse_derived_function(name, source):
+    """The `derived` entry of a parameter -> `DerivedFunction` (its argument names unchecked): a
+    callable, a "package.module:name" string, or a "lambda a, b: ..." string evaluated with `torch`
+    and `math` in its namespace (the precedent: `device_function`'s `function`)."""
+    import inspect
+    fn = source
+    if isinstance(fn, str):
+        text = fn.strip()
+        if text.startswith("lambda"):
+            import math
+            try:
+                import torch
+            except ImportError as e:
+                raise UnsupportedModel(f"parameter '{name}': a derived function needs PyTorch: it "
+                                       f"receives and returns torch tensors ({e})") from e
+            try:
+                fn = eval(text, {"torch": torch, "math": math})  # noqa: S307
+            except Exception as e:   # (whatever the text raises)
+                raise UnsupportedModel(f"parameter '{name}': the derived function {source!r} could "
+                                       f"not be evaluated ({type(e).__name__}: {e})") from e
+        else:
+            import importlib
+            mod, sep, attr = text.partition(":")
+            if not sep or not mod or not attr:
+                raise UnsupportedModel(f"parameter '{name}': a derived function given as a string must "
+                                       f"be 'lambda ...: ...' or 'package.module:name', got {source!r}")
+            try:
+                fn = importlib.import_module(mod)
+                for part in attr.split("."):
+                    fn = getattr(fn, part)
+            except (ImportError, AttributeError) as e:
+                raise UnsupportedModel(f"parameter '{name}': the derived function {source!r} could "
+                                       f"not be resolved ({e})") from e
+    if not callable(fn):
+        raise UnsupportedModel(f"parameter '{name}': `derived` must be a callable, a 'lambda ...' string "
+                               f"or a 'package.module:name' string, got {source!r}")
+    try:
+        sig = inspect.signature(fn)
+    except (TypeError, ValueError) as e:
+        raise UnsupportedModel(f"parameter '{name}': the arguments of the derived function cannot be "
+                               f"read ({e})") from e
+    args = []
+    for a in sig.parameters.values():
+        if a.kind in (a.VAR_POSITIONAL, a.VAR_KEYWORD):
+            raise UnsupportedModel(f"parameter '{name}': the derived function takes *{a.name}: its "
+                                   "arguments must be named after parameters")
+        args.append(a.name)
+    return DerivedFunction(name, fn, args, source)
+
+
+@dataclass
 class ProblemSpec:
     sampled: list  # parameter names in info order (= sampler order, mcmc.py:392-393)
     derived: list
@@ -136,6 +203,13 @@ class ProblemSpec:
     calib_index: int = -1
     # device_function: the batched callable (points (n, d) on the device -> (n,) log-likelihoods)
     function: object = None
+    # function-derived parameters, in `params` order (`DerivedFunction`); never beside `derived`
+    derived_functions: list = field(default_factory=list)
+
+    @property
+    def derived_names(self):
+        """The derived columns of a stored row, in `params` order."""
+        return list(self.derived) + [f.name for f in self.derived_functions]
 
     @property
     def d(self):
@@ -195,10 +269,12 @@ class ProblemSpec:
 
     # ----------------------------------------------------------------- construction
     @classmethod
-    def _from_params(cls, params):
+    def _from_params(cls, params, functions=True):
         """The `params` block -> a spec without likelihoods (parameterization.py: sampled =
-        has `prior`; derived = neither prior nor value)."""
-        sampled, derived, fixed = [], [], {}
+        has `prior`; derived = neither prior nor value).  A derived parameter given as a function
+        becomes a `DerivedFunction` (`functions=False`, the hosted path, where Cobaya's Model
+        owns them: refused)."""
+        sampled, derived, fixed, fderived = [], [], {}, []
         kinds, a, b, per, refs, props, labels = [], [], [], [], [], [], {}
         for name, p in (params or {}).items():
             if isinstance(p, numbers.Real):
@@ -217,7 +293,11 @@ class ProblemSpec:
             if p.get("latex"):
                 labels[name] = p["latex"]
             if p.get("prior") is None:
-                if p.get("derived", True) is not True:
+                how = p.get("derived", True)
+                if (isinstance(how, str) or callable(how)) and functions:
+                    fderived.append(parse_derived_function(name, how))
+                    continue
+                if how is not True:
                     raise UnsupportedModel(f"parameter '{name}': derived functions are not "
                                            "supported")
                 derived.append(name)
@@ -242,8 +322,19 @@ class ProblemSpec:
                                    "the analytic likelihoods handled here")
         if not sampled:
             raise UnsupportedModel("No parameters being varied for sampler")
+        if len(fderived) > MAX_DERIVED_FUNCTIONS:
+            raise UnsupportedModel(f"{len(fderived)} derived parameters are given as functions: mcmc_hip "
+                                   f"evaluates at most {MAX_DERIVED_FUNCTIONS}")
+        for k, f in enumerate(fderived):
+            known = sampled + [g.name for g in fderived[:k]]
+            unknown = [arg for arg in f.args if arg not in known]
+            if unknown:
+                raise UnsupportedModel(
+                    f"parameter '{f.name}': the derived function takes {unknown}, which "
+                    f"{'is' if len(unknown) == 1 else 'are'} neither a sampled parameter nor a derived "
+                    f"function defined earlier in `params` (known: {known})")
         return cls(sampled, derived, np.array(kinds), np.array(a, float), np.array(b, float),
-                   np.array(per), refs, props, labels=labels)
+                   np.array(per), refs, props, labels=labels, derived_functions=fderived)
 
     @classmethod
     def from_info(cls, info):
@@ -259,7 +350,13 @@ class ProblemSpec:
             raise UnsupportedModel("no likelihood given (use `one` for prior-only sampling)")
         comps = [cls._parse_likelihood(lname, linfo, sampled, derived, single=len(likes) == 1)
                  for lname, linfo in likes.items()]
-        return spec._with_components(comps)
+        spec = spec._with_components(comps)
+        if spec.derived_functions and spec.derived:
+            raise UnsupportedModel(
+                f"the derived functions {[f.name for f in spec.derived_functions]} cannot stand beside "
+                f"the derived parameters {list(spec.derived)} of `gaussian_mixture: {{derived: True}}`: "
+                "one kind of derived parameter per model")
+        return spec
 
     def _with_components(self, comps):
         """Attach the parsed likelihoods: one is taken as it is, several are merged."""
@@ -666,7 +763,7 @@ class ProblemSpec:
                                    "and cannot run on the device")
         if len(getattr(model, "theory", None) or {}):
             raise UnsupportedModel("theory codes are out of scope for mcmc_hip")
-        spec = cls._from_params(info["params"])
+        spec = cls._from_params(info["params"], functions=False)
         live = list(model.parameterization.sampled_params())
         if live != spec.sampled:
             raise UnsupportedModel(f"sampled parameters of the model {live} differ from the "

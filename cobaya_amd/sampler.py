@@ -39,6 +39,7 @@ from .autocorr import AutoCorrAccumulator
 from .bestfit import BestFitAccumulator
 from .bounds_ring import BoundsRing
 from .collection import SampleCollection
+from .derived import DerivedAccumulator
 from .engine import (ChainStuck, Engine, EngineError, NotPositiveDefinite, gelman_rubin,
                      incremental_supported)
 from .evidence import EvidenceAccumulator
@@ -177,6 +178,15 @@ HIP_DEFAULTS = {
                               # lnZ_by_radius(), clipped(), ...).  None: off.  True: the ladder
                               # R^2 = (0.5, 0.75, 1, 1.5, 2) d.  Or {"radii": [1..8 ascending
                               # positive f_r], "every": 1}.  Needs temperature: 1
+    "derived_stats": None,    # moments of the function-derived parameters (`params: {s: {derived: "lambda
+                              # a, b: a + b"}}`: batched device functions of the sampled ones, evaluated
+                              # on the engine's stream and written into the stored rows), summed on the
+                              # device from EVERY walker of every moment snapshot of the window --
+                              # products()["derived"], a `cobaya_amd.derived.Derived` (mean, cov, std,
+                              # cross_cov, corr, min, max, nonfinite).  None: {"cross": "all"} when such
+                              # parameters exist.  {"cross": [names] | "all" | None}: the sampled
+                              # parameters whose cross-moments are kept.  False: no moment kernel (rows
+                              # and marginals still get their values).  Needs temperature: 1
     "shared_basis": True,     # True: the walkers of a group share one Haar basis per cycle;
                               # False: every walker draws its own (proposal.py:59-69 to the
                               # letter: the reference-faithful control, much slower)
@@ -257,11 +267,15 @@ class EnsembleMCMC:
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
     MAX_DIM = 128    # ctx.h: kMaxDimBig, every path (mixtures: at most 64 modes, model.py)
     HUGE_MAX_MODES = 4   # 128 < d <= max_dim(): huge_kernels.hip (huge_args.h: kHugeMaxModes)
-    marginals = autocorr = bestfit = evidence = None     # (the options' default: off)
+    marginals = autocorr = bestfit = evidence = derived_stats = None     # (the options' default)
     # What is accumulated on the device beside every moment snapshot (marginals.py states the
     # methods): a new product is one such class, appended here.  `_products`: those that are on
-    PRODUCT_CLASSES = (MarginalsAccumulator, AutoCorrAccumulator, BestFitAccumulator, EvidenceAccumulator)
+    # (DerivedAccumulator FIRST: it configures the derived rows before the marginals that may read
+    # them, and fills them before those are binned)
+    PRODUCT_CLASSES = (DerivedAccumulator, MarginalsAccumulator, AutoCorrAccumulator, BestFitAccumulator,
+                       EvidenceAccumulator)
     _products = ()
+    _derived = None      # the DerivedAccumulator, where the model has function-derived parameters
 
     def _max_dim(self):
         """The cap of the engine behind the seam: its max_dim() where it has one, else 128 (the
@@ -478,10 +492,12 @@ class EnsembleMCMC:
         # closed is freed with the sampler's last reference, not by the cycle collector)
         host = SimpleNamespace(fail=partial(log_and_raise, self._LoggedError, self.log), n_walkers=W,
                                size=self.size, rank=self.rank, all_reduce_sum=dist.all_reduce_sum, temperature=self.temperature,
+                               emit=self.emit,
                                snapshot_steps=int(self.steps_per_launch) * max(1, int(self.moments_every)))
-        made = [c.from_option(getattr(self, c.name), spec, self._engine_factory, host)
+        made = [c.from_option(getattr(self, getattr(c, "option", c.name)), spec, self._engine_factory, host)
                 for c in self.PRODUCT_CLASSES]
         self._products = [p for p in made if p is not None]
+        self._derived = next((p for p in self._products if isinstance(p, DerivedAccumulator)), None)
         try:
             self.engine = self._engine_factory(d, W, group_size=int(self.group_size), device=int(device),
                                  seed=self.seed, walker_offset=self.rank * W,
@@ -734,7 +750,7 @@ class EnsembleMCMC:
     def _init_bookkeeping(self):
         spec = self.spec
         self.collection = self._export_collection(
-            SampleCollection(spec.sampled, spec.derived, self._like_names(),
+            SampleCollection(spec.sampled, spec.derived_names, self._like_names(),
                              self.temperature, name=str(1 + self.rank)))
         # chains mode with output thinned on the host: added weight per walker (dense, saved in
         # the state file under the key the device-thinned path uses: `thin_carry`)
@@ -915,6 +931,8 @@ class EnsembleMCMC:
         behind the one the checkpoint's processing overlaps."""
         eng, spl = self.engine, self.steps_per_launch
         eng.step(spl)
+        if self._derived is not None:
+            self._derived.stale()
         self.n_steps_raw += spl
         self._launches += 1
         self._since_snapshot += spl
@@ -1304,9 +1322,11 @@ class EnsembleMCMC:
         s = self.engine.get_state()
         W = len(s["x"])
         ids = self.rank * W + np.arange(W, dtype=np.float64)
-        rows = np.column_stack((ids, np.ones(W), s["logpost"], s["logprior"], s["loglike"],
-                                s["x"]))
-        self._store_rows(rows)
+        cols = [ids, np.ones(W), s["logpost"], s["logprior"], s["loglike"], s["x"]]
+        if self._derived is not None:
+            # the function-derived columns of the same state (evaluated now if z is not current)
+            cols.append(self._derived.values())
+        self._store_rows(np.column_stack(cols))
 
     def _update_counters(self):
         c = self.engine.counters()
@@ -1504,18 +1524,22 @@ class EnsembleMCMC:
 
     # ------------------------------------------------------------------ products
     def _table_collection(self, rows):
-        """(walker, weight, logpost, logprior, loglike, x...) rows -> SampleCollection with
-        the derived parameters (device) and the per-likelihood chi2 columns (host) filled."""
+        """(walker, weight, logpost, logprior, loglike, x..., function-derived...) rows ->
+        SampleCollection with the derived parameters (device) and the per-likelihood chi2 columns
+        (host) filled."""
         spec = self.spec
-        coll = SampleCollection(spec.sampled, spec.derived, self._like_names(), self.temperature,
+        coll = SampleCollection(spec.sampled, spec.derived_names, self._like_names(), self.temperature,
                                 name=str(1 + self.rank))
         if len(rows):
+            x = rows[:, 5:5 + spec.d]
             derived = None
             if spec.derived:
-                derived = np.vstack([self.engine.evaluate(rows[i:i + 65536, 5:], derived=True)[2]
+                derived = np.vstack([self.engine.evaluate(x[i:i + 65536], derived=True)[2]
                                      for i in range(0, len(rows), 65536)])
-            parts = (spec.component_loglikes(rows[:, 5:]) if len(spec.components) > 1 else None)
-            coll.add_rows(rows[:, 1], rows[:, 2], rows[:, 5:], rows[:, 3], rows[:, 4], derived,
+            elif spec.derived_functions:   # (they came with the row: `_snapshot`)
+                derived = rows[:, 5 + spec.d:]
+            parts = (spec.component_loglikes(x) if len(spec.components) > 1 else None)
+            coll.add_rows(rows[:, 1], rows[:, 2], x, rows[:, 3], rows[:, 4], derived,
                           parts)
         coll.chain_ids = rows[:, 0].astype(np.int64) if len(rows) else np.zeros(0, np.int64)
         return coll
@@ -1523,7 +1547,7 @@ class EnsembleMCMC:
     def _build_collection(self):
         """All rows this process holds: those of earlier legs (read back from the chain file
         at resume) followed by the ones stored in memory."""
-        d = self.spec.d
+        d = self.spec.d + len(self.spec.derived_functions)
         coll = self._table_collection(np.vstack(self._rows) if self._rows
                                       else np.zeros((0, d + 5)))
         self._chain_ids = coll.chain_ids
@@ -1616,7 +1640,7 @@ class EnsembleMCMC:
         blocks, self._pending = self._pending, []
         if not blocks:
             if self._txt_rows == 0:
-                self._table_collection(np.zeros((0, self.spec.d + 5))).to_txt(path)
+                self._table_collection(np.zeros((0, self.spec.d + len(self.spec.derived_functions) + 5))).to_txt(path)
             return
         coll = self._table_collection(np.vstack(blocks))
         if self._txt_rows == 0:

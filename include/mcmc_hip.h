@@ -350,7 +350,9 @@ MCMC_HIP_API int mcmc_hip_fetch_moments(mcmc_hip_ctx* h, int64_t* n_snapshots, d
  *   pair's FIRST parameter as the row; `outside` counts a walker either coordinate of which is out.
  * configure: dims1[n1] sampler indices, 1 <= bins1 <= 1024; pairs[n2][2] ordered (i, j), i != j,
  * 1 <= bins2 <= 64; lo[d], hi[d] indexed by sampler index (read for the parameters in use only:
- * finite, lo < hi).  Allocates and zeroes the slab and its pinned read-out; n1 = n2 = 0 frees them
+ * finite, lo < hi).  With m derived rows configured (mcmc_hip_derived_configure, which must come
+ * first) an index d + r names row r of z and lo / hi hold d + m entries; a NaN there is counted
+ * nowhere by a 1-D entry and `outside` by a pair.  Allocates and zeroes the slab and its pinned read-out; n1 = n2 = 0 frees them
  * (the feature is off).  A bad call returns MCMC_HIP_ERR_ARG and names the argument.
  * accumulate: ONE launch on the engine's stream adds every walker of this process once to every
  * entry (the population a moment snapshot sums); no host synchronisation, no allocation.
@@ -477,6 +479,51 @@ MCMC_HIP_API int mcmc_hip_evidence_set(mcmc_hip_ctx* h, const double* sums, cons
 MCMC_HIP_API int mcmc_hip_evidence_layout(const mcmc_hip_ctx* h, int32_t* on, int32_t* n_radii, int32_t* n_groups,
                              int64_t* n_ell, int32_t* has_active, int32_t* has_staged,
                              int64_t* n_accumulations);
+
+/* Derived parameters: m <= 32 rows z[m][W], dimension-major like x, that the CALLER fills on the
+ * engine's stream (mcmc_hip_stream_handle) from the state as it lies in HBM, and their moments
+ * (derived_kernels.hip).  Same life cycle as the marginals.  The rule ("Derived"):
+ * with a_j = z_j - shift_j and b_c = x_{cross_dims[c]} - (moment shift)_{cross_dims[c]}, a walker is used
+ * iff all m of its derived values are finite; per group g of group_size walkers, over the used
+ * walkers in ascending order from +0.0 (one chain each, product and addition rounded separately):
+ * N[g], A[g][j] = sum a_j, B[g][j][k] = sum a_j a_k (k <= j), C[g][j][c] = sum a_j b_c and, beside
+ * them, X[g][c] = sum b_c and V[g][c] = sum b_c b_c (the sampled parameters over the same walkers); the pooled
+ * accumulators then add the groups in ascending order from their current value.  Exact and
+ * order-independent per name: bad[j] counts the non-finite values, min[j] / max[j] are those of the
+ * finite ones (NaN: none yet).
+ * configure: m in 1..32 (m = 0 frees everything: off), n_cross in 0..d distinct sampler indices,
+ * shift[m] finite; allocates and zeroes z and the accumulators.  It must precede
+ * mcmc_hip_marginals_configure, whose indices d .. d + m - 1 name the rows of z (lo / hi then hold
+ * d + m entries), and is refused while marginals are configured.
+ * buffers: the device pointers of x[d][W] and z[m][W].  x is read-only for the caller.
+ * set_values / get_values: host copies of z, point-major [W][m]; synchronous.
+ * set_group_size: the groups of the sums, by default the engine's group_size; any divisor of
+ * n_walkers (a group may be far larger than LDS).  Synchronous; call it between read-outs.
+ * accumulate: two launches on the engine's stream (the group chains, the pooling) over z as it is;
+ * no host synchronisation, no allocation.  MCMC_HIP_ERR_STATE without a state or before configure.
+ * request / fetch: `request` queues the copy of the accumulators to pinned host memory and their
+ * zeroing in stream order, `fetch` waits for that copy only.  A[m], B[m (m + 1) / 2] with (j, k <= j)
+ * at j (j + 1) / 2 + k, C[m][n_cross], X[n_cross] and V[n_cross] (may be NULL when n_cross = 0), bad[m], min[m],
+ * max[m].  One
+ * request may be pending.
+ * set: restores open accumulators (resume); synchronous.
+ * layout: m (0: off), n_cross, group_size, accumulations since the last request; any pointer may be NULL. */
+MCMC_HIP_API int mcmc_hip_derived_configure(mcmc_hip_ctx* h, int32_t m, int32_t n_cross, const int32_t* cross_dims,
+                               const double* shift);
+MCMC_HIP_API int mcmc_hip_derived_set_group_size(mcmc_hip_ctx* h, int32_t group_size);
+MCMC_HIP_API int mcmc_hip_derived_layout(const mcmc_hip_ctx* h, int32_t* m, int32_t* n_cross, int32_t* group_size,
+                            int64_t* n_accumulations);
+MCMC_HIP_API int mcmc_hip_derived_buffers(mcmc_hip_ctx* h, uint64_t* x_device_ptr, uint64_t* z_device_ptr);
+MCMC_HIP_API int mcmc_hip_derived_set_values(mcmc_hip_ctx* h, const double* values);
+MCMC_HIP_API int mcmc_hip_derived_get_values(mcmc_hip_ctx* h, double* values);
+MCMC_HIP_API int mcmc_hip_derived_accumulate(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_derived_request(mcmc_hip_ctx* h);
+MCMC_HIP_API int mcmc_hip_derived_fetch(mcmc_hip_ctx* h, uint64_t* n_used, double* A, double* B, double* C,
+                           double* X, double* V, uint64_t* bad, double* min, double* max,
+                           int64_t* n_accumulations);
+MCMC_HIP_API int mcmc_hip_derived_set(mcmc_hip_ctx* h, uint64_t n_used, const double* A, const double* B,
+                         const double* C, const double* X, const double* V, const uint64_t* bad,
+                         const double* min, const double* max, int64_t n_accumulations);
 
 /* The learn / convergence checkpoint ON THE DEVICE (MCMC.check_convergence_and_learn_proposal,
  * mcmc.py:773-1032; checkpoint_kernels.hip): the intervals between checkpoints are kept in a

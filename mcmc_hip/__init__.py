@@ -60,6 +60,7 @@ else:
         autocorr: bool | dict | None = HIP_DEFAULTS["autocorr"]
         bestfit: bool | dict | None = HIP_DEFAULTS["bestfit"]
         evidence: bool | dict | None = HIP_DEFAULTS["evidence"]
+        derived_stats: bool | dict | None = HIP_DEFAULTS["derived_stats"]
 
         def _export_collection(self, coll):
             """Our table -> `cobaya.collection.SampleCollection` (same columns,
@@ -93,6 +94,9 @@ else:
                 regexps.append((re.compile(output.prefix_regexp_str + r"bestfit\.npz$"), None))
                 # ln Z and its sums of `evidence` (written once, at the end of the run)
                 regexps.append((re.compile(output.prefix_regexp_str + r"evidence\.npz$"), None))
+                # the moments of function-derived parameters (standalone runs: the hosted path leaves
+                # derived parameters to Cobaya's Model)
+                regexps.append((re.compile(output.prefix_regexp_str + r"derived\.npz$"), None))
             return regexps
 
 
