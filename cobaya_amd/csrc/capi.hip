@@ -175,6 +175,31 @@ int set_target_common(mcmc_hip_ctx* h, int K, const double* means, const double*
 
 }  // namespace
 
+// (outside the extern "C" block: a kernel declared inside it would be exported under its bare name)
+namespace mcmc {
+namespace {
+// The checkpoint read-out: word i of the block gsum | pooled (n_acc accumulators) | accept counter
+// goes to word i of the pinned host block, the stuck flag and a function target's error flag to
+// the two halves of the word behind them; the accumulators -- not the counter -- are zeroed in
+// the same pass when `zero` is set.  Words travel as bit patterns (the counter is an integer).
+__global__ void __launch_bounds__(256) readout_moments_kernel(unsigned long long* __restrict__ acc,
+                                                              size_t n_acc, const int* __restrict__ stuck,
+                                                              const int* __restrict__ fn_bad,
+                                                              unsigned long long* __restrict__ pin, int zero)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_acc) {
+        pin[i] = acc[i];
+        if (zero) acc[i] = 0ull;
+    } else if (i == n_acc) {
+        pin[i] = acc[i];
+        const unsigned lo = (unsigned)*stuck, hi = fn_bad ? (unsigned)*fn_bad : 0u;
+        pin[i + 1] = (unsigned long long)lo | ((unsigned long long)hi << 32);
+    }
+}
+}  // namespace
+}  // namespace mcmc
+
 extern "C" {
 
 const char* mcmc_hip_version(void) { return "mcmc_hip 0.1 (gfx950)"; }
@@ -309,7 +334,10 @@ int mcmc_hip_create(const mcmc_hip_config* cfg, mcmc_hip_ctx** out)
         acc(h->nrows.resize(W));
     }
     // (y is sized when the target is known: [K][d][W])
-    acc(hipHostMalloc((void**)&h->pin_mom, sizeof(double) * (G * d + np + 2), hipHostMallocDefault));
+    // (coherent and mapped: readout_moments_kernel stores into it, mcmc_hip_fetch_moments reads it behind mom_event)
+    acc(hipHostMalloc((void**)&h->pin_mom, sizeof(double) * (G * d + np + 2),
+                      hipHostMallocCoherent | hipHostMallocMapped));
+    if (h->pin_mom) acc(hipHostGetDevicePointer((void**)&h->pin_mom_dev, h->pin_mom, 0));
     acc(hipHostMalloc((void**)&h->pin_T, sizeof(double) * 4 * d * d, hipHostMallocDefault));
     for (auto& e : h->pin_T_done) acc(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     acc(hipEventCreateWithFlags(&h->mom_event, hipEventDisableTiming));
@@ -1163,22 +1191,23 @@ int mcmc_hip_request_moments(mcmc_hip_ctx* h)
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t d = h->d, G = h->G, np = d * (d + 1) / 2;
     hipStream_t s = h->stream;
-    // (gsum, pooled and the accept counter are one block: one copy, one fill)
-    HIP_TRY(h, hipMemcpyAsync(h->pin_mom, h->gsum.p, sizeof(double) * (G * d + np + 1),
-                              hipMemcpyDeviceToHost, s));
-    // the stuck flag travels with the read-out (the spare word behind the accept counter): the
-    // run loop never synchronises, so this is where a walker that tripped max_tries is seen
-    // (mcmc.py:717-743 stops at once)
-    HIP_TRY(h, hipMemcpyAsync(h->pin_mom + G * d + np + 1, h->stuck.p, sizeof(int),
-                              hipMemcpyDeviceToHost, s));
-    // (a function target: its error flag in the other half of that word)
-    if (h->fnt.on)
-        HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<int*>(h->pin_mom + G * d + np + 1) + 1, h->fnt.bad.p,
-                                  sizeof(int), hipMemcpyDeviceToHost, s));
-    h->mom_fn = h->fnt.on;
+    // gsum, pooled and the accept counter are one block; the stuck flag travels with the read-out
+    // (the spare word behind the accept counter): the run loop never synchronises, so this is
+    // where a walker that tripped max_tries is seen (mcmc.py:717-743 stops at once); a function
+    // target's error flag is the other half of that word.  ONE kernel stores all of it to its
+    // places in the pinned block and zeroes the accumulators in the same pass (two or three
+    // device-to-host copies and a fill before: four dependent blits, all latency).
     // (with the device-side checkpoint the accumulators are reset by ckpt_window_kernel, which
     // first files them in the ring: mcmc_hip_checkpoint_begin must follow)
-    if (!h->ck.ring.p) HIP_TRY(h, hipMemsetAsync(h->gsum.p, 0, sizeof(double) * (G * d + np), s));
+    {
+        const size_t n_acc = G * d + np;
+        hipLaunchKernelGGL(mcmc::readout_moments_kernel, dim3((unsigned)((n_acc + 1 + 255) / 256)),
+                           dim3(256), 0, s, reinterpret_cast<unsigned long long*>(h->gsum.p), n_acc,
+                           (const int*)h->stuck.p, h->fnt.on ? (const int*)h->fnt.bad.p : nullptr,
+                           h->pin_mom_dev, h->ck.ring.p ? 0 : 1);
+        HIP_TRY(h, hipGetLastError());
+    }
+    h->mom_fn = h->fnt.on;
     HIP_TRY(h, hipEventRecord(h->mom_event, s));
     h->mom_n = h->n_snapshots;
     h->mom_step = h->step;

@@ -211,6 +211,7 @@ struct mcmc_hip_ctx {
     // asynchronous checkpoint (mcmc_hip_request_moments / mcmc_hip_fetch_moments) and
     // stream-ordered proposal refresh: pinned host staging
     double* pin_mom = nullptr;                      // [G*d + d(d+1)/2 + 2]
+    unsigned long long* pin_mom_dev = nullptr;      // the device's alias of pin_mom (readout_moments_kernel stores there)
     double* pin_T = nullptr;                        // ring of 4 transforms [4][d*d]
     int pin_T_slot = 0;
     hipEvent_t pin_T_done[4] = {nullptr, nullptr, nullptr, nullptr};   // the copy out of slot k has run

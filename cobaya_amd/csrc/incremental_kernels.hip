@@ -1168,12 +1168,103 @@ drag_inc_kernel(const IncStepArgs a)
     wave_add_accepts(s.accept_total, (c == 0) ? nacc - nacc0 : 0);
 }
 
+// ---------------------------------------------------------------- rows of L^-1 times a column
+// Shared by whiten_state_kernel and whiten_directions_kernel.  NR (1 .. 4) rows j0 .. j0 + NR - 1 of
+// the lower-triangular L (row-major, d columns; j0 a multiple of 4) times the column col[i * 64]
+// held in LDS: per row ONE ascending fma chain from +0.0 (orc_whiten, orc_whiten_directions); the
+// NR chains share every element of the column.  L's elements are wave-uniform -- scalar loads,
+// scalar operands of the fmas -- and are requested for eight columns (then four) of all the rows
+// at once, with the column's elements beside them: a chain waits once per batch.  Element by
+// element, as before, every term waited for its own scalar loads.
+template <int NR>
+__device__ __forceinline__ void rows_times_column(cdoubles L, int d, int j0,
+                                                  const double* __restrict__ col, double (&acc)[NR])
+{
+    cdoubles r[NR];
+#pragma unroll
+    for (int q = 0; q < NR; ++q) { r[q] = L + (size_t)(j0 + q) * d; acc[q] = 0.0; }
+    int i = 0;
+    for (; i + 8 <= j0; i += 8) {
+        double c[8], m[NR][8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            c[u] = col[(i + u) * 64];
+#pragma unroll
+            for (int q = 0; q < NR; ++q) m[q][u] = r[q][i + u];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int q = 0; q < NR; ++q) acc[q] = fma(m[q][u], c[u], acc[q]);
+    }
+    if (i < j0) {   // (j0 = 4 (mod 8))
+        double c[4], m[NR][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            c[u] = col[(i + u) * 64];
+#pragma unroll
+            for (int q = 0; q < NR; ++q) m[q][u] = r[q][i + u];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int q = 0; q < NR; ++q) acc[q] = fma(m[q][u], c[u], acc[q]);
+    }
+    // the triangle on the diagonal: row j0 + q ends at column j0 + q
+    double c[NR], m[NR][NR];
+#pragma unroll
+    for (int u = 0; u < NR; ++u) {
+        c[u] = col[(j0 + u) * 64];
+#pragma unroll
+        for (int q = u; q < NR; ++q) m[q][u] = r[q][j0 + u];
+    }
+#pragma unroll
+    for (int u = 0; u < NR; ++u)
+#pragma unroll
+        for (int q = u; q < NR; ++q) acc[q] = fma(m[q][u], c[u], acc[q]);
+}
+
+// The row blocks (four rows each, the last one ragged) of L times the column, dealt to the four
+// waves of a workgroup (`part`) as PAIRS (rb, nblk - 1 - rb): a chain of block rb has 4 rb + 1 .. 4 rb + 4
+// terms, so every pair is as long and the waves finish together (dealt in turn, the wave with the
+// last blocks ran 46 terms deep at d = 30 against 24 of the first).  put(j, u_j) takes each row.
+template <class Put>
+__device__ __forceinline__ void row_blocks_times_column(cdoubles L, int d, int part,
+                                                        const double* __restrict__ col, Put&& put)
+{
+    const int nblk = (d + 3) / 4;
+    for (int pr = part; 2 * pr < nblk; pr += 4) {
+        for (int s = 0; s < 2; ++s) {
+            const int rb = s ? nblk - 1 - pr : pr;
+            if (s && rb == pr) break;
+            const int j0 = 4 * rb, nr = d - j0;
+            if (nr >= 4) {
+                double acc[4];
+                rows_times_column<4>(L, d, j0, col, acc);
+                put(j0, acc[0]); put(j0 + 1, acc[1]); put(j0 + 2, acc[2]); put(j0 + 3, acc[3]);
+            } else if (nr == 3) {
+                double acc[3];
+                rows_times_column<3>(L, d, j0, col, acc);
+                put(j0, acc[0]); put(j0 + 1, acc[1]); put(j0 + 2, acc[2]);
+            } else if (nr == 2) {
+                double acc[2];
+                rows_times_column<2>(L, d, j0, col, acc);
+                put(j0, acc[0]); put(j0 + 1, acc[1]);
+            } else {
+                double acc[1];
+                rows_times_column<1>(L, d, j0, col, acc);
+                put(j0, acc[0]);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- y = L^-1 (x - mu)
 // 64 walkers per workgroup of four waves; the deviations of the workgroup sit in LDS
 // ([i][walker]) and the rows of L^-1 are read at wave-uniform addresses (scalar loads).  One
-// ascending fma chain per row from +0.0 (orc_whiten); four rows advance together on every
-// deviation read (four independent chains per lane), and the blocks of four rows are dealt to
-// the four waves in turn.  Runs once per `refresh_every` steps.
+// ascending fma chain per row from +0.0 (orc_whiten): row_blocks_times_column.  A wave fetches its
+// share of x eight rows at a time (one round trip to memory instead of one per row).  Runs once
+// per `refresh_every` steps.
 __global__ void __launch_bounds__(256) whiten_state_kernel(const double* __restrict__ x,
                                                            double* __restrict__ y,
                                                            const double* __restrict__ mean,
@@ -1186,47 +1277,29 @@ __global__ void __launch_bounds__(256) whiten_state_kernel(const double* __restr
     const int l = threadIdx.x & 63, part = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6),
               w = blockIdx.x * 64 + l;
     const bool live = w < W;
-    const int nblk = (d + 3) / 4;
     for (int k = 0; k < K; ++k) {   // y is [K][d][W]
         __syncthreads();            // (the previous mode's deviations have been used)
-        if (live)
-            for (int i = part; i < d; i += 4) sdev[i * 64 + l] = x[(size_t)i * W + w] - mean[k * d + i];
-        __syncthreads();
-        if (!live) continue;
-        for (int rb = part; rb < nblk; rb += 4) {
-            const int j0 = 4 * rb;
-            if (j0 + 4 <= d) {
-                const double* __restrict__ r0 = Lrow + ((size_t)k * d + j0) * d;
-                const double* __restrict__ r1 = r0 + d;
-                const double* __restrict__ r2 = r1 + d;
-                const double* __restrict__ r3 = r2 + d;
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-                for (int i = 0; i <= j0; ++i) {
-                    const double dv = sdev[i * 64 + l];
-                    a0 = fma(r0[i], dv, a0);
-                    a1 = fma(r1[i], dv, a1);
-                    a2 = fma(r2[i], dv, a2);
-                    a3 = fma(r3[i], dv, a3);
+        if (live) {
+            for (int i0 = part; i0 < d; i0 += 32) {
+                double xv[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int i = i0 + 4 * u;
+                    xv[u] = i < d ? x[(size_t)i * W + w] : 0.0;
                 }
-                const double d1 = sdev[(j0 + 1) * 64 + l], d2 = sdev[(j0 + 2) * 64 + l],
-                             d3 = sdev[(j0 + 3) * 64 + l];
-                a1 = fma(r1[j0 + 1], d1, a1);
-                a2 = fma(r2[j0 + 1], d1, a2);
-                a3 = fma(r3[j0 + 1], d1, a3);
-                a2 = fma(r2[j0 + 2], d2, a2);
-                a3 = fma(r3[j0 + 2], d2, a3);
-                a3 = fma(r3[j0 + 3], d3, a3);
-                double* __restrict__ out = y + ((size_t)k * d + j0) * W + w;
-                out[0] = a0; out[(size_t)W] = a1; out[2 * (size_t)W] = a2; out[3 * (size_t)W] = a3;
-            } else {
-                for (int j = j0; j < d; ++j) {
-                    const double* __restrict__ row = Lrow + ((size_t)k * d + j) * d;
-                    double acc = 0.0;
-                    for (int i = 0; i <= j; ++i) acc = fma(row[i], sdev[i * 64 + l], acc);
-                    y[((size_t)k * d + j) * W + w] = acc;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int i = i0 + 4 * u;
+                    if (i < d) sdev[i * 64 + l] = xv[u] - mean[k * d + i];
                 }
             }
         }
+        __syncthreads();
+        if (!live) continue;
+        const cdoubles L = (cdoubles)(unsigned long long)(Lrow + (size_t)k * d * d);
+        double* __restrict__ out = y + (size_t)k * d * W + w;
+        row_blocks_times_column(L, d, part, sdev + l,
+                                [&](int j, double v) { out[(size_t)j * W] = v; });
     }
 }
 
@@ -1250,7 +1323,14 @@ __global__ void __launch_bounds__(256) whiten_directions_kernel(const IncDirArgs
         const int cyc = (int)(step / (unsigned long long)a.cps - a.cycle0);
         const int col = (int)(step % (unsigned long long)a.cps);
         const double* __restrict__ v = a.V + ((size_t)g * a.ncyc + cyc) * a.slab + (size_t)col * a.ld;
-        for (int i = part; i < d; i += 4) sv[i * 64 + l] = v[i];
+        for (int i0 = part; i0 < d; i0 += 32) {   // (eight rows per round trip, as whiten_state_kernel)
+            double vv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) vv[u] = i0 + 4 * u < d ? v[i0 + 4 * u] : 0.0;
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (i0 + 4 * u < d) sv[(i0 + 4 * u) * 64 + l] = vv[u];
+        }
         if (a.vflag) flag1d = a.vflag[((size_t)g * a.ncyc + cyc) * a.cps + col];
     }
     __syncthreads();
@@ -1261,46 +1341,10 @@ __global__ void __launch_bounds__(256) whiten_directions_kernel(const IncDirArgs
                                   : (size_t)sr;
     double2* __restrict__ out = (double2*)a.VU + ((size_t)g * a.out_total + ocol) * (4 * a.dq);
     if (a.colflag && part == 0) a.colflag[(size_t)g * a.out_total + ocol] = flag1d;
-    // Four rows at a time: four independent chains share every v_i read from LDS (each chain is
-    // still one ascending fma chain from +0.0 -- the order of orc_whiten_directions); the row
-    // blocks of a column are dealt to the four waves of the workgroup (the long ones last).
-    const int nblk = (d + 3) / 4;
-    for (int rb = part; rb < nblk; rb += 4) {
-        const int j = 4 * rb;
-        if (j + 4 <= d) {
-            // (the rows of L^-1 through the constant address space: scalar loads, scalar operands)
-            const cdoubles r0 = (cdoubles)(unsigned long long)(a.Lrow + (size_t)j * d);
-            const cdoubles r1 = r0 + d;
-            const cdoubles r2 = r1 + d;
-            const cdoubles r3 = r2 + d;
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-            for (int i = 0; i <= j; ++i) {
-                const double v = sv[i * 64 + l];
-                a0 = fma(r0[i], v, a0);
-                a1 = fma(r1[i], v, a1);
-                a2 = fma(r2[i], v, a2);
-                a3 = fma(r3[i], v, a3);
-            }
-            const double v1 = sv[(j + 1) * 64 + l], v2 = sv[(j + 2) * 64 + l], v3 = sv[(j + 3) * 64 + l];
-            a1 = fma(r1[j + 1], v1, a1);
-            a2 = fma(r2[j + 1], v1, a2);
-            a3 = fma(r3[j + 1], v1, a3);
-            a2 = fma(r2[j + 2], v2, a2);
-            a3 = fma(r3[j + 2], v2, a3);
-            a3 = fma(r3[j + 3], v3, a3);
-            out[j] = make_double2(sv[j * 64 + l], a0);
-            out[j + 1] = make_double2(v1, a1);
-            out[j + 2] = make_double2(v2, a2);
-            out[j + 3] = make_double2(v3, a3);
-        } else {
-            for (int jj = j; jj < d; ++jj) {
-                const cdoubles row = (cdoubles)(unsigned long long)(a.Lrow + (size_t)jj * d);
-                double acc = 0.0;
-                for (int i = 0; i <= jj; ++i) acc = fma(row[i], sv[i * 64 + l], acc);
-                out[jj] = make_double2(sv[jj * 64 + l], acc);
-            }
-        }
-    }
+    // u = L^-1 v: one ascending fma chain per row from +0.0 (orc_whiten_directions), the row blocks
+    // dealt to the four waves in balanced pairs -- row_blocks_times_column
+    row_blocks_times_column((cdoubles)(unsigned long long)a.Lrow, d, part, sv + l,
+                            [&](int j, double u) { out[j] = make_double2(sv[j * 64 + l], u); });
     if (part == 3)
         for (int j = d; j < 4 * a.dq; ++j) out[j] = make_double2(0.0, 0.0);
     if (a.UU) {

@@ -1352,64 +1352,110 @@ __global__ void __launch_bounds__(64) evaluate_kernel(const EvalArgs a)
 // ---------------------------------------------------------------- moments
 // Per group: sum_x[i] and S_g[i][j] = sum_l x_i x_j over the group's walkers in ascending
 // order (sequential fma chains: deterministic), X tile staged in LDS.
+//
+// The rows of the tile hold a walker's deviations as column PAIRS (2k, 2k + 1), 16 bytes each.  A
+// thread owns a 2 x 2 tile of the lower triangle -- rows {2I, 2I + 1} x columns {2J, 2J + 1}, I >= J
+// -- and advances its four chains on two ds_read_b128 per walker: 8 bytes of LDS per chain term
+// (two chains on four ds_read_b64 took 16).  Every chain is still ONE ascending fma chain from +0.0
+// inside one thread (the specification).  The reads of a batch of eight walkers are requested
+// while the batch before it is in the fmas.
+// Row stride: kMomLd = 2 (mod 4) doubles.  The chain phase reads one row per instruction (all lanes
+// the same walker; equal addresses are a broadcast).  ds_read_b128 banks are (a / 4) mod 64, that is
+// 32 doubles: up to d = 30 (a row of <= 60 dwords) distinct column pairs are distinct banks; at
+// d = 31 and 32 the row is 68 dwords and column pair 16 shares the banks of pair 0 -- 2-way where
+// a 16-lane group reads both.  The staging stores see the stride: a lane stores a column pair of its
+// own walker with ds_write_b128, serviced eight lanes at a time over 32 banks, and 8 rows 2 (mod 4)
+// doubles apart start at 8 different multiples of four dwords: no conflict expected (an odd stride,
+// as for the 8-byte stores before, would not be 16-byte aligned; a multiple of four is 2-way).
+// Measured at gs = 256, d = 30 (profiles/r16_interlude.txt): 11.0 us per launch (14.8 before), with
+// the kernel's SQ_LDS_BANK_CONFLICT there.
+// The loops below have no tail: they take 16 (tiles) and 8 (sums) walkers per turn and find the last
+// wave as gs / 64 - 1, so gs must be a multiple of 64 -- mcmc_hip_create accepts 64, 128 and 256, and
+// launch_moments refuses anything else.
+constexpr int kMomNb = (D + 1) / 2;                       // column pairs of a row
+constexpr int kMomLd = (2 * kMomNb) % 4 == 2 ? 2 * kMomNb : 2 * kMomNb + 2;
+constexpr int kMomTiles = kMomNb * (kMomNb + 1) / 2;
+
 __global__ void __launch_bounds__(256) group_moments_kernel(const MomentArgs a)
 {
-    extern __shared__ __attribute__((aligned(16))) double sX[];  // [gs][D|1]
-    constexpr int LDX = D | 1;
+    extern __shared__ __attribute__((aligned(16))) double sX[];  // [gs][kMomLd]
     const int tid = threadIdx.x, gs = blockDim.x, g = blockIdx.x;
     const int w = g * gs + tid;
+    {
+        double xv[2 * kMomNb];
 #pragma unroll
-    for (int i = 0; i < D; ++i) sX[tid * LDX + i] = a.x[(size_t)i * a.W + w] - a.shift[i];
-    __syncthreads();
-    // Every sum is ONE chain over the group's walkers in ascending order (the specification); a
-    // chain's operands are read from LDS eight walkers at a time, so that the reads of a batch
-    // travel together instead of one LDS round trip per term (round 4: the kernel has one wave
-    // per SIMD and nothing else to cover them: 14.6 -> ~6 us at group_size 256, d = 30).  A thread
-    // runs two chains side by side: the pairs p and p + gs, or -- the last D threads, whose
-    // second pair does not exist when NPAIR <= 2 gs - D -- a pair and a group sum.
-    auto pair_of = [](int p, int& i, int& j) {   // p = i(i+1)/2 + j, i >= j
-        i = (int)((sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
-        while ((i + 1) * (i + 2) / 2 <= p) ++i;
-        while (i * (i + 1) / 2 > p) --i;
-        j = p - i * (i + 1) / 2;
-    };
-    const bool sums_ride = NPAIR + D <= 2 * gs;   // the group sums fit beside the second pairs
-    for (int p0 = tid; p0 < NPAIR || (sums_ride && p0 < gs); p0 += 2 * gs) {
-        const int p1 = p0 + gs;
-        const bool has0 = p0 < NPAIR, has1 = p1 < NPAIR;
-        const int sidx = tid - (gs - D);                       // the group sum this thread carries
-        const bool sum1 = sums_ride && !has1 && p0 < gs && sidx >= 0 && sidx < D;
-        int i0 = 0, j0 = 0, i1 = 0, j1 = 0;
-        if (has0) pair_of(p0, i0, j0);
-        if (has1) pair_of(p1, i1, j1);
-        if (sum1) i1 = sidx;
-        double s0 = 0.0, s1 = 0.0;
-        int l = 0;
-        for (; l + 8 <= gs; l += 8) {
-            double a0[8], b0[8], a1[8], b1[8];
+        for (int i = 0; i < 2 * kMomNb; ++i) xv[i] = i < D ? a.x[(size_t)i * a.W + w] : 0.0;
+        double2* __restrict__ row = (double2*)(sX + tid * kMomLd);
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                a0[q] = sX[(l + q) * LDX + i0]; b0[q] = sX[(l + q) * LDX + j0];
-                a1[q] = sX[(l + q) * LDX + i1]; b1[q] = sX[(l + q) * LDX + j1];
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                s0 = fma(a0[q], b0[q], s0);
-                s1 = sum1 ? s1 + a1[q] : fma(a1[q], b1[q], s1);
-            }
-        }
-        for (; l < gs; ++l) {
-            s0 = fma(sX[l * LDX + i0], sX[l * LDX + j0], s0);
-            s1 = sum1 ? s1 + sX[l * LDX + i1] : fma(sX[l * LDX + i1], sX[l * LDX + j1], s1);
-        }
-        if (has0) a.Sg[(size_t)g * NPAIR + p0] = s0;
-        if (has1) a.Sg[(size_t)g * NPAIR + p1] = s1;
-        if (sum1) a.group_sum[(size_t)g * D + sidx] += s1;
+        for (int k = 0; k < kMomNb; ++k)   // (the column beyond an odd D: +0.0, its chains are dropped)
+            row[k] = make_double2(xv[2 * k] - a.shift[2 * k],
+                                  2 * k + 1 < D ? xv[2 * k + 1] - a.shift[2 * k + 1] : 0.0);
     }
-    if (!sums_ride && tid < D) {   // (small groups: the sums on their own)
-        double s = 0.0;
-        for (int l = 0; l < gs; ++l) s = s + sX[l * LDX + tid];
-        a.group_sum[(size_t)g * D + tid] += s;
+    __syncthreads();
+    constexpr int B = 8;   // walkers per batch of reads (gs is 64, 128 or 256)
+    for (int t = tid; t < kMomTiles; t += gs) {
+        // t = I (I + 1) / 2 + J, I >= J
+        int I = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+        while ((I + 1) * (I + 2) / 2 <= t) ++I;
+        while (I * (I + 1) / 2 > t) --I;
+        const int J = t - I * (I + 1) / 2;
+        const double2* __restrict__ pa = (const double2*)(sX + 2 * I);
+        const double2* __restrict__ pb = (const double2*)(sX + 2 * J);
+        double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;   // s_rc: row 2I + r, column 2J + c
+        double2 A[2][B], Bv[2][B];
+#pragma unroll
+        for (int q = 0; q < B; ++q) {
+            A[0][q] = pa[q * (kMomLd / 2)];
+            Bv[0][q] = pb[q * (kMomLd / 2)];
+        }
+        for (int l = 0; l < gs; l += 2 * B) {   // (two batches per turn: the buffers swap by name)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int nxt = l + (h + 1) * B;
+                if (nxt < gs) {
+#pragma unroll
+                    for (int q = 0; q < B; ++q) {
+                        A[h ^ 1][q] = pa[(nxt + q) * (kMomLd / 2)];
+                        Bv[h ^ 1][q] = pb[(nxt + q) * (kMomLd / 2)];
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < B; ++q) {
+                    s00 = fma(A[h][q].x, Bv[h][q].x, s00);
+                    s01 = fma(A[h][q].x, Bv[h][q].y, s01);
+                    s10 = fma(A[h][q].y, Bv[h][q].x, s10);
+                    s11 = fma(A[h][q].y, Bv[h][q].y, s11);
+                }
+            }
+        }
+        // pair (i, j), i >= j, is word i (i + 1) / 2 + j; a diagonal tile's (2I, 2I + 1) is the
+        // mirror of its (2I + 1, 2I) and is dropped, as are the chains of the column beyond an odd D
+        double* __restrict__ Sg = a.Sg + (size_t)g * NPAIR;
+        const int i0 = 2 * I, j0 = 2 * J, i1 = i0 + 1, j1 = j0 + 1;
+        Sg[i0 * (i0 + 1) / 2 + j0] = s00;
+        if (I != J) Sg[i0 * (i0 + 1) / 2 + j1] = s01;
+        if (i1 < D) {
+            Sg[i1 * (i1 + 1) / 2 + j0] = s10;
+            if (j1 < D) Sg[i1 * (i1 + 1) / 2 + j1] = s11;
+        }
+    }
+    // The group sums (ascending plain sums from +0.0, then group_sum += s): the last wave of the
+    // workgroup, a column pair per lane -- beside the tiles where they leave that wave free
+    // (gs = 256 at d = 30: 120 tiles on waves 0 and 1), behind its tiles otherwise.
+    if ((tid >> 6) == (gs >> 6) - 1) {
+        for (int k = tid & 63; k < kMomNb; k += 64) {
+            const double2* __restrict__ pa = (const double2*)(sX + 2 * k);
+            double s0 = 0.0, s1 = 0.0;
+            for (int l = 0; l < gs; l += B) {
+                double2 v[B];
+#pragma unroll
+                for (int q = 0; q < B; ++q) v[q] = pa[(l + q) * (kMomLd / 2)];
+#pragma unroll
+                for (int q = 0; q < B; ++q) { s0 = s0 + v[q].x; s1 = s1 + v[q].y; }
+            }
+            a.group_sum[(size_t)g * D + 2 * k] += s0;
+            if (2 * k + 1 < D) a.group_sum[(size_t)g * D + 2 * k + 1] += s1;
+        }
     }
 }
 
@@ -1571,7 +1617,9 @@ hipError_t launch_evaluate(const EvalArgs& a, hipStream_t st)
 
 hipError_t launch_moments(const MomentArgs& a, int group_size, hipStream_t st)
 {
-    const size_t lds = sizeof(double) * (size_t)group_size * (D | 1);
+    if (group_size <= 0 || group_size > 256 || group_size % 64 != 0)
+        return hipErrorInvalidValue;   // (group_moments_kernel's loops have no tail)
+    const size_t lds = sizeof(double) * (size_t)group_size * kMomLd;
     hipLaunchKernelGGL(group_moments_kernel, dim3(a.G), dim3(group_size), lds, st, a);
     hipLaunchKernelGGL(pool_moments_kernel, dim3((NPAIR + 63) / 64), dim3(64), 0, st, a);
     return hipGetLastError();
