@@ -158,6 +158,15 @@ __device__ __forceinline__ void stage16_dma(void* lds_dst, const void* gsrc)   /
                                          (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
     }
 }
+// ... and 4 bytes per lane (global_load_lds_dword: lane l writes lds_byte_addr + 4 l), for a source that is not
+// 16-byte aligned: the |u|^2 of a chunk's columns start at any column of a direction set (incremental_duo.hip)
+__device__ __forceinline__ void stage4_dma(void* lds_dst, const void* gsrc)   // lds_dst: wave-uniform, in LDS
+{
+    const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_offset(lds_dst));
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
+}
 // every DMA of this wave has landed (in front of the barrier that publishes the buffer)
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 

@@ -64,6 +64,11 @@
 #ifndef MCMC_DUO1_DMA_HIDDEN
 #define MCMC_DUO1_DMA_HIDDEN 1
 #endif
+// |u|^2 of a chunk's columns staged into LDS with the chunk (1) or read by a scalar load inside the step (0)
+// (measured: profiles/r17_step_path.txt)
+#ifndef MCMC_DUO1_UU_LDS
+#define MCMC_DUO1_UU_LDS 1
+#endif
 #ifndef MCMC_DUO1_LADDER
 #define MCMC_DUO1_LADDER 4   // (pairs per counted LDS wait of the one-mode step, >= 1: see its step loop)
 #endif
@@ -568,6 +573,11 @@ __host__ __device__ constexpr int duo1_chunk(int dq)
     int c = ((80 * 1024 - 16896 - 2048) / (2 * 64 * dq)) & ~3;
     return c > 64 ? 64 : c;
 }
+// the dynamic LDS of step_inc_duo_kernel: two buffers of pairs and, behind them, two of the columns' |u|^2
+__host__ __device__ constexpr size_t duo1_lds(int dq)
+{
+    return (size_t)2 * duo1_chunk(dq) * (64 * dq + (MCMC_DUO1_UU_LDS != 0 ? 8 : 0));
+}
 
 template <int DQ, int NE, bool SPLIT, bool UNIT_T>
 __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs a)
@@ -576,6 +586,10 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
     constexpr int COLB = 4 * DQ, dpad = 4 * DQ;  // (v, u) pairs per column
     constexpr int C = duo1_chunk(DQ);
     constexpr int CHUNK = C * COLB;              // pairs per chunk
+    constexpr bool UU_LDS = MCMC_DUO1_UU_LDS != 0;
+    static_assert(duo1_lds(DQ) + sizeof(pair_t) * kDuoStagedPairs + sizeof(dpair_t) * SHORT_LOG_TABLE_SIZE <= 80 * 1024,
+                  "two workgroups per CU");
+    static_assert(2 * C <= 256, "a chunk's |u|^2: at most one dword per lane of the workgroup");
     static_assert(SPLIT ? (NE == 2 * DQ || NE == 2 * DQ - 1) : NE == 2 * DQ, "dimensions per lane");
     const StepArgs& s = a.s;
     const int tid = threadIdx.x, h = tid & 1, wave = tid >> 6, lane = tid & 63;
@@ -586,6 +600,8 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
     // (the launch's columns inside its direction set: see IncStepArgs::vu_cols)
     const int set_cols = a.vu_cols > 0 ? a.vu_cols : ncols;
     const double2* __restrict__ gVU = (const double2*)a.VU + ((size_t)g * set_cols + (size_t)a.col0) * COLB;
+    const double* __restrict__ gUUc = a.UU + ((size_t)g * set_cols + (size_t)a.col0);   // |u|^2 of the launch's columns
+    double* const sUU = (double*)(smem2 + 2 * CHUNK);                                    // [2][C], behind the pairs
     auto stage = [&](int k) {   // chunk k -> buffer k & 1, by DMA (as in step_inc_kernel)
         const int first = k * C;
         if (first >= ncols) return;
@@ -596,6 +612,12 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
         for (int kb = wave; kb * 1024 < bytes; kb += 4) {
             if (kb * 1024 + lane * 16 < bytes)
                 stage16_dma<MCMC_DUO1_DMA_HIDDEN != 0>(dst + kb * 1024, src + kb * 1024 + lane * 16);
+        }
+        // the chunk's |u|^2, a dword per lane (8-byte aligned only: a launch starts at any column of its set); wave
+        // j moves the dwords 64 j .. 64 j + 63 of the 2 cols
+        if constexpr (UU_LDS) {
+            if (wave * 64 + lane < 2 * cols)
+                stage4_dma((char*)(sUU + (k & 1) * C) + wave * 256, (const char*)(gUUc + first) + (wave * 64 + lane) * 4);
         }
     };
     const bool refresh_y = (a.anchor & 2) != 0;   // wave-uniform
@@ -681,17 +703,26 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
     DuoVariates sv;
     sv.init(sRE, wave, lane);
     const int hw_slot = hw_wave_slot();
+    // the lanes that were over the limit of tries at some step: gathered by every step, looked at once per chunk
+    unsigned long long stuck_m = 0ull;
 
+    // A chunk's steps run OCTET by octet of the global step index (round 17): the burst of variates, then the up to
+    // eight steps the octet has inside the chunk -- a chunk is a multiple of four columns and a launch starts
+    // anywhere, so an octet may begin in one chunk and end in the next.  The common path of a step is straight-line
+    // code whose one taken branch is the back-edge (tools/check_step_path.py): the octet test and the 64-bit step
+    // index stand in front of the octet, the exact support test, the exact accept, the burn-in bookkeeping and the
+    // report of a stuck chain behind the loop.
     for (int base = 0, k = 0; base < ncols; base += C, ++k) {
         const double2* __restrict__ cur = smem2 + (k & 1) * CHUNK;
         stage(k + 1);
         const int cols = __builtin_amdgcn_readfirstlane(ncols - base < C ? ncols - base : C);
         unsigned coff = lds_offset(cur + (SPLIT ? h : 2 * h));
+        unsigned uoff = lds_offset(sUU + (k & 1) * C);   // (the same address in every lane: a broadcast read)
 #pragma unroll 1
-        for (int sl = 0; sl < cols; ++sl, coff += COLB * 16) {
-            const unsigned long long S = s.step0 + (unsigned long long)(base + sl);
-            if ((S >> 3) != cur_oct) {   // wave-uniform: every eighth step
-                cur_oct = S >> 3;
+        for (int sl0 = 0; sl0 < cols;) {
+            const unsigned long long S0 = s.step0 + (unsigned long long)(base + sl0);
+            if ((S0 >> 3) != cur_oct) {   // (not the octet the chunk before ended in)
+                cur_oct = S0 >> 3;
                 rotate_priority<2>(hw_slot);
 #pragma unroll 1
                 for (int q = 0; q < 2; ++q) {   // (rolled: one Philox block's registers at a time)
@@ -699,94 +730,143 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
                     pr.run_lazy(s.key0, s.key1, gid, (cur_oct << 2) + (unsigned long long)(2 * h + q), slog);
                     sv.put(sRE, wave, lane, h, q, pr);
                 }
-                sv.seek(S);
             }
-            double r, Ea;
-            sv.fetch(r, Ea);
-            sv.next();
-            // the step's pairs stay in registers from the trial to the commit (requesting the next
-            // step's behind the commit, over the bookkeeping, was measured slower: 1.24 against 1.02 ms)
-            pair_t pk[NE];
-            const lds_pairs col = (lds_pairs)(unsigned long long)coff;
-#pragma unroll
-            for (int e = 0; e < NE; ++e) pk[e] = col[duo1_off<SPLIT>(e)];
-            // the support test on the high words of the trial coordinates (step_inc_kernel MODE 0)
-            unsigned hmx = 0u;
-            double pc0 = 0.0, pc1 = 0.0;
-            // The reads land in order and each is waited for by its count (stage16_dma), so the arithmetic runs
-            // underneath their return: groups of G = MCMC_DUO1_LADDER pairs (1 <= G <= NE; measured at dq = 8 only:
-            // G = 4 against G = 1 and the compiler's own order, profiles/r14_lds_wait_ladder.txt; the smaller dq
-            // take the same G unmeasured) pinned in this order: the trial of the group's LAST pair first -- one rung
-            // retires the group's reads --, then the others, then the group's y . u in ascending order (the sums'
-            // order is the specification's).
-            {
-                constexpr int G = MCMC_DUO1_LADDER;
-                static_assert(G >= 1, "pairs per rung");
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int e0 = 0; e0 < NE; e0 += G) {
-                    const int e1 = e0 + G < NE ? e0 + G : NE;
-#pragma unroll
-                    for (int q = 0; q < e1 - e0; ++q) {
-                        const int e = q == 0 ? e1 - 1 : e0 + q - 1;
-                        const unsigned hw = (unsigned)__double2hiint(fma(r, pk[e].x, x[e]));
-                        hmx = hmx > hw ? hmx : hw;
-                    }
-#pragma unroll
-                    for (int e = e0; e < e1; ++e) {
-                        if (e & 1) pc1 = fma(y[e], pk[e].y, pc1);   // (y . u: the log-likelihood is carried)
-                        else pc0 = fma(y[e], pk[e].y, pc0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
+            sv.seek(S0);
+            const int left = cols - sl0, in_oct = 8 - (int)(S0 & 7ull);
+            const int n_oct = left < in_oct ? left : in_oct;   // >= 1
+            [[maybe_unused]] const cdoubles uu_oct = gUU + (base + sl0);
+#pragma unroll 1
+            for (int so = 0; so < n_oct; ++so, coff += COLB * 16) {
+                // (the step's place in the octet as the compiler cannot follow it: the 64-bit step index, which only
+                // the exact accept needs, is then formed there and not carried by every step)
+                int so_here = so;
+                asm volatile("" : "+s"(so_here));
+                // |u|^2 of the column from the chunk's LDS, requested in FRONT of the step's other reads (LDS answers in
+                // order: the first rung's count covers it) -- no scalar load between the reads and the commit
+                double uu;
+                if constexpr (UU_LDS) {
+                    uu = *(lds_doubles)(unsigned long long)uoff;
+                    uoff += 8u;
                 }
-                asm volatile("" : "+v"(pc0), "+v"(pc1));   // (here, not sunk behind the support test's branch)
-            }
-            // (behind the last rung: a scalar load in flight across the reads puts LGKM truly out of order)
-            const double uu = gUU[base + sl];   // (wave-uniform address: a scalar load)
-            unsigned long long inside_m = lanes(pair_max_u32(hmx) < bhi_word);
-            if (inside_m != lanes(true)) {   // (wave-uniform, rare) the exact test
-                unsigned long long inb = ~0ull;
+                double r, Ea;
+                sv.fetch(r, Ea);
+                sv.next();
+                // the step's pairs stay in registers from the trial to the commit (requesting the next
+                // step's behind the commit, over the bookkeeping, was measured slower: 1.24 against 1.02 ms)
+                pair_t pk[NE];
+                const lds_pairs col = (lds_pairs)(unsigned long long)coff;
+#pragma unroll
+                for (int e = 0; e < NE; ++e) pk[e] = col[duo1_off<SPLIT>(e)];
+                // the support test on the high words of the trial coordinates (step_inc_kernel MODE 0)
+                unsigned hmx = 0u;
+                double pc0 = 0.0, pc1 = 0.0;
+                // The reads land in order and each is waited for by its count (stage16_dma), so the arithmetic runs
+                // underneath their return: groups of G = MCMC_DUO1_LADDER pairs (1 <= G <= NE; measured at dq = 8 only:
+                // G = 4 against G = 1 and the compiler's own order, profiles/r14_lds_wait_ladder.txt; the smaller dq
+                // take the same G unmeasured) pinned in this order: the trial of the group's LAST pair first -- one rung
+                // retires the group's reads --, then the others, then the group's y . u in ascending order (the sums'
+                // order is the specification's).
+                {
+                    constexpr int G = MCMC_DUO1_LADDER;
+                    static_assert(G >= 1, "pairs per rung");
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int e0 = 0; e0 < NE; e0 += G) {
+                        const int e1 = e0 + G < NE ? e0 + G : NE;
+#pragma unroll
+                        for (int q = 0; q < e1 - e0; ++q) {
+                            const int e = q == 0 ? e1 - 1 : e0 + q - 1;
+                            const unsigned hw = (unsigned)__double2hiint(fma(r, pk[e].x, x[e]));
+                            hmx = hmx > hw ? hmx : hw;
+                        }
+#pragma unroll
+                        for (int e = e0; e < e1; ++e) {
+                            if (e & 1) pc1 = fma(y[e], pk[e].y, pc1);   // (y . u: the log-likelihood is carried)
+                            else pc0 = fma(y[e], pk[e].y, pc0);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    asm volatile("" : "+v"(pc0), "+v"(pc1));   // (here, not sunk behind the support test's branch)
+                }
+                // (behind the last rung: a scalar load in flight across the reads puts LGKM truly out of order)
+                if constexpr (!UU_LDS) uu = uu_oct[so_here];   // (wave-uniform address: a scalar load)
+                // The support test, decided on the high words where they decide it (round 17).  hmx is the unsigned maximum
+                // of the high words of the walker's trial coordinates t (both lanes: pair_max_u32), W = bhi_word the high
+                // word of hi; blo == +0 and 0 < hi < inf, so W < 0x7ff00000.  The exact test is 0 <= t && t <= hi for every t.
+                //   hmx < W: INSIDE.  Every high word is below W, so every sign bit is clear (t >= +0) and, the doubles of one
+                //     sign being ordered as their bit patterns, every t < the least double with high word W <= hi.
+                //   hmx > W and hmx != 0x80000000: OUTSIDE.  Let t be a coordinate whose high word is hmx.  Sign bit clear:
+                //     t's bit pattern is above that of every double with high word W, hi among them -- t > hi, +inf, or a
+                //     NaN, for which both exact compares are false.  Sign bit set and hmx > 0x80000000: a negative normal
+                //     number, -inf or a NaN with the sign set -- t >= 0 is false.
+                //   hmx == 0x80000000: IN DOUBT.  The coordinate is -0.0 (inside: -0.0 >= +0 and <= hi) or a negative
+                //     denormal (outside), which the low word tells apart; every other high word is at most 0x80000000, so
+                //     the other coordinates may lie on either side of hi.
+                //   hmx == W: IN DOUBT.  Every coordinate is >= +0 and those with a high word below W are inside; those
+                //     with W lie in the slice [trunc(hi), trunc(hi) + 2^-20 ulp_hi), hi itself among them, on either side of hi.
+                // (A padded dimension rests at hi / 2 with v = 0: its high word is below W for a normal hi; for a denormal
+                // hi W is 0, nothing is below it and every step is in doubt.)  Only a wave with a lane in doubt takes the
+                // exact comparisons, for all its lanes; they agree with the two certain classes by the above.  A wave with a
+                // lane outside and none in doubt (estimated at 13 % of the wave-steps on bench.py's target) took them before.
+                const unsigned pmx = pair_max_u32(hmx);
+                unsigned long long inside_m = lanes(pmx < bhi_word);
+                if (__builtin_expect(inside_m != lanes(true), 0)) {   // (wave-uniform) a lane outside or in doubt
+                    if (__builtin_expect((lanes(pmx == bhi_word) | lanes(pmx == 0x80000000u)) != 0ull, 0)) {   // (rare) in doubt
+                        unsigned long long inb = ~0ull;
+#pragma unroll
+                        for (int e = 0; e < NE; ++e) {
+                            const double t = fma(r, pk[e].x, x[e]);
+                            inb &= lanes(t <= bhi) & lanes(t >= blo);
+                        }
+                        inside_m = pair_all_mask(inb);
+                    }
+                }
+                // chi2(y + r u) - chi2(y) = r (2 y.u + r |u|^2) (step_core_inc, `carry`)
+                const double yu = duo1_sum<SPLIT>(pc0, pc1);
+                const double mhr = -0.5 * r;
+                const double lp = s.uniform_logp;
+                const double ll = fma(mhr, fma(r, uu, yu + yu), llik);
+                const double lt = lp + ll;
+                const double delta = UNIT_T ? (lpost - lt) : (lpost - lt) / s.temperature;
+                // (Ea > delta from the staged estimate, exact where in doubt: det_math.h accept_lanes.  At T = 1
+                // lt > lpost is delta = lpost - lt < 0 < Ea, already in it; at other temperatures the compare stays)
+                const unsigned long long up_m = UNIT_T ? 0ull : lanes(lt > lpost);
+                const unsigned long long acc_m =
+                    inside_m & (up_m | accept_lanes(Ea, delta, a.accept_slack, s.key0, s.key1, gid,
+                                                    S0 + (unsigned long long)so_here, slog));   // (the index: formed where it is used)
+                const bool accept = __builtin_amdgcn_inverse_ballot_w64(acc_m);
+                llik = accept ? ll : llik;
+                {
+                    const bool inside = __builtin_amdgcn_inverse_ballot_w64(inside_m);
+                    prej = accept ? 0 : (prej + (inside ? 0 : 1));
+                    wt = accept ? 1 : wt + 1;
+                    nacc += accept ? 1 : 0;
+                }
+                // (the limit of tries of a wave past its burn-in is a scalar; the burning wave's bookkeeping, with its
+                // own compare, lies behind the loop.  `burning` goes from true to false once per run)
+                unsigned long long over_m = lanes(wt - prej > lim1);
+                if (__builtin_expect(burning, 0)) {   // wave-uniform (see step_inc_kernel)
+                    const int lim = burn > 0 ? lim10 : lim1;
+                    burn -= (accept & (burn > 0)) ? 1 : 0;
+                    burning = lanes(burn > 0) != 0ull;
+                    over_m = lanes(wt - prej > lim);
+                }
+                stuck_m |= over_m;
+                const double ra = accept ? r : 0.0;
 #pragma unroll
                 for (int e = 0; e < NE; ++e) {
-                    const double t = fma(r, pk[e].x, x[e]);
-                    inb &= lanes(t <= bhi) & lanes(t >= blo);
+                    x[e] = fma(ra, pk[e].x, x[e]);
+                    y[e] = fma(ra, pk[e].y, y[e]);
                 }
-                inside_m = pair_all_mask(inb);
+                lpost = accept ? lt : lpost;
             }
-            // chi2(y + r u) - chi2(y) = r (2 y.u + r |u|^2) (step_core_inc, `carry`)
-            const double yu = duo1_sum<SPLIT>(pc0, pc1);
-            const double mhr = -0.5 * r;
-            const double lp = s.uniform_logp;
-            const double ll = fma(mhr, fma(r, uu, yu + yu), llik);
-            const double lt = lp + ll;
-            const double delta = UNIT_T ? (lpost - lt) : (lpost - lt) / s.temperature;
-            // (Ea > delta from the staged estimate, exact where in doubt: det_math.h accept_lanes.  At T = 1
-            // lt > lpost is delta = lpost - lt < 0 < Ea, already in it; at other temperatures the compare stays)
-            const unsigned long long up_m = UNIT_T ? 0ull : lanes(lt > lpost);
-            const unsigned long long acc_m =
-                inside_m & (up_m | accept_lanes(Ea, delta, a.accept_slack, s.key0, s.key1, gid, S, slog));
-            const bool accept = __builtin_amdgcn_inverse_ballot_w64(acc_m);
-            llik = accept ? ll : llik;
-            int lim = lim1;
-            if (burning) {   // wave-uniform (see step_inc_kernel)
-                lim = burn > 0 ? lim10 : lim1;
-                burn -= (accept & (burn > 0)) ? 1 : 0;
-                burning = lanes(burn > 0) != 0ull;
-            }
-            const double ra = accept ? r : 0.0;
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                x[e] = fma(ra, pk[e].x, x[e]);
-                y[e] = fma(ra, pk[e].y, y[e]);
-            }
-            lpost = accept ? lt : lpost;
-            {
-                const bool inside = __builtin_amdgcn_inverse_ballot_w64(inside_m);
-                prej = accept ? 0 : (prej + (inside ? 0 : 1));
-                wt = accept ? 1 : wt + 1;
-                nacc += accept ? 1 : 0;
-            }
-            if (wt - prej > lim && h == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
+            sl0 += n_oct;
+        }
+        // a chain over its limit of tries is reported by a lane that was over it at some step of the chunk (it may
+        // have accepted since): the flag says that, and names such a walker
+        if (__builtin_expect(stuck_m != 0ull, 0)) {
+            if (__builtin_amdgcn_inverse_ballot_w64(stuck_m) && h == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
+            stuck_m = 0ull;
         }
         dma_wait();   // the next chunk has landed
         __syncthreads();
@@ -843,7 +923,8 @@ template <int DQ, int NE, bool SPLIT>
 hipError_t launch_duo1(const IncStepArgs& a, hipStream_t st)
 {
     constexpr int C = duo1_chunk(DQ);
-    const size_t lds = sizeof(double2) * 2 * C * 4 * DQ;
+    const size_t lds = duo1_lds(DQ);
+    static_assert(duo1_lds(DQ) >= sizeof(double2) * 2 * C * 4 * DQ, "the pairs' buffers");
     const bool unit_t = a.s.temperature == 1.0;
     typedef void (*kern_t)(const IncStepArgs);
     static const kern_t kerns[2] = {step_inc_duo_kernel<DQ, NE, SPLIT, false>,

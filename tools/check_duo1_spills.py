@@ -26,6 +26,9 @@ def report(asm_text):
             b = re.match(r"^\.LBB\d+_\d+:.*Depth=(\d+)", line)
             if b or re.match(r"^\.LBB\d+_\d+:", line):
                 in_loop = bool(b) and int(b.group(1)) >= 2
+            elif re.match(r"^\s*;\s*=>\s*This (?:Inner )?Loop Header: Depth=(\d+)", line):
+                # (a loop header inside other loops: the label's line names the outermost parent's depth)
+                in_loop = int(re.search(r"Depth=(\d+)", line).group(1)) >= 2
             elif in_loop and line.strip().startswith("scratch_"):
                 n += 1
                 n_st += line.strip().startswith("scratch_store")

@@ -30,6 +30,10 @@ def report(asm_text):
             b = re.match(r"^(\.LBB\d+_\d+):(?:.*Depth=(\d+))?", line)
             if b:
                 in_loop, label, run, cur = bool(b.group(2)) and int(b.group(2)) >= 2, b.group(1), 0, None
+            elif re.match(r"^;\s*=>\s*This (?:Inner )?Loop Header: Depth=(\d+)", text):
+                # (a loop header inside other loops: its label's own line names the outermost parent's depth, this
+                # line of the label's comment its own)
+                in_loop = int(re.search(r"Depth=(\d+)", text).group(1)) >= 2
             elif not in_loop or not text or text.startswith(";"):
                 continue
             elif text.startswith("ds_read_b128"):
