@@ -109,6 +109,7 @@ def translation_units(dims, big=True):
             ("bestfit_kernels.hip", "bestfit", []),     # best fit, MAP and profile likelihoods
             ("evidence_kernels.hip", "evidence", []),   # the sums of the truncated harmonic mean (evidence)
             ("derived_kernels.hip", "derived", []),     # moments of the derived rows
+            ("importance_kernels.hip", "importance", []),   # weighted moments under exp(log-weight)
             ("comm.hip", "comm", [])]   # the RCCL communicator (bound at run time)
     tus += [("incremental_kernels.hip", f"incremental_{lo}", [f"-DMCMC_DQ_LO={lo}", f"-DMCMC_DQ_HI={hi}"])
             for lo, hi in INC_DQ_RANGES]
@@ -132,7 +133,8 @@ def translation_units(dims, big=True):
             ("capi_autocorr.hip", "capi_autocorr", []),
             ("capi_bestfit.hip", "capi_bestfit", []),
             ("capi_evidence.hip", "capi_evidence", []),
-            ("capi_derived.hip", "capi_derived", [])]
+            ("capi_derived.hip", "capi_derived", []),
+            ("capi_importance.hip", "capi_importance", [])]
     return tus
 
 

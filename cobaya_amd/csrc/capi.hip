@@ -434,6 +434,9 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     h->dv.cross.release();
     if (h->dv.pin) (void)hipHostFree(h->dv.pin);
     if (h->dv.ev) (void)hipEventDestroy(h->dv.ev);
+    h->imp.slab.release();
+    if (h->imp.pin) (void)hipHostFree(h->imp.pin);
+    if (h->imp.ev) (void)hipEventDestroy(h->imp.ev);
     if (h->ck.ev) (void)hipEventDestroy(h->ck.ev);
     if (h->pin_mom) (void)hipHostFree(h->pin_mom);
     if (h->pin_T) (void)hipHostFree(h->pin_T);

@@ -26,6 +26,7 @@
 #include "bestfit_args.h"
 #include "evidence_args.h"
 #include "derived_args.h"
+#include "importance_args.h"
 #include "comm.h"
 #include "inc_choice.h"
 
@@ -343,6 +344,23 @@ struct mcmc_hip_ctx {
         hipEvent_t ev = nullptr;
         bool pending = false;
     } dv;
+    // importance reweighting (mcmc_hip_importance_*; importance_kernels.hip): the slab of 64-bit words
+    // sums (alternative k at off[k]: [G][n_chains_k] doubles) | n[n_alt][G] | counters[n_alt][3] | the
+    // keys of c [n_alt], with its pinned read-out.  The log-weights live with the caller
+    struct Importance {
+        DevBuf<unsigned long long> slab;
+        unsigned long long* pin = nullptr;     // [n_words]
+        size_t n_words = 0, n_sums = 0;
+        unsigned long long off[mcmc::kImMaxAlt] = {};
+        int cov[mcmc::kImMaxAlt] = {};
+        int n_alt = 0;
+        int gs = 0, G = 0;                     // the groups of the sums (default: the engine's)
+        bool on = false;
+        int64_t n_acc = 0;                     // accumulations since the last closing request / set
+        int64_t pend_n = 0;                    // ... of the pending read-out
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+    } imp;
     // the walker shards' communicator (comm.hip; not owned): the device checkpoint all-reduces
     // its payload over it in stream order
     mcmc_hip_comm* comm = nullptr;

@@ -242,6 +242,24 @@ def parse_option(opt, sampled):
     return {"cross": cross}
 
 
+def check_values(what, val, n, like):
+    """What a batched device function returned: a torch.float64 tensor of shape (n,) on the device of
+    `like`; else an EngineError (ERR_CALLBACK) that begins with `what`."""
+    import torch
+    if not isinstance(val, torch.Tensor):
+        raise EngineError(ERR_CALLBACK, f"{what}: its function must return a "
+                             f"torch.Tensor, got {type(val).__name__}")
+    if tuple(val.shape) != (n,):
+        raise EngineError(ERR_CALLBACK, f"{what}: its function must return shape "
+                             f"({n},), got shape {tuple(val.shape)}")
+    if val.dtype != torch.float64:
+        raise EngineError(ERR_CALLBACK, f"{what}: its function must return dtype "
+                             f"torch.float64, got dtype {val.dtype}")
+    if val.device != like.device:
+        raise EngineError(ERR_CALLBACK, f"{what}: its function must return a tensor "
+                             f"on device {like.device}, got device {val.device}")
+
+
 # ---------------------------------------------------------------------------------- the sampler's side
 ENGINE_METHODS = ("configure_derived", "derived_row_views", "derived_get_values", "accumulate_derived",
                   "request_derived", "fetch_derived", "derived_set")
@@ -307,18 +325,7 @@ class DerivedAccumulator:
                 except Exception as e:
                     raise EngineError(ERR_CALLBACK, f"derived parameter '{f.name}': its function raised "
                                          f"{type(e).__name__}: {e}") from e
-                if not isinstance(val, torch.Tensor):
-                    raise EngineError(ERR_CALLBACK, f"derived parameter '{f.name}': its function must return a "
-                                         f"torch.Tensor, got {type(val).__name__}")
-                if tuple(val.shape) != (n,):
-                    raise EngineError(ERR_CALLBACK, f"derived parameter '{f.name}': its function must return shape "
-                                         f"({n},), got shape {tuple(val.shape)}")
-                if val.dtype != torch.float64:
-                    raise EngineError(ERR_CALLBACK, f"derived parameter '{f.name}': its function must return dtype "
-                                         f"torch.float64, got dtype {val.dtype}")
-                if val.device != out.device:
-                    raise EngineError(ERR_CALLBACK, f"derived parameter '{f.name}': its function must return a tensor "
-                                         f"on device {out.device}, got device {val.device}")
+                check_values(f"derived parameter '{f.name}'", val, n, out)
                 if val.data_ptr() != out.data_ptr():
                     out.copy_(val)
                 rows[f.name] = out

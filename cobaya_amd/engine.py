@@ -176,6 +176,16 @@ SYMBOLS = [
                                            c_int32_p, c_int64_p]),
     ("mcmc_hip_bestfit_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p,
                                           c_int64_p]),
+    ("mcmc_hip_importance_configure", C.c_int, [_H, C.c_int32, c_int32_p]),
+    ("mcmc_hip_importance_set_group_size", C.c_int, [_H, C.c_int32]),
+    ("mcmc_hip_importance_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int64_p, c_int64_p, c_int32_p, c_int64_p,
+                                             C.POINTER(C.c_uint64)]),
+    ("mcmc_hip_importance_accumulate", C.c_int, [_H, C.c_uint64]),
+    ("mcmc_hip_importance_request", C.c_int, [_H, C.c_int32]),
+    ("mcmc_hip_importance_fetch", C.c_int, [_H, c_double_p, C.c_int64, c_uint64_p, C.c_int64, c_uint64_p,
+                                            c_double_p, c_int64_p]),
+    ("mcmc_hip_importance_set", C.c_int, [_H, c_double_p, C.c_int64, c_uint64_p, C.c_int64, c_uint64_p,
+                                          c_double_p, C.c_int64]),
     ("mcmc_hip_derived_configure", C.c_int, [_H, C.c_int32, C.c_int32, c_int32_p, c_double_p]),
     ("mcmc_hip_derived_set_group_size", C.c_int, [_H, C.c_int32]),
     ("mcmc_hip_derived_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p, c_int64_p]),
@@ -1145,6 +1155,101 @@ class Engine:
         self._check(self._lib.mcmc_hip_evidence_set(
             self._h, _dp(s), c.ctypes.data_as(c_uint64_p), len(s) if len(s) == len(c) else -1, int(clamped),
             int(n_accumulations), None if act is None else _dp(act), None if stg is None else _dp(stg), n_ell))
+
+    # -- importance reweighting: the weighted sums under exp(log-weight)
+    def configure_importance(self, cov=()):
+        """One alternative per entry of `cov` (1..8; truthy: the full weighted covariance is kept, d <=
+        128) whose sums every `accumulate_importance` adds to (mcmc_hip_importance_configure).  None
+        listed: off, everything is freed."""
+        cov = np.ascontiguousarray([1 if c else 0 for c in cov], dtype=np.int32)
+        self._check(self._lib.mcmc_hip_importance_configure(self._h, len(cov), _ip(cov) if len(cov) else None))
+        self._importance_views = None
+
+    def importance_set_group_size(self, group_size):
+        """The groups of the importance sums (default: the engine's group_size): any divisor of W.  The
+        sums are dropped."""
+        self._check(self._lib.mcmc_hip_importance_set_group_size(self._h, int(group_size)))
+
+    def importance_layout(self):
+        """{"n_alt", "n_groups", "n_sums", "offsets" [n_alt], "cov" [n_alt], "n_accumulations", "x_ptr"}
+        (mcmc_hip_importance_layout); n_alt == 0: off."""
+        na, ng = C.c_int32(), C.c_int32()
+        ns, nacc, xp = C.c_int64(), C.c_int64(), C.c_uint64()
+        off, cov = np.zeros(8, np.int64), np.zeros(8, np.int32)
+        self._check(self._lib.mcmc_hip_importance_layout(self._h, C.byref(na), C.byref(ng), C.byref(ns),
+                                                         off.ctypes.data_as(c_int64_p), _ip(cov), C.byref(nacc),
+                                                         C.byref(xp)))
+        return {"n_alt": na.value, "n_groups": ng.value, "n_sums": ns.value, "offsets": off[:na.value].tolist(),
+                "cov": cov[:na.value].tolist(), "n_accumulations": nacc.value, "x_ptr": xp.value}
+
+    def importance_row_views(self):
+        """(x rows, delta, stream): zero-copy torch.float64 views of the d rows of x[d][W], each of
+        shape (W,) and for reading; the log-weights delta[n_alt][W], a tensor of the caller's to fill;
+        and the engine's stream as a `torch.cuda.ExternalStream`.  `import torch` before the first
+        Engine is created."""
+        if getattr(self, "_importance_views", None) is None:
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device))
+            try:
+                stream = torch.cuda.ExternalStream(self.stream_handle(), device=dev)
+            except RuntimeError as e:
+                raise EngineError(ERR_DEVICE,
+                                  f"PyTorch cannot use device {dev} in this process ({e}): `import torch` "
+                                  "before the first Engine is created (before libmcmc_hip.so is loaded), so "
+                                  "that both use one HIP runtime") from e
+            lay = self.importance_layout()
+
+            class _View:   # __cuda_array_interface__ of float64 at a device pointer: no copy
+                def __init__(self, ptr, shape):
+                    self.__cuda_array_interface__ = {"shape": shape, "typestr": "<f8", "data": (ptr, False),
+                                                     "version": 2, "strides": None}
+
+            x = torch.as_tensor(_View(lay["x_ptr"], (self.d, self.W)), device=dev)
+            with torch.cuda.stream(stream):
+                delta = torch.zeros((lay["n_alt"], self.W), dtype=torch.float64, device=dev)
+            self._importance_views = (list(x.unbind(0)), delta, stream)
+        return self._importance_views
+
+    def accumulate_importance(self, delta):
+        """Queue one accumulation of the log-weights `delta` [n_alt][W] (a contiguous torch.float64
+        tensor on the engine's device, filled on its stream) against the state as it is."""
+        n_alt = self.importance_layout()["n_alt"]
+        if tuple(delta.shape) != (n_alt, self.W) or not delta.is_contiguous() or delta.element_size() != 8 \
+                or not delta.is_cuda or not delta.dtype.is_floating_point:
+            raise EngineError(ERR_ARG, f"accumulate_importance: delta must be a contiguous torch.float64 tensor of "
+                                       f"shape ({n_alt}, {self.W}) on the device, got {tuple(delta.shape)} "
+                                       f"{delta.dtype} on {delta.device}")
+        self._check(self._lib.mcmc_hip_importance_accumulate(self._h, int(delta.data_ptr())))
+
+    def request_importance(self, close=True):
+        """Queue the read-out behind the work already in the stream.  `close`: also zero the sums, in
+        stream order (False: nothing is disturbed)."""
+        self._check(self._lib.mcmc_hip_importance_request(self._h, 1 if close else 0))
+
+    def fetch_importance(self):
+        """{"sums" [n_sums] float64 (alternative k: [G][n_chains_k] at offsets[k]), "n" [n_alt, G]
+        uint64, "counters" [n_alt, 3] uint64 (zero, nonfinite, clamped), "c" [n_alt], "n_acc"} of the
+        pending request; waits for the copy only."""
+        lay = self.importance_layout()
+        sums = np.zeros(lay["n_sums"])
+        n = np.zeros((lay["n_alt"], lay["n_groups"]), np.uint64)
+        cnt, c, k = np.zeros((lay["n_alt"], 3), np.uint64), np.zeros(lay["n_alt"]), C.c_int64()
+        self._check(self._lib.mcmc_hip_importance_fetch(
+            self._h, _dp(sums), sums.size, n.ctypes.data_as(c_uint64_p), n.size, cnt.ctypes.data_as(c_uint64_p),
+            _dp(c), C.byref(k)))
+        return {"sums": sums, "n": n, "counters": cnt, "c": c, "n_acc": int(k.value)}
+
+    def importance_set(self, part):
+        """Restore the sums of an unfinished interval (resume): a dict as `fetch_importance` gives."""
+        s = np.ascontiguousarray(part["sums"], dtype=np.float64).reshape(-1)
+        n = np.ascontiguousarray(part["n"], dtype=np.uint64).reshape(-1)
+        cnt = np.ascontiguousarray(part["counters"], dtype=np.uint64).reshape(-1)
+        c = np.ascontiguousarray(part["c"], dtype=np.float64).reshape(-1)
+        n_alt = self.importance_layout()["n_alt"]
+        ok = len(cnt) == 3 * n_alt and len(c) == n_alt
+        self._check(self._lib.mcmc_hip_importance_set(
+            self._h, _dp(s), len(s) if ok else -1, n.ctypes.data_as(c_uint64_p), len(n),
+            cnt.ctypes.data_as(c_uint64_p), _dp(c), int(part["n_acc"])))
 
     # -- the checkpoint on the device
     def checkpoint_set_ring(self, intervals=(), min_capacity=16, first_index=0):

@@ -1,0 +1,598 @@
+"""Importance reweighting of the ensemble (Cobaya's `post`, for the moments): the product (`Importance`),
+the sampler option behind it (`parse_option`) and what the sampler holds of it while it runs
+(`ImportanceAccumulator`, a device product with the methods `marginals.MarginalsAccumulator` states).
+
+An alternative posterior is given by its log-weight: a batched device function of the sampled parameters
+(the forms and checks of `model.DerivedFunction`), bound BY NAME to 1-D torch.float64 views of the rows of
+the state x[d][W] under the engine's stream, which returns delta[W] = ln(new posterior density / sampled
+posterior density) up to a constant.  It must be elementwise in the walker.  The sums come from the
+engine (mcmc_hip_importance_*; importance_kernels.hip), which looks at every walker of every moment
+snapshot.  The rule ("Importance"): per alternative and checkpoint interval, with c
+the exact maximum of the finite delta of the interval's first accumulation (0.0: none) and s the moment
+shift, a walker with delta NaN or +inf is left out (`nonfinite`), one with -inf is used with e = 0
+(`zero`), every other has e = dexp(min(delta - c, 700)) (`clamped` counts delta - c > 700), and each group
+of group_size walkers adds, over its used walkers in ascending order, one chain each from +0.0 with the
+product and the addition as separate roundings,
+
+    n,   S1 = sum e,   S2 = sum e * e,   M_i = sum u_i,   V_i = sum u_i * b_i,   Q_ij = sum u_i * b_j (j < i)
+
+with b_i = x_i - s_i and u_i = e * b_i; the chain of an accumulation is then added to the interval's
+value.  On the host, C = the largest c of the window; every interval's sums are scaled by exp(c - C) in
+float64 (S2, a sum of squares, by its square) and added in interval order, and
+
+    log_ratio = C + ln(S1 / n),   ess = S1^2 / S2,   mean = s + M / S1,   cov = Q / S1 - (M / S1)(M / S1)^T;
+
+the standard errors are delete-one-group jackknives (groups are independent chains, so they absorb the
+correlation between snapshots).
+
+Out of scope: reweighted marginal histograms, derived or bestfit products under the new weights,
+function-derived names as arguments, `temperature != 1`, and writing reweighted chains.
+"""
+from __future__ import annotations
+
+import math
+import time
+
+import numpy as np
+
+from .derived import check_values
+from .engine import ERR_CALLBACK, EngineError
+from .model import UnsupportedModel, parse_derived_function
+
+MAX_ALT = 8                 # importance_args.h: kImMaxAlt
+MAX_DIM = 256               # importance_args.h: kImMaxDim
+MAX_COV_DIM = 128           # importance_args.h: kImMaxCovDim
+CLAMP = 700.0               # importance_args.h: kImClamp
+OPTION_KEYS = ("function", "cov")
+LOW_ESS = 0.05              # an ESS fraction below this is warned about
+
+
+class ImportanceError(ValueError):
+    """An `importance` option (or a pair of products) that cannot be served; the message begins with
+    the option's name."""
+
+
+def n_chains(d, cov):
+    """Chains of one (alternative, group): S1 | S2 | M[d] | V[d] | with `cov` Q[d (d - 1) / 2], (i, j < i)
+    at i (i - 1) / 2 + j."""
+    return 2 + 2 * d + (d * (d - 1) // 2 if cov else 0)
+
+
+def scaled(S, f):
+    """The chains [G, n_chains] of weights e -> those of weights f e: S2, the sum of squares, takes f * f."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = f * S
+        out[:, 1] = (f * f) * S[:, 1]
+    return out
+
+
+def split_sums(flat, d, cov, G):
+    """The flat sums of a read-out -> one [G, n_chains] array per alternative."""
+    out, at = [], 0
+    flat = np.asarray(flat, dtype=np.float64).reshape(-1)
+    for cv in cov:
+        k = G * n_chains(d, cv)
+        out.append(flat[at:at + k].reshape(G, n_chains(d, cv)))
+        at += k
+    if at != len(flat):
+        raise ImportanceError(f"importance: {len(flat)} sums do not fit {len(cov)} alternatives of {G} groups "
+                              f"at d = {d}")
+    return out
+
+
+# ---------------------------------------------------------------------------------- the product
+class Importance:
+    """Weighted moments of the sampled parameters, the effective sample size and the ratio of evidences,
+    per alternative.
+
+    `names`: the alternatives; `params`: the sampled parameters; `shift` [d]: what the sums are taken
+    about; `cov` [n_alt]: whether Q is kept; `n_walkers`: the walkers of the G groups held; `n_acc`:
+    accumulations of the window; `C` [n_alt]: the centring constant the sums are scaled to; `sums`: per
+    alternative float64 [G, n_chains], the window's total per group; `n` uint64 [n_alt, G]: the used
+    walkers; `n_zero`, `n_nonfinite`, `n_clamped` int64 [n_alt]."""
+
+    reports = True
+
+    def __init__(self, names, params, shift, cov, n_walkers, n_acc, C, sums, n, n_zero, n_nonfinite, n_clamped):
+        self.names, self.params = [str(v) for v in names], [str(v) for v in params]
+        na, d = len(self.names), len(self.params)
+        self.d, self.n_walkers, self.n_acc = d, int(n_walkers), int(n_acc)
+        try:
+            self.shift = np.array(shift, dtype=np.float64).reshape(d)
+            self.cov_kept = [bool(c) for c in np.asarray(cov).reshape(na)]
+            self.C = np.array(C, dtype=np.float64).reshape(na)
+            self.n = np.array(n, dtype=np.uint64).reshape(na, -1)
+            G = self.n.shape[1]
+            self.sums = [np.array(s, dtype=np.float64).reshape(G, n_chains(d, c)) for s, c in zip(sums, self.cov_kept)]
+            if len(self.sums) != na:
+                raise ValueError(f"{len(self.sums)} arrays of sums")
+            self.n_zero = np.array(n_zero, dtype=np.int64).reshape(na)
+            self.n_nonfinite = np.array(n_nonfinite, dtype=np.int64).reshape(na)
+            self.n_clamped = np.array(n_clamped, dtype=np.int64).reshape(na)
+        except ValueError as e:
+            raise ImportanceError(f"importance: the arrays of {na} alternatives and {d} parameters do not fit "
+                                  f"together ({e})") from None
+
+    @classmethod
+    def from_parts(cls, names, params, shift, cov, n_walkers, parts, n_groups=None):
+        """From the read-outs of the window's intervals, in their order: dicts {"sums" (flat), "n"
+        [n_alt, G], "counters" [n_alt, 3], "c" [n_alt], "n_acc"}.  Intervals without an accumulation
+        are skipped."""
+        na, d = len(names), len(params)
+        parts = [p for p in parts if int(p["n_acc"]) > 0]
+        G = int(np.asarray(parts[0]["n"]).reshape(na, -1).shape[1]) if parts else int(n_groups or 0)
+        c = np.array([np.asarray(p["c"], np.float64).reshape(na) for p in parts]).reshape(len(parts), na)
+        C = c.max(axis=0) if len(parts) else np.zeros(na)
+        sums = [np.zeros((G, n_chains(d, cv))) for cv in cov]
+        n, cnt = np.zeros((na, G), np.uint64), np.zeros((na, 3), np.int64)
+        for p, ci in zip(parts, c):
+            split = split_sums(p["sums"], d, cov, G)
+            for k in range(na):
+                with np.errstate(invalid="ignore", over="ignore"):
+                    sums[k] = sums[k] + scaled(split[k], math.exp(ci[k] - C[k]))
+            n = n + np.asarray(p["n"], np.uint64).reshape(na, G)
+            cnt = cnt + np.asarray(p["counters"]).reshape(na, 3).astype(np.int64)
+        return cls(names, params, shift, cov, n_walkers, sum(int(p["n_acc"]) for p in parts), C, sums, n,
+                   cnt[:, 0], cnt[:, 1], cnt[:, 2])
+
+    # -- look-ups
+    def _k(self, name):
+        try:
+            return self.names.index(name)
+        except ValueError:
+            raise KeyError(f"no alternative {name!r} (have {self.names})") from None
+
+    @property
+    def n_groups(self):
+        return self.n.shape[1]
+
+    @property
+    def n_samples(self):
+        """Walkers looked at: accumulations x walkers."""
+        return self.n_acc * self.n_walkers
+
+    def n_used(self, name):
+        """Walkers whose log-weight was finite or -inf."""
+        return int(self.n[self._k(name)].sum())
+
+    def zero(self, name):
+        """Walkers used with weight 0 (log-weight -inf)."""
+        return int(self.n_zero[self._k(name)])
+
+    def nonfinite(self, name):
+        """Walkers left out (log-weight NaN or +inf)."""
+        return int(self.n_nonfinite[self._k(name)])
+
+    def clamped(self, name):
+        """Walkers whose log-weight lay more than 700 above its interval's c."""
+        return int(self.n_clamped[self._k(name)])
+
+    # -- the estimates
+    def _tot(self, k):
+        """(n [G], S [G, n_chains], their totals) of alternative k."""
+        n, S = self.n[k].astype(np.float64), self.sums[k]
+        return n, S, n.sum(), S.sum(axis=0)
+
+    def log_ratio(self, name):
+        """ln(Z_new / Z_sampled) = C + ln(S1 / n) (NaN: nothing used; -inf: every weight is zero)."""
+        k = self._k(name)
+        _, _, nt, St = self._tot(k)
+        if nt <= 0:
+            return float("nan")
+        return float(self.C[k] + math.log(St[0] / nt)) if St[0] > 0 else (-math.inf if St[0] == 0 else float("nan"))
+
+    def log_ratio_stderr(self, name):
+        """The delete-one-group jackknife error of `log_ratio` (NaN: fewer than two groups, or a group
+        that holds all the weight)."""
+        k = self._k(name)
+        n, S, nt, St = self._tot(k)
+        G = len(n)
+        if G < 2 or nt <= 0:
+            return float("nan")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            loo = np.log((St[0] - S[:, 0]) / (nt - n))
+        if not np.all(np.isfinite(loo)):
+            return float("nan")
+        return float(math.sqrt((G - 1.0) / G * float(np.sum((loo - loo.mean()) ** 2))))
+
+    def ess(self, name):
+        """The effective sample size (sum w)^2 / sum w^2 (0.0: every weight is zero)."""
+        _, _, _, St = self._tot(self._k(name))
+        with np.errstate(all="ignore"):
+            return float(St[0] / St[1] * St[0]) if St[1] > 0 else 0.0
+
+    def ess_fraction(self, name):
+        n = self.n_used(name)
+        return self.ess(name) / n if n else float("nan")
+
+    def _moments(self, k):
+        """(M / S1 [d], V / S1 [d]) of alternative k (NaN: every weight is zero)."""
+        d = self.d
+        _, _, _, St = self._tot(k)
+        with np.errstate(all="ignore"):
+            return St[2:2 + d] / St[0], St[2 + d:2 + 2 * d] / St[0]
+
+    def mean(self, name):
+        """float64 [d]: the weighted means of the sampled parameters."""
+        return self.shift + self._moments(self._k(name))[0]
+
+    def mean_stderr(self, name):
+        """float64 [d]: the delete-one-group jackknife errors of the means."""
+        k, d = self._k(name), self.d
+        n, S, _, St = self._tot(k)
+        G = len(n)
+        if G < 2:
+            return np.full(d, np.nan)
+        with np.errstate(all="ignore"):
+            loo = (St[2:2 + d] - S[:, 2:2 + d]) / (St[0] - S[:, 0])[:, None]
+            return np.sqrt((G - 1.0) / G * np.sum((loo - loo.mean(axis=0)) ** 2, axis=0))
+
+    def var(self, name):
+        m, v = self._moments(self._k(name))
+        return v - m * m
+
+    def std(self, name):
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(np.maximum(self.var(name), 0.0))
+
+    def cov(self, name):
+        """float64 [d, d]: the weighted covariance (ddof = 0, like SampleCollection.cov)."""
+        k, d = self._k(name), self.d
+        if not self.cov_kept[k]:
+            raise ImportanceError(f"importance: alternative {name!r} keeps no covariance (cov: False); var() and "
+                                  "std() are kept")
+        _, _, _, St = self._tot(k)
+        full = np.zeros((d, d))
+        i, j = np.tril_indices(d, -1)
+        full[i, j] = full[j, i] = St[2 + 2 * d:]
+        full[np.arange(d), np.arange(d)] = St[2 + d:2 + 2 * d]
+        m = self._moments(k)[0]
+        with np.errstate(all="ignore"):
+            return full / St[0] - np.outer(m, m)
+
+    def warnings(self, name):
+        """What the run's last log lines warn about: a low ESS fraction, clamped weights."""
+        out, f = [], self.ess_fraction(name)
+        if self.n_used(name) and f < LOW_ESS:
+            out.append("ESS fraction %.3g is below %g: the sampled posterior barely covers this one" % (f, LOW_ESS))
+        if self.clamped(name):
+            out.append("%d weights were clamped at exp(%g) above their interval's largest" % (self.clamped(name), CLAMP))
+        return out
+
+    def lines(self):
+        """One line per alternative for the log at the end of a run: (text, warns)."""
+        out = []
+        for name in self.names:
+            if not self.n_used(name):
+                out.append(("Importance %s: no walker with a usable log-weight (%d looked at)."
+                            % (name, self.n_samples), True))
+                continue
+            w = self.warnings(name)
+            out.append(("Importance %s: ESS fraction %.3g, ln(Z_new / Z) = %.5g +- %.2g (%d of %d walkers used%s)%s"
+                        % (name, self.ess_fraction(name), self.log_ratio(name), self.log_ratio_stderr(name),
+                           self.n_used(name), self.n_samples,
+                           "; %d with weight zero" % self.zero(name) if self.zero(name) else "",
+                           ". WARNING: " + "; ".join(w) + "." if w else "."), bool(w)))
+        return out
+
+    def summary(self):
+        return "\n".join(t for t, _ in self.lines())
+
+    def report(self, log):
+        """One log line per alternative; a warning where the ESS fraction is low or weights were clamped."""
+        for text, warns in self.lines():
+            (log.warning if warns else log.info)("%s", text)
+
+    # -- arithmetic, files
+    def _layout(self):
+        return (tuple(self.names), tuple(self.params), self.shift.tobytes(), tuple(self.cov_kept), self.n_acc)
+
+    def scaled_to(self, C):
+        """The sums per alternative, scaled from self.C to the centring constants C >= self.C."""
+        return [scaled(s, math.exp(self.C[k] - C[k])) for k, s in enumerate(self.sums)]
+
+    def merge(self, other):
+        """The groups of two shards of one run, side by side, scaled to their common C."""
+        if not isinstance(other, Importance) or self._layout() != other._layout():
+            raise ImportanceError("importance: only shards of one run (alternatives, parameters, shift and "
+                                  "accumulations) merge")
+        C = np.maximum(self.C, other.C)
+        sums = [np.concatenate((a, b), axis=0) for a, b in zip(self.scaled_to(C), other.scaled_to(C))]
+        return Importance(self.names, self.params, self.shift, self.cov_kept, self.n_walkers + other.n_walkers,
+                          self.n_acc, C, sums, np.concatenate((self.n, other.n), axis=1),
+                          self.n_zero + other.n_zero, self.n_nonfinite + other.n_nonfinite,
+                          self.n_clamped + other.n_clamped)
+
+    def __eq__(self, other):
+        return (isinstance(other, Importance) and self._layout() == other._layout()
+                and self.n_walkers == other.n_walkers and np.array_equal(self.C, other.C)
+                and np.array_equal(self.n, other.n)
+                and all(np.array_equal(a, b, equal_nan=True) for a, b in zip(self.sums, other.sums))
+                and all(np.array_equal(getattr(self, k), getattr(other, k))
+                        for k in ("n_zero", "n_nonfinite", "n_clamped")))
+
+    __hash__ = None
+
+    def save(self, path):
+        extra = {"sums_%d" % k: s for k, s in enumerate(self.sums)}
+        with np.errstate(all="ignore"):   # (for a reader without this class)
+            extra.update(log_ratio=np.array([self.log_ratio(v) for v in self.names]),
+                         log_ratio_stderr=np.array([self.log_ratio_stderr(v) for v in self.names]),
+                         ess=np.array([self.ess(v) for v in self.names]),
+                         mean=np.array([self.mean(v) for v in self.names]),
+                         std=np.array([self.std(v) for v in self.names]))
+        with open(path, "wb") as f:   # (np.savez would append ".npz" to a bare name)
+            np.savez(f, names=np.array(self.names, dtype=str), params=np.array(self.params, dtype=str),
+                     shift=self.shift, cov_kept=np.array(self.cov_kept, dtype=np.int64),
+                     geometry=np.array([self.n_walkers, self.n_acc], dtype=np.int64), C=self.C, n=self.n,
+                     counters=np.stack((self.n_zero, self.n_nonfinite, self.n_clamped), axis=1), **extra)
+
+    @classmethod
+    def load(cls, path):
+        z = np.load(path, allow_pickle=False)
+        names = [str(v) for v in z["names"]]
+        cnt = z["counters"].reshape(len(names), 3)
+        return cls(names, [str(v) for v in z["params"]], z["shift"], z["cov_kept"], int(z["geometry"][0]),
+                   int(z["geometry"][1]), z["C"], [z["sums_%d" % k] for k in range(len(names))], z["n"],
+                   cnt[:, 0], cnt[:, 1], cnt[:, 2])
+
+
+# ---------------------------------------------------------------------------------- the option
+def parse_option(opt, sampled, derived=()):
+    """The sampler option `importance` -> None (off) or a list of {"name", "function" (a
+    `model.DerivedFunction`: callable and argument names), "cov"}.  `sampled`: the sampled parameters
+    the arguments are bound to by name; `derived`: the function-derived names, which are refused as
+    arguments.  Refuses, by the option's name, anything else that cannot be served."""
+    if opt is None or opt is False:
+        return None
+    sampled, d = list(sampled), len(sampled)
+    if not isinstance(opt, dict) or not opt:
+        raise ImportanceError(f"importance: expected None or a dict of 1..{MAX_ALT} named alternatives, got {opt!r}")
+    if len(opt) > MAX_ALT:
+        raise ImportanceError(f"importance: at most {MAX_ALT} alternatives are served, not {len(opt)}")
+    out = []
+    for name, alt in opt.items():
+        what = f"importance: alternative {str(name)!r}"
+        if not isinstance(alt, dict):
+            raise ImportanceError(f"{what}: expected a dict with the key 'function' (and 'cov'), got {alt!r}")
+        unknown = sorted(set(alt) - set(OPTION_KEYS))
+        if unknown:
+            raise ImportanceError(f"{what}: unknown key(s) {unknown}; valid keys: {list(OPTION_KEYS)}")
+        if alt.get("function") is None:
+            raise ImportanceError(f"{what}: no 'function' (the log-weight: a callable, a 'lambda ...' string or a "
+                                  "'package.module:name' string)")
+        try:
+            fn = parse_derived_function(str(name), alt["function"])
+        except UnsupportedModel as e:    # (the forms and checks of a derived function, under this option's name)
+            raise ImportanceError(f"importance: {e}") from e
+        if not fn.args:
+            raise ImportanceError(f"{what}: its function takes no arguments; they are bound by name to the sampled "
+                                  f"parameters {sampled}")
+        for a in fn.args:
+            if a in derived:
+                raise ImportanceError(f"{what}: argument {a!r} is a function-derived parameter, which is out of "
+                                      f"scope here; the arguments are sampled parameters ({sampled})")
+            if a not in sampled:
+                raise ImportanceError(f"{what}: argument {a!r} is not a sampled parameter; the sampled parameters "
+                                      f"are {sampled}")
+        cov = alt.get("cov")
+        if cov is not None and not isinstance(cov, (bool, np.bool_)):
+            raise ImportanceError(f"{what}: cov must be True, False or None, got {cov!r}")
+        if cov and d > MAX_COV_DIM:
+            raise ImportanceError(f"{what}: cov: True needs d <= {MAX_COV_DIM}, not d = {d} (means and variances "
+                                  "are kept at any d)")
+        out.append({"name": str(name), "function": fn, "cov": bool(d <= MAX_COV_DIM if cov is None else cov)})
+    return out
+
+
+# ---------------------------------------------------------------------------------- the sampler's side
+ENGINE_METHODS = ("configure_importance", "importance_layout", "importance_row_views", "accumulate_importance",
+                  "request_importance", "fetch_importance", "importance_set")
+
+
+class ImportanceAccumulator:
+    """What the sampler holds of the sums while it runs: a device product.
+
+    The sums are floats and the unfinished interval is NEVER split: it stays on the device, `_peek`
+    reads it without disturbing it (a request that does not close), and an interval is the closing
+    request's read-out alone: sums, counts and the c it was taken under.  `open`: the open interval as
+    last read, which is what a product is formed from once the engine is gone.  `eval_seconds`: host
+    time spent in the log-weight functions (queueing their torch operations)."""
+
+    name, reports = "importance", True
+
+    def __init__(self, cfg, spec, host):
+        self.cfg, self.spec, self.host, self.engine = cfg, spec, host, None
+        self.names = [a["name"] for a in cfg]
+        self.cov = [bool(a["cov"]) for a in cfg]
+        self.ivs, self.open, self.fetched = [], None, None
+        self.shift, self.G, self.eval_seconds = None, 0, 0.0
+
+    @classmethod
+    def from_option(cls, opt, spec, engine_factory, host):
+        try:
+            cfg = parse_option(opt, spec.sampled, [f.name for f in getattr(spec, "derived_functions", None) or []])
+        except ImportanceError as e:
+            host.fail("%s", str(e), cause=e)
+        if cfg is None:
+            return None
+        if host.temperature != 1:
+            host.fail("importance: the sums weigh the walkers as they are, which at temperature %g follow "
+                      "the tempered law, not the posterior; use temperature: 1 or turn importance off",
+                      host.temperature)
+        if not all(hasattr(engine_factory, m) for m in ENGINE_METHODS):
+            host.fail("importance: this engine keeps no importance sums (its library predates "
+                      "mcmc_hip_importance_*)")
+        if spec.d > MAX_DIM:
+            host.fail("importance: the importance kernel serves at most %d parameters, not %d", MAX_DIM, spec.d)
+        return cls(cfg, spec, host)
+
+    def attach(self, engine, resumed=False, centre=None, covmat=None):
+        """Hand the alternatives to the engine.  The sums are taken about the moment shift (`centre`);
+        a resumed run takes it from the state file: `load`."""
+        self.engine = engine
+        if centre is not None:
+            self.shift = np.array(centre, dtype=np.float64)
+        try:
+            engine.configure_importance(self.cov)
+            lay = engine.importance_layout()
+        except EngineError as e:
+            self.host.fail("importance: %s", str(e), cause=e)
+        self.G = int(lay["n_groups"])
+        want = sum(self.G * n_chains(self.spec.d, c) for c in self.cov)
+        if (lay["n_alt"], [bool(c) for c in lay["cov"]], lay["n_sums"]) != (len(self.cov), self.cov, want):
+            self.host.fail("importance: the engine lays its sums out differently (%r) from the product", lay)
+
+    # -- evaluation
+    def evaluate(self):
+        """Fill the log-weights from the state as it lies on the device: the functions in the option's
+        order, under the engine's stream.  Nothing synchronises with the host."""
+        import torch
+        t0 = time.perf_counter()
+        xrows, delta, stream = self.engine.importance_row_views()
+        rows = dict(zip(self.spec.sampled, xrows))
+        n = len(xrows[0])
+        with torch.cuda.stream(stream):
+            for k, alt in enumerate(self.cfg):
+                f, what = alt["function"], f"importance: alternative '{alt['name']}'"
+                try:
+                    val = f.function(*[rows[a] for a in f.args])
+                except Exception as e:
+                    raise EngineError(ERR_CALLBACK, f"{what}: its function raised {type(e).__name__}: {e}") from e
+                check_values(what, val, n, delta)
+                delta[k].copy_(val)
+        self.eval_seconds += time.perf_counter() - t0
+        return delta
+
+    # -- the device product
+    def accumulate(self):
+        self.engine.accumulate_importance(self.evaluate())
+
+    def request(self):
+        self.engine.request_importance(True)
+
+    def fetch_requested(self):
+        if self.fetched is None:
+            self.fetched = self.engine.fetch_importance()
+
+    def _peek(self, pending):
+        """The open interval, read WITHOUT disturbing it."""
+        eng = self.engine
+        if eng is not None:
+            if pending:
+                self.fetch_requested()
+            eng.request_importance(False)
+            self.open = eng.fetch_importance()
+        return self.open
+
+    def file(self, n_snap):
+        """The interval: what the closing request at this checkpoint read out."""
+        fetched, self.fetched = self.fetched, None
+        if fetched is None:    # (no read-out was queued: request and fetch now)
+            self.engine.request_importance(True)
+            fetched = self.engine.fetch_importance()
+        if n_snap:
+            self.ivs.append(fetched)
+
+    def drop(self, k):
+        self.ivs = self.ivs[k:]
+
+    def product(self, intervals, combined=False, pending=False):
+        """The intervals of the window, in their order, plus the unfinished interval."""
+        host = self.host
+        parts = list(self.ivs)
+        if self.fetched is not None:   # (requested, not filed yet: the newest interval)
+            parts.append(self.fetched)
+        last = self._peek(pending)
+        if last is not None:
+            parts.append(last)
+        shift = np.zeros(self.spec.d) if self.shift is None else self.shift
+        out = Importance.from_parts(self.names, self.spec.sampled, shift, self.cov, int(host.n_walkers), parts, self.G)
+        if combined and host.size > 1:
+            out = self._combined(out)
+        return out
+
+    def _reduced(self, buf):
+        res = self.host.all_reduce_sum(buf)
+        return buf if res is None else np.asarray(res).reshape(buf.shape)
+
+    def _combined(self, own):
+        """The groups of all processes side by side (every process has closed the same intervals):
+        one host all-reduce for the common C, one of a zero matrix in which every process fills its own
+        row with its sums scaled to it."""
+        host, na, G = self.host, len(self.names), own.n_groups
+        size, rank = int(host.size), int(host.rank)
+        if np.any(own.n >= np.uint64(2 ** 53)):
+            host.fail("importance: a count above 2^53 cannot be carried over processes exactly")
+        head = np.zeros((size, na + 2))
+        head[rank] = np.concatenate((own.C, [float(own.n_acc), float(G)]))
+        head = self._reduced(head.reshape(-1)).reshape(size, na + 2)
+        if not np.all(head[:, na:] == head[rank, na:]):
+            host.fail("importance: the processes hold different windows (accumulations, groups: %r)",
+                      head[:, na:].tolist())
+        C = head[:, :na].max(axis=0)
+        row = np.concatenate([s.reshape(-1) for s in own.scaled_to(C)]
+                             + [own.n.astype(np.float64).reshape(-1), own.n_zero.astype(np.float64),
+                                own.n_nonfinite.astype(np.float64), own.n_clamped.astype(np.float64)])
+        buf = np.zeros((size, len(row)))
+        buf[rank] = row
+        buf = self._reduced(buf.reshape(-1)).reshape(size, len(row))
+        n_sums = sum(s.size for s in own.sums)
+        sums = [np.concatenate(s, axis=0) for s in zip(*(split_sums(b[:n_sums], own.d, self.cov, G) for b in buf))]
+        n = np.concatenate([b[n_sums:n_sums + na * G].astype(np.uint64).reshape(na, G) for b in buf], axis=1)
+        cnt = buf[:, n_sums + na * G:].sum(axis=0).astype(np.int64).reshape(3, na)
+        return Importance(self.names, own.params, own.shift, self.cov, own.n_walkers * size, own.n_acc, C, sums, n,
+                          cnt[0], cnt[1], cnt[2])
+
+    # -- the state file
+    def _stack(self, parts):
+        k, na, G = len(parts), len(self.names), self.G
+        n_sums = sum(G * n_chains(self.spec.d, c) for c in self.cov)
+        return {"sums": np.array([p["sums"] for p in parts], dtype=np.float64).reshape(k, n_sums),
+                "n": np.array([p["n"] for p in parts], dtype=np.uint64).reshape(k, na, G),
+                "counters": np.array([p["counters"] for p in parts], dtype=np.uint64).reshape(k, na, 3),
+                "c": np.array([p["c"] for p in parts], dtype=np.float64).reshape(k, na),
+                "nacc": np.array([p["n_acc"] for p in parts], dtype=np.int64).reshape(k)}
+
+    @staticmethod
+    def _unstack(z, prefix):
+        return [{"sums": np.array(z[prefix + "sums"][i]), "n": np.array(z[prefix + "n"][i]),
+                 "counters": np.array(z[prefix + "counters"][i]), "c": np.array(z[prefix + "c"][i]),
+                 "n_acc": int(z[prefix + "nacc"][i])} for i in range(len(z[prefix + "nacc"]))]
+
+    def save(self, pending):
+        """What a resumed run must repeat (the alternatives' names and `cov`) and what it goes on from:
+        the shift, the intervals of the window and the open sums, c included."""
+        o = self._peek(pending)
+        out = {"iw_names": np.array(self.names, dtype=str), "iw_cov": np.array(self.cov, dtype=np.int64),
+               "iw_shift": np.zeros(self.spec.d) if self.shift is None else self.shift}
+        out.update({"iw_iv_" + k: v for k, v in self._stack(self.ivs).items()})
+        out.update({"iw_open_" + k: v for k, v in self._stack([o]).items()})
+        return out
+
+    def load(self, z, n_intervals):
+        """Resume: the alternatives must be the ones the sums were formed with (their names and `cov`;
+        the functions themselves cannot be compared); the shift, the window's intervals and the open
+        sums come back, c included: no new maximum is taken for an interval that is under way."""
+        fail = self.host.fail
+        if "iw_names" not in z:
+            fail("importance: cannot resume -- the run was written without importance (the window of its "
+                 "sums cannot begin in mid-run)")
+        saved = ([str(n) for n in z["iw_names"]], [bool(c) for c in z["iw_cov"]])
+        if saved != (self.names, self.cov):
+            fail("importance: cannot resume -- the run was written with the alternatives %r (cov: %r), and now "
+                 "has %r (cov: %r): sums of different weights do not add up", *saved, self.names, self.cov)
+        self.shift = np.array(z["iw_shift"], dtype=np.float64)
+        self.ivs = self._unstack(z, "iw_iv_")
+        if len(self.ivs) != n_intervals:
+            fail("importance: the state file holds %d interval sums for %d intervals", len(self.ivs), n_intervals)
+        self.open = self._unstack(z, "iw_open_")[0]
+        try:
+            self.engine.importance_set(self.open)
+        except EngineError as e:
+            fail("importance: %s", str(e), cause=e)
+
+    def detach(self, pending=False):
+        if self.engine is not None:
+            self._peek(pending)       # (kept for product() after the engine is gone)
+        self.engine = None

@@ -43,6 +43,7 @@ from .derived import DerivedAccumulator
 from .engine import (ChainStuck, Engine, EngineError, NotPositiveDefinite, gelman_rubin,
                      incremental_supported)
 from .evidence import EvidenceAccumulator
+from .importance import ImportanceAccumulator
 from .marginals import MarginalsAccumulator
 from .model import ProblemSpec, UnsupportedModel
 
@@ -187,6 +188,16 @@ HIP_DEFAULTS = {
                               # parameters exist.  {"cross": [names] | "all" | None}: the sampled
                               # parameters whose cross-moments are kept.  False: no moment kernel (rows
                               # and marginals still get their values).  Needs temperature: 1
+    "importance": None,       # importance reweighting of the ensemble (Cobaya's `post`, for the moments):
+                              # {name: {"function": log-weight, "cov": True | False | None}}, 1..8
+                              # alternatives.  `function` is a batched device function of the sampled
+                              # parameters, bound by name (a callable, "package.module:name" or "lambda
+                              # a, b: ..." with `torch` and `math`), returning ln(new posterior / sampled
+                              # posterior) per walker up to a constant.  Weighted means, variances and
+                              # (cov: the default for d <= 128) covariances, the effective sample size and
+                              # ln(Z_new / Z) with jackknife errors, summed on the device from EVERY walker
+                              # of every moment snapshot of the window -- products()["importance"], a
+                              # `cobaya_amd.importance.Importance`.  None: off.  Needs temperature: 1
     "shared_basis": True,     # True: the walkers of a group share one Haar basis per cycle;
                               # False: every walker draws its own (proposal.py:59-69 to the
                               # letter: the reference-faithful control, much slower)
@@ -267,13 +278,13 @@ class EnsembleMCMC:
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
     MAX_DIM = 128    # ctx.h: kMaxDimBig, every path (mixtures: at most 64 modes, model.py)
     HUGE_MAX_MODES = 4   # 128 < d <= max_dim(): huge_kernels.hip (huge_args.h: kHugeMaxModes)
-    marginals = autocorr = bestfit = evidence = derived_stats = None     # (the options' default)
+    marginals = autocorr = bestfit = evidence = derived_stats = importance = None     # (the options' default)
     # What is accumulated on the device beside every moment snapshot (marginals.py states the
     # methods): a new product is one such class, appended here.  `_products`: those that are on
     # (DerivedAccumulator FIRST: it configures the derived rows before the marginals that may read
     # them, and fills them before those are binned)
     PRODUCT_CLASSES = (DerivedAccumulator, MarginalsAccumulator, AutoCorrAccumulator, BestFitAccumulator,
-                       EvidenceAccumulator)
+                       EvidenceAccumulator, ImportanceAccumulator)
     _products = ()
     _derived = None      # the DerivedAccumulator, where the model has function-derived parameters
 
@@ -906,7 +917,9 @@ class EnsembleMCMC:
             out = p.product(self._intervals, combined=True, pending=self._ckpt_pending)
             if self.output and self.rank == 0:
                 out.save(self._out_file("." + p.name + ".npz"))
-            if p.reports:
+            if p.reports and hasattr(out, "report"):   # (several lines, some of them warnings)
+                out.report(self.log)
+            elif p.reports:
                 self.log.info("%s", out.summary())
 
     def advance(self):

@@ -525,6 +525,38 @@ MCMC_HIP_API int mcmc_hip_derived_set(mcmc_hip_ctx* h, uint64_t n_used, const do
                          const double* C, const double* X, const double* V, const uint64_t* bad,
                          const double* min, const double* max, int64_t n_accumulations);
 
+/* Importance reweighting: the weighted sums of the sampled parameters under w = exp(delta)
+ * (importance_kernels.hip).  The rule ("Importance").  The CALLER owns the
+ * log-weights delta[n_alt][W] (row k: alternative k) and fills them on the engine's stream from the state
+ * x[d][W], whose device pointer `layout` hands out.
+ * configure: n_alt alternatives (0: off, everything is freed; at most 8), cov[k] != 0: alternative k
+ *   keeps the full weighted covariance (d <= 128).  Per (alternative, group) the chains are
+ *   S1 | S2 | M[d] | V[d] | Q[d (d - 1) / 2] with (i, j < i) at i (i - 1) / 2 + j, Q with cov[k] alone;
+ *   `sums` holds alternative k's [n_groups][n_chains] doubles at offsets[k], n_sums doubles in all.
+ * accumulate: queues one accumulation of every walker of this process on the engine's stream.  The first
+ *   accumulation after configure, a closing request or a set with n_accumulations = 0 OPENS an interval:
+ *   c[k] = the exact maximum of the finite delta[k] (0.0: none) is taken on the device first.
+ * request: queues the read-out behind the work already in the stream; close != 0: also zeroes the sums.
+ * fetch: waits for the copy only.  n[n_alt][n_groups] the used walkers, counters[n_alt][3] = zero,
+ *   nonfinite, clamped, c[n_alt].
+ * set: restores an unfinished interval (resume).
+ * set_group_size: the groups of the sums (default: the engine's group_size), any divisor of n_walkers;
+ *   the sums are dropped.
+ * Before configure, accumulate / request / set answer MCMC_HIP_ERR_STATE and nothing is allocated or
+ * launched.  layout: any pointer may be NULL (offsets, cov: 8 entries each); n_alt == 0: off. */
+MCMC_HIP_API int mcmc_hip_importance_configure(mcmc_hip_ctx* h, int32_t n_alt, const int32_t* cov);
+MCMC_HIP_API int mcmc_hip_importance_set_group_size(mcmc_hip_ctx* h, int32_t group_size);
+MCMC_HIP_API int mcmc_hip_importance_layout(const mcmc_hip_ctx* h, int32_t* n_alt, int32_t* n_groups,
+                               int64_t* n_sums, int64_t* offsets, int32_t* cov, int64_t* n_accumulations,
+                               uint64_t* x_device_ptr);
+MCMC_HIP_API int mcmc_hip_importance_accumulate(mcmc_hip_ctx* h, uint64_t delta_device_ptr);
+MCMC_HIP_API int mcmc_hip_importance_request(mcmc_hip_ctx* h, int32_t close);
+MCMC_HIP_API int mcmc_hip_importance_fetch(mcmc_hip_ctx* h, double* sums, int64_t n_sums, uint64_t* n,
+                              int64_t n_groups, uint64_t* counters, double* c, int64_t* n_accumulations);
+MCMC_HIP_API int mcmc_hip_importance_set(mcmc_hip_ctx* h, const double* sums, int64_t n_sums, const uint64_t* n,
+                            int64_t n_groups, const uint64_t* counters, const double* c,
+                            int64_t n_accumulations);
+
 /* The learn / convergence checkpoint ON THE DEVICE (MCMC.check_convergence_and_learn_proposal,
  * mcmc.py:773-1032; checkpoint_kernels.hip): the intervals between checkpoints are kept in a
  * device ring, the statistics of the window (the later half of the run, mcmc.py:787-790) are

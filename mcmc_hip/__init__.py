@@ -61,6 +61,7 @@ else:
         bestfit: bool | dict | None = HIP_DEFAULTS["bestfit"]
         evidence: bool | dict | None = HIP_DEFAULTS["evidence"]
         derived_stats: bool | dict | None = HIP_DEFAULTS["derived_stats"]
+        importance: dict | None = HIP_DEFAULTS["importance"]
 
         def _export_collection(self, coll):
             """Our table -> `cobaya.collection.SampleCollection` (same columns,
@@ -97,6 +98,8 @@ else:
                 # the moments of function-derived parameters (standalone runs: the hosted path leaves
                 # derived parameters to Cobaya's Model)
                 regexps.append((re.compile(output.prefix_regexp_str + r"derived\.npz$"), None))
+                # the weighted sums of `importance` (written once, at the end of the run)
+                regexps.append((re.compile(output.prefix_regexp_str + r"importance\.npz$"), None))
             return regexps
 
 
