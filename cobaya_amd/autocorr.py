@@ -21,6 +21,7 @@ import math
 import numpy as np
 
 from .engine import EngineError
+from .product import DeviceProduct, option_dict, option_int
 
 MAX_LAGS = 64               # autocorr_args.h: kAcMaxLags
 DEFAULT_LAGS = 16
@@ -191,16 +192,10 @@ def parse_option(opt, sampled):
     """The sampler option `autocorr` -> None (off) or {"params": [names], "lags": L}.  `True` = every
     sampled parameter, 16 lags.  Refuses, by the option's name, unknown keys and parameter names,
     a parameter listed twice and `lags` outside 1..64."""
-    if opt is None or opt is False:
+    opt = option_dict(opt, "autocorr", OPTION_KEYS, AutoCorrError)
+    if opt is None:
         return None
     sampled = list(sampled)
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise AutoCorrError(f"autocorr: expected True, None or a dict, got {opt!r}")
-    unknown = sorted(set(opt) - set(OPTION_KEYS))
-    if unknown:
-        raise AutoCorrError(f"autocorr: unknown key(s) {unknown}; valid keys: {list(OPTION_KEYS)}")
     params = opt.get("params", "all")
     if isinstance(params, str):
         if params != "all":
@@ -215,11 +210,8 @@ def parse_option(opt, sampled):
     if len(set(params)) != len(params):
         twice = sorted({n for n in params if params.count(n) > 1})
         raise AutoCorrError(f"autocorr: params lists {twice} twice")
-    lags = opt.get("lags", DEFAULT_LAGS)
-    if isinstance(lags, bool) or not isinstance(lags, (int, np.integer, float)) or int(lags) != lags \
-            or not 1 <= int(lags) <= MAX_LAGS:
-        raise AutoCorrError(f"autocorr: lags must be an integer in 1..{MAX_LAGS}, got {lags!r}")
-    return {"params": params, "lags": int(lags)}
+    lags = option_int(opt.get("lags", DEFAULT_LAGS), "autocorr: lags", 1, MAX_LAGS, AutoCorrError)
+    return {"params": params, "lags": lags}
 
 
 # ---------------------------------------------------------------------------------- the sampler's side
@@ -227,39 +219,27 @@ ENGINE_METHODS = ("configure_autocorr", "accumulate_autocorr", "request_autocorr
                   "autocorr_set", "autocorr_reset", "autocorr_layout")
 
 
-class AutoCorrAccumulator:
-    """What the sampler holds of the sums while it runs: a device product, with the methods
-    `marginals.MarginalsAccumulator` states.
+class AutoCorrAccumulator(DeviceProduct):
+    """What the sampler holds of the sums while it runs: a device product whose unfinished interval
+    is never split.  A part is (sums, pairs per lag); the peek reads out and sets back."""
 
-    HERE the sums are floats and the unfinished interval is NEVER split: it stays on the device,
-    `_peek` reads it without disturbing it, and an interval's sums are the requested read-out alone
-    (a host part would change the order of the additions, hence the bits).  `open`: the open sums
-    as last read, which is what a product is formed from once the engine is gone."""
+    name, error, ENGINE_METHODS = "autocorr", AutoCorrError, ENGINE_METHODS
+    predates = "autocorr: this engine has no lagged cross-products (its library predates mcmc_hip_autocorr_*)"
 
-    name, reports = "autocorr", True
-
-    def __init__(self, cfg, spec, host):
-        self.cfg, self.spec, self.host, self.engine = cfg, spec, host, None
-        self.ivs, self.open, self.fetched = [], None, None
+    @staticmethod
+    def parse(opt, spec):
+        return parse_option(opt, spec.sampled)
 
     @classmethod
     def from_option(cls, opt, spec, engine_factory, host):
-        try:
-            cfg = parse_option(opt, spec.sampled)
-        except AutoCorrError as e:
-            host.fail("%s", str(e), cause=e)
-        if cfg is None:
-            return None
-        if not all(hasattr(engine_factory, m) for m in ENGINE_METHODS):
-            host.fail("autocorr: this engine has no lagged cross-products (its library predates "
-                      "mcmc_hip_autocorr_*)")
-        cfg["interval_steps"] = int(host.snapshot_steps)   # one lag, fixed for the run
-        return cls(cfg, spec, host)
+        self = super().from_option(opt, spec, engine_factory, host)
+        if self is not None:
+            self.cfg["interval_steps"] = int(host.snapshot_steps)   # one lag, fixed for the run
+        return self
 
     def attach(self, engine, resumed=False, centre=None, covmat=None):
         """Hand the configuration to the engine (which allocates the ring, or refuses it)."""
         cfg, self.engine = self.cfg, engine
-        self.accumulate, self.request = engine.accumulate_autocorr, engine.request_autocorr
         try:
             engine.configure_autocorr([self.spec.sampled.index(n) for n in cfg["params"]], cfg["lags"])
         except EngineError as e:
@@ -273,44 +253,11 @@ class AutoCorrAccumulator:
         L1 = self.cfg["lags"] + 1
         return np.zeros((3, L1, len(self.cfg["params"]))), np.zeros(L1, np.int64)
 
-    def fetch_requested(self):
-        if self.fetched is None:
-            self.fetched = self.engine.fetch_autocorr()
-
-    def _peek(self, pending):
-        """The sums of the unfinished interval, read WITHOUT disturbing them: read out (which zeroes
-        them in stream order) and set back to the same values, so that the device goes on adding
-        to exactly the numbers it held."""
-        eng = self.engine
-        if eng is not None:
-            if pending:
-                self.fetch_requested()
-            eng.request_autocorr()
-            self.open = eng.fetch_autocorr()
-            eng.autocorr_set(*self.open)
-        return self.open
-
-    def file(self, n_snap):
-        """The interval's sums: what the request at this checkpoint read out."""
-        fetched, self.fetched = self.fetched, None
-        if fetched is None:    # (no read-out was queued: request and fetch now)
-            self.engine.request_autocorr()
-            fetched = self.engine.fetch_autocorr()
-        if n_snap:
-            self.ivs.append(fetched)
-
-    def drop(self, k):
-        self.ivs = self.ivs[k:]
-
     def product(self, intervals, combined=False, pending=False):
         """The intervals of the window, in their order, plus the unfinished interval."""
         cfg, host = self.cfg, self.host
         sums, n_pairs = self._zero()
-        parts = list(self.ivs)
-        if self.fetched is not None:   # (requested, not filed yet: the newest interval)
-            parts.append(self.fetched)
-        parts.append(self._peek(pending))
-        for s_, n_ in parts:
+        for s_, n_ in self._parts(pending):
             sums = sums + s_
             n_pairs = n_pairs + n_
         n_walkers = int(host.n_walkers)
@@ -357,8 +304,3 @@ class AutoCorrAccumulator:
         # the unfinished interval goes back to the device, where the next accumulation adds to it
         self.engine.autocorr_set(z["ac_open"], z["ac_open_pairs"])
         self.open = (np.array(z["ac_open"], dtype=np.float64), np.array(z["ac_open_pairs"], dtype=np.int64))
-
-    def detach(self, pending=False):
-        if self.open is not None:
-            self._peek(pending)       # (kept for product() after the engine is gone)
-        self.engine = self.accumulate = self.request = None

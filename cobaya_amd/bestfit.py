@@ -21,6 +21,7 @@ import numpy as np
 
 from .engine import EngineError
 from .marginals import MarginalsError, resolve_ranges
+from .product import DeviceProduct, option_dict, option_int, option_ranges
 
 MAX_BINS = 1024             # bestfit_args.h: kBfMaxBins
 RECORD_HEAD = 6             # bestfit_args.h: kBfRecordHead -- key, walker, step, logpost, logprior, loglike
@@ -222,16 +223,10 @@ def parse_option(opt, sampled):
     dict | "prior" | "covmat", "quantity"}.  `True` = both records and the profile of every
     sampled parameter; "params": None = the records only.  Refuses, by the option's name, unknown
     keys and parameter names, a bin count out of range, bad ranges and an unknown quantity."""
-    if opt is None or opt is False:
+    opt = option_dict(opt, "bestfit", OPTION_KEYS, BestFitError, {"params": "all"})
+    if opt is None:
         return None
     sampled = list(sampled)
-    if opt is True:
-        opt = {"params": "all"}
-    if not isinstance(opt, dict):
-        raise BestFitError(f"bestfit: expected True, None or a dict, got {opt!r}")
-    unknown = sorted(set(opt) - set(OPTION_KEYS))
-    if unknown:
-        raise BestFitError(f"bestfit: unknown key(s) {unknown}; valid keys: {list(OPTION_KEYS)}")
     params = opt.get("params", "all")
     if isinstance(params, str):
         if params != "all":
@@ -243,35 +238,12 @@ def parse_option(opt, sampled):
         raise BestFitError(f"bestfit: unknown parameter name(s) {bad}; the sampled parameters are {sampled}")
     if len(set(params)) != len(params):
         raise BestFitError("bestfit: params lists a parameter twice")
-    bins = opt.get("bins", 64)
-    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer, float)) or int(bins) != bins \
-            or not 1 <= int(bins) <= MAX_BINS:
-        raise BestFitError(f"bestfit: bins must be an integer in 1..{MAX_BINS}, got {bins!r}")
+    bins = option_int(opt.get("bins", 64), "bestfit: bins", 1, MAX_BINS, BestFitError)
     quantity = opt.get("quantity", "loglike")
     if quantity not in QUANTITIES:
         raise BestFitError(f"bestfit: quantity must be one of {list(QUANTITIES)}, got {quantity!r}")
-    ranges = opt.get("ranges", "prior")
-    if isinstance(ranges, str):
-        if ranges not in ("prior", "covmat"):
-            raise BestFitError(f"bestfit: ranges must be a dict, 'prior' or 'covmat', got {ranges!r}")
-    elif isinstance(ranges, dict):
-        bad = sorted(str(n) for n in ranges if n not in sampled)
-        if bad:
-            raise BestFitError(f"bestfit: ranges names unknown parameter(s) {bad}")
-        clean = {}
-        for n, r in ranges.items():
-            try:
-                lo, hi = float(r[0]), float(r[1])
-                ok = len(r) == 2
-            except (TypeError, ValueError, IndexError):
-                ok = False
-            if not ok or not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
-                raise BestFitError(f"bestfit: ranges[{n!r}] must be a finite [lo, hi] with lo < hi, got {r!r}")
-            clean[str(n)] = (lo, hi)
-        ranges = clean
-    else:
-        raise BestFitError(f"bestfit: ranges must be a dict, 'prior' or 'covmat', got {ranges!r}")
-    return {"params": params, "bins": int(bins), "ranges": ranges, "quantity": str(quantity)}
+    ranges = option_ranges(opt.get("ranges", "prior"), "bestfit", sampled, BestFitError)
+    return {"params": params, "bins": bins, "ranges": ranges, "quantity": str(quantity)}
 
 
 def _resolve(cfg, spec, centre=None, covmat=None):
@@ -289,38 +261,27 @@ ENGINE_METHODS = ("configure_bestfit", "accumulate_bestfit", "request_bestfit", 
                   "bestfit_set")
 
 
-class BestFitAccumulator:
-    """What the sampler holds of the records and profiles while it runs: the methods of a device
-    product (`marginals.MarginalsAccumulator`).  One (slab, records) per checkpoint interval of the
-    window (`ivs`), dropped with it: the product is the maximum over the later half of the run plus
-    the unfinished interval.  A maximum is exact, so the unfinished interval is split the way the
-    marginals' counts are: `open` is the host's part (slab, records, accumulations), the device
-    holds the rest, and `_drain` moves that over (which empties it on the device)."""
+class BestFitAccumulator(DeviceProduct):
+    """What the sampler holds of the records and profiles while it runs: a device product whose
+    unfinished interval is split (a maximum is exact).  A part is (slab, records, accumulations);
+    `ivs` keeps one (slab, records) per checkpoint interval of the window, dropped with it: the
+    product is the maximum over the later half of the run plus the unfinished interval."""
 
-    name, reports = "bestfit", True
+    name, split, error, ENGINE_METHODS = "bestfit", True, BestFitError, ENGINE_METHODS
+    predates = "bestfit: this engine keeps no best fit and profiles (its library predates mcmc_hip_bestfit_*)"
+    _merge = staticmethod(_merge)
 
-    def __init__(self, cfg, spec, host):
-        self.cfg, self.spec, self.host, self.engine = cfg, spec, host, None
-        self.ivs, self.open, self.fetched = [], None, None
+    @staticmethod
+    def parse(opt, spec):
+        return parse_option(opt, spec.sampled)
 
-    @classmethod
-    def from_option(cls, opt, spec, engine_factory, host):
-        try:
-            cfg = parse_option(opt, spec.sampled)
-        except BestFitError as e:
-            host.fail("%s", str(e), cause=e)
-        if cfg is None:
-            return None
-        if not all(hasattr(engine_factory, m) for m in ENGINE_METHODS):
-            host.fail("bestfit: this engine keeps no best fit and profiles (its library predates "
-                      "mcmc_hip_bestfit_*)")
-        return cls(cfg, spec, host)
+    def _kept(self, part):
+        return part[:2]
 
     def attach(self, engine, resumed=False, centre=None, covmat=None):
         """Fix the ranges and hand the layout to the engine.  A resumed run repeats the ranges of
         the state file: `load` configures the engine."""
         self.engine = engine
-        self.accumulate, self.request = engine.accumulate_bestfit, engine.request_bestfit
         if resumed:
             return
         try:
@@ -353,38 +314,9 @@ class BestFitAccumulator:
                 fail("bestfit: the engine lays its slab and records out differently (%r) from the "
                      "product (%d keys, %d words)", lay, self.open[0].size, self.open[1].size)
 
-    def fetch_requested(self):
-        if self.fetched is None:
-            self.fetched = self.engine.fetch_bestfit()
-
-    def _drain(self, pending):
-        """Move what the device holds of the unfinished interval into `open`."""
-        if pending:
-            self.fetch_requested()
-        self.engine.request_bestfit()
-        self.open = _merge(self.open, self.engine.fetch_bestfit())
-
-    def file(self, n_snap):
-        """The interval's part: what the request read out merged with what the host held of it."""
-        part = self.open if self.fetched is None else _merge(self.open, self.fetched)
-        self.fetched = None
-        self.open = self._empty()
-        if n_snap:
-            self.ivs.append(part[:2])
-
-    def drop(self, k):
-        self.ivs = self.ivs[k:]
-
     def product(self, intervals, combined=False, pending=False):
         cfg, host = self.cfg, self.host
-        if self.engine is not None:
-            self._drain(pending)
-        part = self.open
-        if self.fetched is not None:   # (requested, not filed yet: the newest interval)
-            part = _merge(part, self.fetched)
-        for (n_snap, _, _), (slab, rec) in zip(intervals, self.ivs):
-            part = _merge(part, (slab, rec, n_snap))
-        slab, rec, n_acc = part
+        slab, rec, n_acc = self._merged(intervals, pending)
         n_samples = n_acc * int(host.n_walkers)
         if combined and host.size > 1:
             # ONE host all-reduce of a zero matrix in which every process fills its own row: the
@@ -453,8 +385,3 @@ class BestFitAccumulator:
                  len(self.ivs), n_intervals)
         # the unfinished interval goes back to the device, where the next accumulation goes on from it
         self.engine.bestfit_set(z["bf_open_slab"], z["bf_open_rec"], int(z["bf_open_n"]))
-
-    def detach(self, pending=False):
-        if self.engine is not None and self.open is not None:
-            self._drain(pending)     # (the device's part of the unfinished interval)
-        self.engine = self.accumulate = self.request = None

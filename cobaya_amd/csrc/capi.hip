@@ -416,27 +416,8 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     h->bd.ring.release(); h->bd.bounds.release(); h->bd.payload.release();
     if (h->bd.pin) (void)hipHostFree(h->bd.pin);
     if (h->ck.pin_out) (void)hipHostFree(h->ck.pin_out);
-    h->mg.slab.release(); h->mg.entries.release();
-    if (h->mg.pin) (void)hipHostFree(h->mg.pin);
-    if (h->mg.ev) (void)hipEventDestroy(h->mg.ev);
-    h->ac.ring.release(); h->ac.ringS.release(); h->ac.Pg.release(); h->ac.acc.release();
-    h->ac.dims.release();
-    if (h->ac.pin) (void)hipHostFree(h->ac.pin);
-    if (h->ac.ev) (void)hipEventDestroy(h->ac.ev);
-    h->bf.slab.release(); h->bf.records.release(); h->bf.cand.release(); h->bf.entries.release();
-    if (h->bf.pin) (void)hipHostFree(h->bf.pin);
-    if (h->bf.ev) (void)hipEventDestroy(h->bf.ev);
-    h->evd.slab.release(); h->evd.ell.release(); h->evd.s.release();
-    if (h->evd.pin) (void)hipHostFree(h->evd.pin);
-    if (h->evd.pin_ell) (void)hipHostFree(h->evd.pin_ell);
-    if (h->evd.ev) (void)hipEventDestroy(h->evd.ev);
-    h->dv.z.release(); h->dv.Sg.release(); h->dv.shift.release(); h->dv.Ng.release(); h->dv.slab.release();
-    h->dv.cross.release();
-    if (h->dv.pin) (void)hipHostFree(h->dv.pin);
-    if (h->dv.ev) (void)hipEventDestroy(h->dv.ev);
-    h->imp.slab.release();
-    if (h->imp.pin) (void)hipHostFree(h->imp.pin);
-    if (h->imp.ev) (void)hipEventDestroy(h->imp.ev);
+    destroy_product(h->mg); destroy_product(h->ac); destroy_product(h->bf);
+    destroy_product(h->evd); destroy_product(h->dv); destroy_product(h->imp);
     if (h->ck.ev) (void)hipEventDestroy(h->ck.ev);
     if (h->pin_mom) (void)hipHostFree(h->pin_mom);
     if (h->pin_T) (void)hipHostFree(h->pin_T);
@@ -1117,11 +1098,11 @@ int mcmc_hip_set_moment_shift(mcmc_hip_ctx* h, const double* shift)
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipMemcpyAsync(h->dshift.p, h->shift.data(), sizeof(double) * h->d,
                               hipMemcpyHostToDevice, h->stream));
-    if (changed && h->ac.acc.p) {
+    if (changed && h->ac.ro.on()) {
         // the autocorrelation ring's group sums and the open accumulators refer to the old shift
         h->ac.held = h->ac.head = 0;
         std::fill(h->ac.n_pairs.begin(), h->ac.n_pairs.end(), (int64_t)0);
-        HIP_TRY(h, hipMemsetAsync(h->ac.acc.p, 0, sizeof(double) * h->ac.acc.n, h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->ac.ro.slab, 0, h->ac.ro.bytes(), h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MCMC_HIP_OK;

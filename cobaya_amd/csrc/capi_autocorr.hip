@@ -1,24 +1,7 @@
 // libmcmc_hip.so: lagged cross-products of the ensemble for the integrated autocorrelation time
-// (autocorr_kernels.hip).  Life cycle of the marginals: configure once, accumulate beside every
-// moment snapshot, request / fetch at a checkpoint (the hot loop is never stalled), set on resume.
+// (autocorr_kernels.hip).  The life cycle is the Readout's (readout.h), but what is counted is pairs
+// per lag, not accumulations.
 #include "ctx.h"
-
-namespace {
-
-void ac_release(mcmc_hip_ctx* h)
-{
-    auto& A = h->ac;
-    A.ring.release(); A.ringS.release(); A.Pg.release(); A.acc.release(); A.dims.release();
-    if (A.pin) (void)hipHostFree(A.pin);
-    A.pin = nullptr;
-    A.n = A.lags = A.rows_per_pass = A.held = A.head = 0;
-    A.n_pairs.clear(); A.pend_pairs.clear();
-    A.pending = false;
-}
-
-size_t ac_doubles(const mcmc_hip_ctx* h) { return (size_t)3 * (h->ac.lags + 1) * h->ac.n; }
-
-}  // namespace
 
 extern "C" {
 
@@ -29,7 +12,7 @@ int mcmc_hip_autocorr_configure(mcmc_hip_ctx* h, int32_t n_dims, const int32_t* 
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (n_dims == 0) {
-        ac_release(h);
+        h->ac.release();
         return MCMC_HIP_OK;
     }
     if (!dims) return fail(h, MCMC_HIP_ERR_ARG, "dims is null");
@@ -47,7 +30,8 @@ int mcmc_hip_autocorr_configure(mcmc_hip_ctx* h, int32_t n_dims, const int32_t* 
     const int rows = mcmc_hip_autocorr_rows_per_pass(h->gs, lags);
     if (rows < 1)
         return fail(h, MCMC_HIP_ERR_ARG, "lags = %d: a group of %d walkers does not fit the kernel's tile", lags, h->gs);
-    ac_release(h);
+    auto& A = h->ac;
+    A.release();
     const size_t slots = (size_t)lags + 1, n = (size_t)n_dims;
     const size_t n_ring = slots * n * (size_t)h->W, n_S = slots * (size_t)h->G * n, n_acc = 3 * slots * n;
     const size_t need = sizeof(double) * (n_ring + 2 * n_S + n_acc) + sizeof(int) * n;
@@ -56,16 +40,12 @@ int mcmc_hip_autocorr_configure(mcmc_hip_ctx* h, int32_t n_dims, const int32_t* 
     if (need > free_b)
         return fail(h, MCMC_HIP_ERR_ARG, "lags = %d: the ring of %d snapshots of %d parameters x %d walkers needs "
                     "%zu bytes of device memory, %zu are free", lags, lags + 1, n_dims, h->W, need, free_b);
-    auto& A = h->ac;
-    HIP_TRY(h, A.ring.resize(n_ring));
-    HIP_TRY(h, A.ringS.resize(n_S));
-    HIP_TRY(h, A.Pg.resize(n_S));
-    HIP_TRY(h, A.acc.resize(n_acc));
-    HIP_TRY(h, A.dims.resize(n));
-    HIP_TRY(h, hipHostMalloc((void**)&A.pin, sizeof(double) * n_acc, hipHostMallocDefault));
-    if (!A.ev) HIP_TRY(h, hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
-    HIP_TRY(h, hipMemcpy(A.dims.p, dims, sizeof(int) * n, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemset(A.acc.p, 0, sizeof(double) * n_acc));
+    HIP_TRY_BUILD(h, A, A.ring.resize(n_ring));
+    HIP_TRY_BUILD(h, A, A.ringS.resize(n_S));
+    HIP_TRY_BUILD(h, A, A.Pg.resize(n_S));
+    HIP_TRY_BUILD(h, A, A.ro.alloc(n_acc, h->stream));
+    HIP_TRY_BUILD(h, A, A.dims.resize(n));
+    HIP_TRY_BUILD(h, A, hipMemcpy(A.dims.p, dims, sizeof(int) * n, hipMemcpyHostToDevice));
     A.n = n_dims; A.lags = lags; A.rows_per_pass = rows;
     A.n_pairs.assign(slots, 0);
     A.pend_pairs.assign(slots, 0);
@@ -79,7 +59,7 @@ int mcmc_hip_autocorr_layout(const mcmc_hip_ctx* h, int32_t* n_dims, int32_t* la
     const auto& A = h->ac;
     if (n_dims) *n_dims = A.n;
     if (lags) *lags = A.lags;
-    if (n_doubles) *n_doubles = A.acc.p ? (int64_t)ac_doubles(h) : 0;
+    if (n_doubles) *n_doubles = (int64_t)A.ro.n_words;
     if (held) *held = A.held;
     return MCMC_HIP_OK;
 }
@@ -88,13 +68,13 @@ int mcmc_hip_autocorr_accumulate(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& A = h->ac;
-    if (!A.acc.p) return fail(h, MCMC_HIP_ERR_STATE, "autocorr_configure must precede autocorr_accumulate");
+    if (!A.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "autocorr_configure must precede autocorr_accumulate");
     if (!h->have_state) return fail(h, MCMC_HIP_ERR_STATE, "no state");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const int held = std::min(A.held + 1, A.lags + 1);
     mcmc::AcArgs a{};
     a.x = h->x.p; a.shift = h->dshift.p; a.dims = A.dims.p;
-    a.ring = A.ring.p; a.ringS = A.ringS.p; a.Pg = A.Pg.p; a.acc = A.acc.p;
+    a.ring = A.ring.p; a.ringS = A.ringS.p; a.Pg = A.Pg.p; a.acc = A.ro.dev<double>();
     a.W = h->W; a.G = h->G; a.gs = h->gs; a.n = A.n; a.lags = A.lags;
     a.held = held; a.head = A.head; a.rows_per_pass = A.rows_per_pass;
     HIP_TRY(h, mcmc_hip_launch_autocorr(&a, h->stream));
@@ -108,16 +88,13 @@ int mcmc_hip_autocorr_request(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& A = h->ac;
-    if (!A.acc.p) return fail(h, MCMC_HIP_ERR_STATE, "autocorr_configure must precede autocorr_request");
-    if (A.pending) return fail(h, MCMC_HIP_ERR_STATE, "an autocorr request is already pending");
+    if (!A.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "autocorr_configure must precede autocorr_request");
+    if (A.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "an autocorr request is already pending");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t bytes = sizeof(double) * ac_doubles(h);
-    HIP_TRY(h, hipMemcpyAsync(A.pin, A.acc.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemsetAsync(A.acc.p, 0, bytes, h->stream));
-    HIP_TRY(h, hipEventRecord(A.ev, h->stream));
+    HIP_TRY(h, A.ro.copy_out(h->stream, A.ro.n_words));
+    HIP_TRY(h, A.ro.mark(h->stream));
     A.pend_pairs = A.n_pairs;
     std::fill(A.n_pairs.begin(), A.n_pairs.end(), (int64_t)0);
-    A.pending = true;
     return MCMC_HIP_OK;
 }
 
@@ -125,14 +102,13 @@ int mcmc_hip_autocorr_fetch(mcmc_hip_ctx* h, double* sums, int64_t n, int64_t* n
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& A = h->ac;
-    if (!A.pending) return fail(h, MCMC_HIP_ERR_STATE, "no autocorr request is pending");
-    if (!sums || (size_t)n != ac_doubles(h))
-        return fail(h, MCMC_HIP_ERR_ARG, "sums: the accumulators hold %zu doubles, not %lld", ac_doubles(h), (long long)n);
+    if (!A.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "no autocorr request is pending");
+    if (!sums || (size_t)n != A.ro.n_words)
+        return fail(h, MCMC_HIP_ERR_ARG, "sums: the accumulators hold %zu doubles, not %lld", A.ro.n_words, (long long)n);
     if (!n_pairs) return fail(h, MCMC_HIP_ERR_ARG, "n_pairs is null");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipEventSynchronize(A.ev));
-    A.pending = false;
-    std::copy(A.pin, A.pin + ac_doubles(h), sums);
+    HIP_TRY(h, A.ro.wait());
+    std::copy(A.ro.host<double>(), A.ro.host<double>() + A.ro.n_words, sums);
     std::copy(A.pend_pairs.begin(), A.pend_pairs.end(), n_pairs);
     return MCMC_HIP_OK;
 }
@@ -141,16 +117,16 @@ int mcmc_hip_autocorr_set(mcmc_hip_ctx* h, const double* sums, int64_t n, const 
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& A = h->ac;
-    if (!A.acc.p) return fail(h, MCMC_HIP_ERR_STATE, "autocorr_configure must precede autocorr_set");
-    if (A.pending) return fail(h, MCMC_HIP_ERR_STATE, "an autocorr request is pending (fetch it first)");
-    if (!sums || (size_t)n != ac_doubles(h))
-        return fail(h, MCMC_HIP_ERR_ARG, "sums: the accumulators hold %zu doubles, not %lld", ac_doubles(h), (long long)n);
+    if (!A.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "autocorr_configure must precede autocorr_set");
+    if (A.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "an autocorr request is pending (fetch it first)");
+    if (!sums || (size_t)n != A.ro.n_words)
+        return fail(h, MCMC_HIP_ERR_ARG, "sums: the accumulators hold %zu doubles, not %lld", A.ro.n_words, (long long)n);
     if (!n_pairs) return fail(h, MCMC_HIP_ERR_ARG, "n_pairs is null");
     for (int k = 0; k <= A.lags; ++k)
         if (n_pairs[k] < 0) return fail(h, MCMC_HIP_ERR_ARG, "n_pairs[%d] = %lld must be >= 0", k, (long long)n_pairs[k]);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(A.acc.p, sums, sizeof(double) * ac_doubles(h), hipMemcpyHostToDevice));
+    HIP_TRY(h, A.ro.upload(sums));
     A.n_pairs.assign(n_pairs, n_pairs + A.lags + 1);
     return MCMC_HIP_OK;
 }
@@ -159,7 +135,7 @@ int mcmc_hip_autocorr_reset(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& A = h->ac;
-    if (!A.acc.p) return fail(h, MCMC_HIP_ERR_STATE, "autocorr_configure must precede autocorr_reset");
+    if (!A.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "autocorr_configure must precede autocorr_reset");
     A.held = A.head = 0;   // (the slots are overwritten before they are read again)
     return MCMC_HIP_OK;
 }

@@ -1,24 +1,8 @@
 // libmcmc_hip.so: best fit, MAP and profile likelihoods of the ensemble (bestfit_kernels.hip).
-// Life cycle of the marginals: configure once, accumulate beside every moment snapshot, request /
-// fetch at a checkpoint (the hot loop is never stalled), set on resume.
+// The life cycle is the Readout's (readout.h); its slab holds the keys and, behind them, the records.
 #include "ctx.h"
 
 namespace {
-
-void bf_release(mcmc_hip_ctx* h)
-{
-    auto& F = h->bf;
-    F.slab.release();
-    F.records.release();
-    F.cand.release();
-    F.entries.release();
-    if (F.pin) (void)hipHostFree(F.pin);
-    F.pin = nullptr;
-    F.n_slab = F.n_rec = 0;
-    F.n = F.bins = F.quantity = 0;
-    F.n_acc = F.pend_n = 0;
-    F.on = F.pending = false;
-}
 
 // walkers one workgroup reads: 4096 (16 per thread) amortise the flush of the LDS bins; with few
 // entries the slices shrink (to 1024) so that the launch still spreads over the chip.  A maximum
@@ -71,8 +55,8 @@ int mcmc_hip_bestfit_configure(mcmc_hip_ctx* h, int32_t n, const int32_t* dims, 
             return fail(h, MCMC_HIP_ERR_ARG, "lo / hi of parameter %d (dims[%d]): the range [%g, %g] is too narrow for %d bins",
                         i, k, lo[i], hi[i], bins);
     }
-    bf_release(h);
     auto& F = h->bf;
+    F.release();
     std::vector<mcmc::BfEntry> E((size_t)n);
     for (int k = 0; k < n; ++k) {
         const int i = dims[k];
@@ -83,19 +67,13 @@ int mcmc_hip_bestfit_configure(mcmc_hip_ctx* h, int32_t n, const int32_t* dims, 
     const size_t n_slab = (size_t)n * (n ? bins : 0);
     const size_t n_rec = (size_t)mcmc::kBfRecords * (mcmc::kBfRecordHead + d);
     const size_t n_cand = (size_t)((h->W + 1023) / 1024) * mcmc::kBfRecords * 2;   // the most slices there can be
-    if (n_slab) HIP_TRY(h, F.slab.resize(n_slab));
-    if (n) HIP_TRY(h, F.entries.resize(E.size()));
-    HIP_TRY(h, F.records.resize(n_rec));
-    HIP_TRY(h, F.cand.resize(n_cand));
-    HIP_TRY(h, hipHostMalloc((void**)&F.pin, sizeof(unsigned long long) * (n_slab + n_rec), hipHostMallocDefault));
-    if (!F.ev) HIP_TRY(h, hipEventCreateWithFlags(&F.ev, hipEventDisableTiming));
-    if (n) HIP_TRY(h, hipMemcpy(F.entries.p, E.data(), sizeof(mcmc::BfEntry) * E.size(), hipMemcpyHostToDevice));
-    if (n_slab) HIP_TRY(h, hipMemset(F.slab.p, 0, sizeof(unsigned long long) * n_slab));
-    HIP_TRY(h, hipMemset(F.records.p, 0, sizeof(unsigned long long) * n_rec));
-    HIP_TRY(h, hipMemset(F.cand.p, 0, sizeof(unsigned long long) * n_cand));
+    HIP_TRY_BUILD(h, F, F.ro.alloc(n_slab + n_rec, h->stream));
+    if (n) HIP_TRY_BUILD(h, F, F.entries.resize(E.size()));
+    HIP_TRY_BUILD(h, F, F.cand.resize(n_cand));
+    if (n) HIP_TRY_BUILD(h, F, hipMemcpy(F.entries.p, E.data(), sizeof(mcmc::BfEntry) * E.size(), hipMemcpyHostToDevice));
+    HIP_TRY_BUILD(h, F, hipMemsetAsync(F.cand.p, 0, sizeof(unsigned long long) * n_cand, h->stream));
     F.n_slab = n_slab; F.n_rec = n_rec;
     F.n = n; F.bins = n ? bins : 0; F.quantity = quantity;
-    F.on = true;
     return MCMC_HIP_OK;
 }
 
@@ -104,7 +82,7 @@ int mcmc_hip_bestfit_layout(const mcmc_hip_ctx* h, int32_t* on, int32_t* n, int3
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     const auto& F = h->bf;
-    if (on) *on = F.on ? 1 : 0;
+    if (on) *on = F.ro.on() ? 1 : 0;
     if (n) *n = F.n;
     if (bins) *bins = F.bins;
     if (quantity) *quantity = F.quantity;
@@ -117,20 +95,20 @@ int mcmc_hip_bestfit_accumulate(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->bf;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "bestfit_configure must precede bestfit_accumulate");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "bestfit_configure must precede bestfit_accumulate");
     if (!h->have_state) return fail(h, MCMC_HIP_ERR_STATE, "no state");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     mcmc::BfArgs a{};
     a.x = h->x.p; a.logpost = h->logpost.p; a.logprior = h->logprior.p; a.loglike = h->loglike.p;
     a.value = F.quantity == MCMC_HIP_BESTFIT_LOGPOST ? h->logpost.p : h->loglike.p;
-    a.entries = F.entries.p; a.slab = F.slab.p; a.cand = F.cand.p; a.records = F.records.p;
+    a.entries = F.entries.p; a.slab = F.ro.dev(); a.cand = F.cand.p; a.records = F.ro.dev() + F.n_slab;
     a.step = h->step; a.walker0 = h->cfg.walker_offset;
     a.W = h->W; a.d = h->d; a.n_entries = F.n; a.B = F.bins;
     a.slice = bf_slice(h);
     a.n_slices = (h->W + a.slice - 1) / a.slice;
     HIP_TRY(h, mcmc_hip_launch_bestfit(&a, h->stream));
     HIP_TRY(h, mcmc_hip_launch_bestfit_commit(&a, h->stream));
-    F.n_acc += 1;
+    F.ro.n_acc += 1;
     return MCMC_HIP_OK;
 }
 
@@ -138,20 +116,11 @@ int mcmc_hip_bestfit_request(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->bf;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "bestfit_configure must precede bestfit_request");
-    if (F.pending) return fail(h, MCMC_HIP_ERR_STATE, "a bestfit request is already pending");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "bestfit_configure must precede bestfit_request");
+    if (F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "a bestfit request is already pending");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t sb = sizeof(unsigned long long) * F.n_slab, rb = sizeof(unsigned long long) * F.n_rec;
-    if (sb) {
-        HIP_TRY(h, hipMemcpyAsync(F.pin, F.slab.p, sb, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemsetAsync(F.slab.p, 0, sb, h->stream));
-    }
-    HIP_TRY(h, hipMemcpyAsync(F.pin + F.n_slab, F.records.p, rb, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemsetAsync(F.records.p, 0, rb, h->stream));
-    HIP_TRY(h, hipEventRecord(F.ev, h->stream));
-    F.pend_n = F.n_acc;
-    F.n_acc = 0;
-    F.pending = true;
+    HIP_TRY(h, F.ro.copy_out(h->stream, F.ro.n_words));
+    HIP_TRY(h, F.ro.mark(h->stream));
     return MCMC_HIP_OK;
 }
 
@@ -160,14 +129,13 @@ int mcmc_hip_bestfit_fetch(mcmc_hip_ctx* h, uint64_t* slab, int64_t n_slab, uint
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->bf;
-    if (!F.pending) return fail(h, MCMC_HIP_ERR_STATE, "no bestfit request is pending");
+    if (!F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "no bestfit request is pending");
     if (int rc = bf_sizes_ok(h, "bestfit_fetch", slab, n_slab, records, n_records)) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipEventSynchronize(F.ev));
-    F.pending = false;
-    if (F.n_slab) std::copy(F.pin, F.pin + F.n_slab, slab);
-    std::copy(F.pin + F.n_slab, F.pin + F.n_slab + F.n_rec, records);
-    if (n_accumulations) *n_accumulations = F.pend_n;
+    HIP_TRY(h, F.ro.wait());
+    if (F.n_slab) std::copy(F.ro.host(), F.ro.host() + F.n_slab, slab);
+    std::copy(F.ro.host() + F.n_slab, F.ro.host() + F.ro.n_words, records);
+    if (n_accumulations) *n_accumulations = F.ro.pend_n;
     return MCMC_HIP_OK;
 }
 
@@ -176,16 +144,15 @@ int mcmc_hip_bestfit_set(mcmc_hip_ctx* h, const uint64_t* slab, int64_t n_slab, 
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->bf;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "bestfit_configure must precede bestfit_set");
-    if (F.pending) return fail(h, MCMC_HIP_ERR_STATE, "a bestfit request is pending (fetch it first)");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "bestfit_configure must precede bestfit_set");
+    if (F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "a bestfit request is pending (fetch it first)");
     if (int rc = bf_sizes_ok(h, "bestfit_set", slab, n_slab, records, n_records)) return rc;
     if (n_accumulations < 0) return fail(h, MCMC_HIP_ERR_ARG, "n_accumulations = %lld must be >= 0", (long long)n_accumulations);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (F.n_slab)
-        HIP_TRY(h, hipMemcpy(F.slab.p, slab, sizeof(unsigned long long) * F.n_slab, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(F.records.p, records, sizeof(unsigned long long) * F.n_rec, hipMemcpyHostToDevice));
-    F.n_acc = n_accumulations;
+    HIP_TRY(h, F.ro.upload(slab, 0, F.n_slab));
+    HIP_TRY(h, F.ro.upload(records, F.n_slab, F.n_rec));
+    F.ro.n_acc = n_accumulations;
     return MCMC_HIP_OK;
 }
 

@@ -1,23 +1,10 @@
 // libmcmc_hip.so: derived parameters (derived_kernels.hip).  The library owns the rows z[m][W] and
 // their moments; the CALLER fills z on the engine's stream from the state as it lies in HBM
-// (mcmc_hip_derived_buffers hands out both pointers).  Life cycle of the other device products:
-// configure once, accumulate beside a moment snapshot, request / fetch at a checkpoint (the hot loop
-// is never stalled), set on resume.
+// (mcmc_hip_derived_buffers hands out both pointers).  The life cycle of the moments is the Readout's
+// (readout.h).
 #include "ctx.h"
 
 namespace {
-
-void dv_release(mcmc_hip_ctx* h)
-{
-    auto& D = h->dv;
-    D.z.release(); D.Sg.release(); D.shift.release(); D.Ng.release(); D.slab.release(); D.cross.release();
-    if (D.pin) (void)hipHostFree(D.pin);
-    D.pin = nullptr;
-    D.n_words = 0;
-    D.m = D.n_cross = D.n_col = D.gs = D.G = 0;
-    D.n_acc = D.pend_n = 0;
-    D.on = D.pending = false;
-}
 
 size_t dv_n_pairs(int m) { return (size_t)m * (m + 1) / 2; }
 
@@ -28,9 +15,9 @@ mcmc::DvArgs dv_args(mcmc_hip_ctx* h)
     mcmc::DvArgs a{};
     a.x = h->x.p; a.z = D.z.p; a.shift = D.shift.p; a.xshift = h->dshift.p; a.cross = D.cross.p;
     a.Sg = D.Sg.p; a.Ng = D.Ng.p;
-    a.N = D.slab.p;
-    a.S = (double*)(D.slab.p + 1);
-    a.bad = D.slab.p + 1 + n_S;
+    a.N = D.ro.dev();
+    a.S = D.ro.dev<double>() + 1;
+    a.bad = D.ro.dev() + 1 + n_S;
     a.kmax = a.bad + D.m;
     a.kmin = a.kmax + D.m;
     a.W = h->W; a.gs = D.gs; a.G = D.G; a.m = D.m; a.n_cross = D.n_cross; a.n_col = D.n_col;
@@ -90,13 +77,13 @@ int mcmc_hip_derived_configure(mcmc_hip_ctx* h, int32_t m, int32_t n_cross, cons
     if (!h) return MCMC_HIP_ERR_ARG;
     if (m < 0 || m > mcmc::kDvMaxNames)
         return fail(h, MCMC_HIP_ERR_ARG, "m = %d must lie in 0..%d", m, mcmc::kDvMaxNames);
-    if (h->mg.slab.p)
+    if (h->mg.ro.on())
         return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede marginals_configure (release the "
                     "marginals first: their entries may read the derived rows)");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (m == 0) {
-        dv_release(h);
+        h->dv.release();
         return MCMC_HIP_OK;
     }
     const int d = h->d;
@@ -114,22 +101,20 @@ int mcmc_hip_derived_configure(mcmc_hip_ctx* h, int32_t m, int32_t n_cross, cons
     }
     for (int j = 0; j < m; ++j)
         if (!std::isfinite(shift[j])) return fail(h, MCMC_HIP_ERR_ARG, "shift[%d] = %g is not finite", j, shift[j]);
-    dv_release(h);
     auto& D = h->dv;
+    D.release();
     D.m = m; D.n_cross = n_cross; D.n_col = 1 + m + n_cross;
-    D.n_words = 1 + (size_t)(m + 2) * D.n_col + 3 * (size_t)m;
-    HIP_TRY(h, D.z.resize((size_t)m * h->W));
-    HIP_TRY(h, D.shift.resize((size_t)m));
-    HIP_TRY(h, D.cross.resize((size_t)std::max(n_cross, 1)));
-    HIP_TRY(h, D.slab.resize(D.n_words));
-    if (int rc = dv_resize_groups(h, h->gs)) return rc;
-    HIP_TRY(h, hipHostMalloc((void**)&D.pin, sizeof(unsigned long long) * D.n_words, hipHostMallocDefault));
-    if (!D.ev) HIP_TRY(h, hipEventCreateWithFlags(&D.ev, hipEventDisableTiming));
-    HIP_TRY(h, hipMemset(D.z.p, 0, sizeof(double) * (size_t)m * h->W));
-    HIP_TRY(h, hipMemset(D.slab.p, 0, sizeof(unsigned long long) * D.n_words));
-    HIP_TRY(h, hipMemcpy(D.shift.p, shift, sizeof(double) * m, hipMemcpyHostToDevice));
-    if (n_cross > 0) HIP_TRY(h, hipMemcpy(D.cross.p, cross_dims, sizeof(int) * n_cross, hipMemcpyHostToDevice));
-    D.on = true;
+    HIP_TRY_BUILD(h, D, D.z.resize((size_t)m * h->W));
+    HIP_TRY_BUILD(h, D, D.shift.resize((size_t)m));
+    HIP_TRY_BUILD(h, D, D.cross.resize((size_t)std::max(n_cross, 1)));
+    HIP_TRY_BUILD(h, D, D.ro.alloc(1 + (size_t)(m + 2) * D.n_col + 3 * (size_t)m, h->stream));
+    if (int rc = dv_resize_groups(h, h->gs)) {
+        D.release();
+        return rc;
+    }
+    HIP_TRY_BUILD(h, D, hipMemsetAsync(D.z.p, 0, sizeof(double) * (size_t)m * h->W, h->stream));
+    HIP_TRY_BUILD(h, D, hipMemcpy(D.shift.p, shift, sizeof(double) * m, hipMemcpyHostToDevice));
+    if (n_cross > 0) HIP_TRY_BUILD(h, D, hipMemcpy(D.cross.p, cross_dims, sizeof(int) * n_cross, hipMemcpyHostToDevice));
     return MCMC_HIP_OK;
 }
 
@@ -137,7 +122,7 @@ int mcmc_hip_derived_set_group_size(mcmc_hip_ctx* h, int32_t group_size)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& D = h->dv;
-    if (!D.on) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_set_group_size");
+    if (!D.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_set_group_size");
     if (group_size < 1 || h->W % group_size)
         return fail(h, MCMC_HIP_ERR_ARG, "group_size = %d must divide n_walkers = %d", group_size, h->W);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -153,14 +138,14 @@ int mcmc_hip_derived_layout(const mcmc_hip_ctx* h, int32_t* m, int32_t* n_cross,
     if (m) *m = D.m;
     if (n_cross) *n_cross = D.n_cross;
     if (group_size) *group_size = D.gs;
-    if (n_accumulations) *n_accumulations = D.n_acc;
+    if (n_accumulations) *n_accumulations = D.ro.n_acc;
     return MCMC_HIP_OK;
 }
 
 int mcmc_hip_derived_buffers(mcmc_hip_ctx* h, uint64_t* x_device_ptr, uint64_t* z_device_ptr)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
-    if (!h->dv.on) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_buffers");
+    if (!h->dv.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_buffers");
     if (x_device_ptr) *x_device_ptr = (uint64_t)(uintptr_t)h->x.p;
     if (z_device_ptr) *z_device_ptr = (uint64_t)(uintptr_t)h->dv.z.p;
     return MCMC_HIP_OK;
@@ -170,7 +155,7 @@ int mcmc_hip_derived_set_values(mcmc_hip_ctx* h, const double* values)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& D = h->dv;
-    if (!D.on) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_set_values");
+    if (!D.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_set_values");
     if (!values) return fail(h, MCMC_HIP_ERR_ARG, "values is null");
     const size_t W = h->W, m = D.m;
     std::vector<double> t(m * W);
@@ -186,7 +171,7 @@ int mcmc_hip_derived_get_values(mcmc_hip_ctx* h, double* values)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& D = h->dv;
-    if (!D.on) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_get_values");
+    if (!D.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_get_values");
     if (!values) return fail(h, MCMC_HIP_ERR_ARG, "values is null");
     const size_t W = h->W, m = D.m;
     std::vector<double> t(m * W);
@@ -202,12 +187,12 @@ int mcmc_hip_derived_accumulate(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& D = h->dv;
-    if (!D.on) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_accumulate");
+    if (!D.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_accumulate");
     if (!h->have_state) return fail(h, MCMC_HIP_ERR_STATE, "no state");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const mcmc::DvArgs a = dv_args(h);
     HIP_TRY(h, mcmc_hip_launch_derived(&a, h->stream));
-    D.n_acc += 1;
+    D.ro.n_acc += 1;
     return MCMC_HIP_OK;
 }
 
@@ -215,16 +200,11 @@ int mcmc_hip_derived_request(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& D = h->dv;
-    if (!D.on) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_request");
-    if (D.pending) return fail(h, MCMC_HIP_ERR_STATE, "a derived request is already pending");
+    if (!D.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_request");
+    if (D.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "a derived request is already pending");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t bytes = sizeof(unsigned long long) * D.n_words;
-    HIP_TRY(h, hipMemcpyAsync(D.pin, D.slab.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemsetAsync(D.slab.p, 0, bytes, h->stream));
-    HIP_TRY(h, hipEventRecord(D.ev, h->stream));
-    D.pend_n = D.n_acc;
-    D.n_acc = 0;
-    D.pending = true;
+    HIP_TRY(h, D.ro.copy_out(h->stream, D.ro.n_words));
+    HIP_TRY(h, D.ro.mark(h->stream));
     return MCMC_HIP_OK;
 }
 
@@ -233,14 +213,13 @@ int mcmc_hip_derived_fetch(mcmc_hip_ctx* h, uint64_t* n_used, double* A, double*
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& D = h->dv;
-    if (!D.pending) return fail(h, MCMC_HIP_ERR_STATE, "no derived request is pending");
+    if (!D.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "no derived request is pending");
     if (!n_used) return fail(h, MCMC_HIP_ERR_ARG, "derived_fetch: n_used is null");
     if (int rc = dv_null(h, "derived_fetch", A, B, C, X, V, bad, min, max)) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipEventSynchronize(D.ev));
-    D.pending = false;
-    dv_unpack(h, D.pin, n_used, A, B, C, X, V, bad, min, max);
-    if (n_accumulations) *n_accumulations = D.pend_n;
+    HIP_TRY(h, D.ro.wait());
+    dv_unpack(h, D.ro.host(), n_used, A, B, C, X, V, bad, min, max);
+    if (n_accumulations) *n_accumulations = D.ro.pend_n;
     return MCMC_HIP_OK;
 }
 
@@ -250,13 +229,13 @@ int mcmc_hip_derived_set(mcmc_hip_ctx* h, uint64_t n_used, const double* A, cons
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& D = h->dv;
-    if (!D.on) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_set");
-    if (D.pending) return fail(h, MCMC_HIP_ERR_STATE, "a derived request is pending (fetch it first)");
+    if (!D.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "derived_configure must precede derived_set");
+    if (D.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "a derived request is pending (fetch it first)");
     if (int rc = dv_null(h, "derived_set", A, B, C, X, V, bad, min, max)) return rc;
     if (n_accumulations < 0)
         return fail(h, MCMC_HIP_ERR_ARG, "n_accumulations = %lld must be >= 0", (long long)n_accumulations);
     const int m = D.m, nc = D.n_col;
-    std::vector<unsigned long long> words(D.n_words, 0ull);
+    std::vector<unsigned long long> words(D.ro.n_words, 0ull);
     double* S = (double*)(words.data() + 1);
     unsigned long long* wb = words.data() + 1 + (size_t)(m + 2) * nc;
     words[0] = n_used;
@@ -276,8 +255,8 @@ int mcmc_hip_derived_set(mcmc_hip_ctx* h, uint64_t n_used, const double* A, cons
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(D.slab.p, words.data(), sizeof(unsigned long long) * D.n_words, hipMemcpyHostToDevice));
-    D.n_acc = n_accumulations;
+    HIP_TRY(h, D.ro.upload(words.data()));
+    D.ro.n_acc = n_accumulations;
     return MCMC_HIP_OK;
 }
 

@@ -1,28 +1,12 @@
-// libmcmc_hip.so: the sums of the ellipsoid-truncated harmonic mean (evidence_kernels.hip).  Life
-// cycle of the other device products: configure once, accumulate beside a moment snapshot, request /
-// fetch at a checkpoint (the hot loop is never stalled), set on resume.  What is new here is the
+// libmcmc_hip.so: the sums of the ellipsoid-truncated harmonic mean (evidence_kernels.hip).  The
+// life cycle is the Readout's (readout.h); a request may leave the interval open (close = 0), and a
+// closing one keeps the slab's last word, c.  What is new here is the
 // ellipsoid: handed in as (m, cov), factorised on the host, and -- after the first -- only STAGED
 // until a closing request activates it in stream order, so that no interval mixes two ellipsoids.
 #include "ctx.h"
 #include "host_linalg.h"
 
 namespace {
-
-void ev_release(mcmc_hip_ctx* h)
-{
-    auto& F = h->evd;
-    F.slab.release();
-    F.ell.release();
-    F.s.release();
-    if (F.pin) (void)hipHostFree(F.pin);
-    if (F.pin_ell) (void)hipHostFree(F.pin_ell);
-    F.pin = F.pin_ell = nullptr;
-    F.active.clear(); F.staged.clear(); F.pend_active.clear(); F.pend_staged.clear();
-    F.n_words = 0;
-    F.n_r = 0;
-    F.n_acc = F.pend_n = 0;
-    F.on = F.pending = false;
-}
 
 size_t ev_n(const mcmc_hip_ctx* h) { return (size_t)h->G * h->evd.n_r; }
 size_t ev_n_ell(const mcmc_hip_ctx* h) { return (size_t)h->d * (h->d + 1) + 1; }
@@ -35,10 +19,10 @@ mcmc::EvArgs ev_args(mcmc_hip_ctx* h)
     a.x = h->x.p; a.logpost = h->logpost.p;
     a.m = F.ell.p; a.Linv = F.ell.p + d;
     a.s = F.s.p;
-    a.acc = F.slab.p;
-    a.cnt = (unsigned long long*)(F.slab.p + n);
-    a.clamped = (unsigned long long*)(F.slab.p + 2 * n);
-    a.ckey = (unsigned long long*)(F.slab.p + 2 * n + 1);
+    a.acc = F.ro.dev<double>();
+    a.cnt = F.ro.dev() + n;
+    a.clamped = F.ro.dev() + 2 * n;
+    a.ckey = F.ro.dev() + 2 * n + 1;
     for (int r = 0; r < mcmc::kEvMaxRadii; ++r) a.r2[r] = F.r2[r];
     a.W = h->W; a.d = h->d; a.gs = h->gs; a.G = h->G; a.n_r = F.n_r;
     return a;
@@ -86,22 +70,17 @@ int mcmc_hip_evidence_configure(mcmc_hip_ctx* h, int32_t n_radii, const double* 
         return fail(h, MCMC_HIP_ERR_ARG, "d = %d: the evidence kernel serves d <= %d", h->d, mcmc::kEvMaxDim);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    ev_release(h);
-    if (n_radii == 0) return MCMC_HIP_OK;
     auto& F = h->evd;
+    F.release();
+    if (n_radii == 0) return MCMC_HIP_OK;
     F.n_r = n_radii;
     for (int r = 0; r < mcmc::kEvMaxRadii; ++r) F.r2[r] = r < n_radii ? r2[r] : 0.0;
     const size_t n = ev_n(h), d = h->d;
-    F.n_words = 2 * n + 2;
-    HIP_TRY(h, F.slab.resize(F.n_words));
-    HIP_TRY(h, F.ell.resize(d * (d + 1)));
-    HIP_TRY(h, F.s.resize((size_t)h->W));
-    HIP_TRY(h, hipHostMalloc((void**)&F.pin, sizeof(double) * F.n_words, hipHostMallocDefault));
-    HIP_TRY(h, hipHostMalloc((void**)&F.pin_ell, sizeof(double) * d * (d + 1), hipHostMallocDefault));
-    if (!F.ev) HIP_TRY(h, hipEventCreateWithFlags(&F.ev, hipEventDisableTiming));
-    HIP_TRY(h, hipMemset(F.slab.p, 0, sizeof(double) * F.n_words));
-    HIP_TRY(h, hipMemset(F.ell.p, 0, sizeof(double) * d * (d + 1)));
-    F.on = true;
+    HIP_TRY_BUILD(h, F, F.ro.alloc(2 * n + 2, h->stream));
+    HIP_TRY_BUILD(h, F, F.ell.resize(d * (d + 1)));
+    HIP_TRY_BUILD(h, F, F.s.resize((size_t)h->W));
+    HIP_TRY_BUILD(h, F, hipHostMalloc((void**)&F.pin_ell, sizeof(double) * d * (d + 1), hipHostMallocDefault));
+    HIP_TRY_BUILD(h, F, hipMemsetAsync(F.ell.p, 0, sizeof(double) * d * (d + 1), h->stream));
     return MCMC_HIP_OK;
 }
 
@@ -110,13 +89,13 @@ int mcmc_hip_evidence_layout(const mcmc_hip_ctx* h, int32_t* on, int32_t* n_radi
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     const auto& F = h->evd;
-    if (on) *on = F.on ? 1 : 0;
+    if (on) *on = F.ro.on() ? 1 : 0;
     if (n_radii) *n_radii = F.n_r;
-    if (n_groups) *n_groups = F.on ? h->G : 0;
-    if (n_ell) *n_ell = F.on ? (int64_t)ev_n_ell(h) : 0;
+    if (n_groups) *n_groups = F.ro.on() ? h->G : 0;
+    if (n_ell) *n_ell = F.ro.on() ? (int64_t)ev_n_ell(h) : 0;
     if (has_active) *has_active = F.active.empty() ? 0 : 1;
     if (has_staged) *has_staged = F.staged.empty() ? 0 : 1;
-    if (n_accumulations) *n_accumulations = F.n_acc;
+    if (n_accumulations) *n_accumulations = F.ro.n_acc;
     return MCMC_HIP_OK;
 }
 
@@ -124,7 +103,7 @@ int mcmc_hip_evidence_set_ellipsoid(mcmc_hip_ctx* h, const double* m, const doub
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->evd;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "evidence_configure must precede evidence_set_ellipsoid");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "evidence_configure must precede evidence_set_ellipsoid");
     if (!m || !cov) return fail(h, MCMC_HIP_ERR_ARG, "%s is null", !m ? "m" : "cov");
     const int d = h->d;
     for (int i = 0; i < d; ++i)
@@ -152,13 +131,13 @@ int mcmc_hip_evidence_accumulate(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->evd;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "evidence_configure must precede evidence_accumulate");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "evidence_configure must precede evidence_accumulate");
     if (F.active.empty()) return fail(h, MCMC_HIP_ERR_STATE, "no ellipsoid is active: call evidence_set_ellipsoid first");
     if (!h->have_state) return fail(h, MCMC_HIP_ERR_STATE, "no state");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const mcmc::EvArgs a = ev_args(h);
     HIP_TRY(h, mcmc_hip_launch_evidence(&a, h->stream));
-    F.n_acc += 1;
+    F.ro.n_acc += 1;
     return MCMC_HIP_OK;
 }
 
@@ -166,26 +145,20 @@ int mcmc_hip_evidence_request(mcmc_hip_ctx* h, int32_t close)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->evd;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "evidence_configure must precede evidence_request");
-    if (F.pending) return fail(h, MCMC_HIP_ERR_STATE, "an evidence request is already pending");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "evidence_configure must precede evidence_request");
+    if (F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "an evidence request is already pending");
     if (close && !F.staged.empty() && !h->have_state)
         return fail(h, MCMC_HIP_ERR_STATE, "no state: the staged ellipsoid takes c from logpost");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipMemcpyAsync(F.pin, F.slab.p, sizeof(double) * F.n_words, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, F.ro.copy_out(h->stream, close ? F.ro.n_words - 1 : 0));   // (c stays)
     F.pend_active = F.active;
     F.pend_staged = F.staged;
-    F.pend_n = F.n_acc;
-    if (close) {
-        HIP_TRY(h, hipMemsetAsync(F.slab.p, 0, sizeof(double) * (F.n_words - 1), h->stream));   // (c stays)
-        F.n_acc = 0;
-        if (!F.staged.empty()) {
-            if (int rc = ev_activate(h, F.staged)) return rc;
-            F.active = std::move(F.staged);
-            F.staged.clear();
-        }
+    if (close && !F.staged.empty()) {
+        if (int rc = ev_activate(h, F.staged)) return rc;
+        F.active = std::move(F.staged);
+        F.staged.clear();
     }
-    HIP_TRY(h, hipEventRecord(F.ev, h->stream));   // (last: a fetch also vouches for the pinned ellipsoid)
-    F.pending = true;
+    HIP_TRY(h, F.ro.mark(h->stream));   // (last: a fetch also vouches for the pinned ellipsoid)
     return MCMC_HIP_OK;
 }
 
@@ -195,24 +168,22 @@ int mcmc_hip_evidence_fetch(mcmc_hip_ctx* h, double* sums, uint64_t* counts, int
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->evd;
-    if (!F.pending) return fail(h, MCMC_HIP_ERR_STATE, "no evidence request is pending");
+    if (!F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "no evidence request is pending");
     if (int rc = ev_sizes_ok(h, "evidence_fetch", sums, counts, n, n_ell)) return rc;
     if (!active || !staged) return fail(h, MCMC_HIP_ERR_ARG, "%s is null", !active ? "active" : "staged");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipEventSynchronize(F.ev));
-    F.pending = false;
+    HIP_TRY(h, F.ro.wait());
     const size_t k = ev_n(h);
-    std::copy(F.pin, F.pin + k, sums);
-    std::memcpy(counts, F.pin + k, sizeof(uint64_t) * k);
-    if (clamped) std::memcpy(clamped, F.pin + 2 * k, sizeof(uint64_t));
-    if (n_accumulations) *n_accumulations = F.pend_n;
+    const unsigned long long* words = F.ro.host();
+    std::copy(F.ro.host<double>(), F.ro.host<double>() + k, sums);
+    std::copy(words + k, words + 2 * k, counts);
+    if (clamped) *clamped = words[2 * k];
+    if (n_accumulations) *n_accumulations = F.ro.pend_n;
     std::fill(active, active + n_ell, 0.0);
     std::fill(staged, staged + n_ell, 0.0);
     if (!F.pend_active.empty()) {
         std::copy(F.pend_active.begin(), F.pend_active.end(), active);
-        unsigned long long key;
-        std::memcpy(&key, F.pin + 2 * k + 1, sizeof key);
-        active[n_ell - 1] = mcmc::ev_value(key);
+        active[n_ell - 1] = mcmc::ev_value(words[2 * k + 1]);
     }
     if (!F.pend_staged.empty()) std::copy(F.pend_staged.begin(), F.pend_staged.end(), staged);
     if (has_active) *has_active = F.pend_active.empty() ? 0 : 1;
@@ -225,8 +196,8 @@ int mcmc_hip_evidence_set(mcmc_hip_ctx* h, const double* sums, const uint64_t* c
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->evd;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "evidence_configure must precede evidence_set");
-    if (F.pending) return fail(h, MCMC_HIP_ERR_STATE, "an evidence request is pending (fetch it first)");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "evidence_configure must precede evidence_set");
+    if (F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "an evidence request is pending (fetch it first)");
     if (int rc = ev_sizes_ok(h, "evidence_set", sums, counts, n, n_ell)) return rc;
     if (n_accumulations < 0)
         return fail(h, MCMC_HIP_ERR_ARG, "n_accumulations = %lld must be >= 0", (long long)n_accumulations);
@@ -239,13 +210,12 @@ int mcmc_hip_evidence_set(mcmc_hip_ctx* h, const double* sums, const uint64_t* c
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const size_t k = ev_n(h), ne = (size_t)n_ell - 1;
-    std::vector<double> words(F.n_words, 0.0);
-    std::copy(sums, sums + k, words.begin());
-    std::memcpy(words.data() + k, counts, sizeof(uint64_t) * k);
-    std::memcpy(words.data() + 2 * k, &clamped, sizeof(uint64_t));
-    const unsigned long long key = active ? mcmc::ev_key(active[ne]) : 0ull;
-    std::memcpy(words.data() + 2 * k + 1, &key, sizeof key);
-    HIP_TRY(h, hipMemcpy(F.slab.p, words.data(), sizeof(double) * F.n_words, hipMemcpyHostToDevice));
+    std::vector<unsigned long long> words(F.ro.n_words, 0ull);
+    std::memcpy(words.data(), sums, sizeof(double) * k);
+    std::copy(counts, counts + k, words.begin() + k);
+    words[2 * k] = clamped;
+    words[2 * k + 1] = active ? mcmc::ev_key(active[ne]) : 0ull;
+    HIP_TRY(h, F.ro.upload(words.data()));
     F.active.clear();
     F.staged.clear();
     if (active) {
@@ -253,7 +223,7 @@ int mcmc_hip_evidence_set(mcmc_hip_ctx* h, const double* sums, const uint64_t* c
         HIP_TRY(h, hipMemcpy(F.ell.p, active, sizeof(double) * ne, hipMemcpyHostToDevice));
     }
     if (staged) F.staged.assign(staged, staged + ne);
-    F.n_acc = n_accumulations;
+    F.ro.n_acc = n_accumulations;
     return MCMC_HIP_OK;
 }
 

@@ -1,24 +1,11 @@
 // libmcmc_hip.so: the weighted sums of importance reweighting (importance_kernels.hip).  The CALLER
 // owns the log-weights delta[n_alt][W]: it fills them on the engine's stream from the state as it lies
 // in HBM (mcmc_hip_importance_layout hands out the pointer of x) and passes their device pointer to
-// accumulate.  Life cycle of the other device products: configure once, accumulate beside a moment
-// snapshot, request / fetch at a checkpoint (the hot loop is never stalled), set on resume.  The
-// centring constants c are taken ON THE DEVICE by the first accumulation of an interval.
+// accumulate.  The life cycle is the Readout's (readout.h); a request may leave the interval open
+// (close = 0).  The centring constants c are taken ON THE DEVICE by the first accumulation of an interval.
 #include "ctx.h"
 
 namespace {
-
-void im_release(mcmc_hip_ctx* h)
-{
-    auto& F = h->imp;
-    F.slab.release();
-    if (F.pin) (void)hipHostFree(F.pin);
-    F.pin = nullptr;
-    F.n_words = F.n_sums = 0;
-    F.n_alt = F.gs = F.G = 0;
-    F.n_acc = F.pend_n = 0;
-    F.on = F.pending = false;
-}
 
 size_t im_n_groups(const mcmc_hip_ctx* h) { return (size_t)h->imp.n_alt * h->imp.G; }
 
@@ -27,8 +14,8 @@ mcmc::ImArgs im_args(mcmc_hip_ctx* h, const double* delta)
     auto& F = h->imp;
     mcmc::ImArgs a{};
     a.x = h->x.p; a.shift = h->dshift.p; a.delta = delta;
-    a.sums = (double*)F.slab.p;
-    a.n = F.slab.p + F.n_sums;
+    a.sums = F.ro.dev<double>();
+    a.n = F.ro.dev() + F.n_sums;
     a.counters = a.n + im_n_groups(h);
     a.ckey = a.counters + 3 * (size_t)F.n_alt;
     for (int k = 0; k < mcmc::kImMaxAlt; ++k) { a.off[k] = F.off[k]; a.cov[k] = F.cov[k]; }
@@ -48,14 +35,7 @@ int im_resize_groups(mcmc_hip_ctx* h, int gs)
         if (k < F.n_alt) at += (size_t)F.G * mcmc::im_n_chains(h->d, F.cov[k]);
     }
     F.n_sums = at;
-    F.n_words = F.n_sums + im_n_groups(h) + 4 * (size_t)F.n_alt;
-    F.slab.release();
-    if (F.pin) (void)hipHostFree(F.pin);
-    F.pin = nullptr;
-    HIP_TRY(h, F.slab.resize(F.n_words));
-    HIP_TRY(h, hipHostMalloc((void**)&F.pin, sizeof(unsigned long long) * F.n_words, hipHostMallocDefault));
-    HIP_TRY(h, hipMemset(F.slab.p, 0, sizeof(unsigned long long) * F.n_words));
-    F.n_acc = 0;
+    HIP_TRY_BUILD(h, F, F.ro.alloc(F.n_sums + im_n_groups(h) + 4 * (size_t)F.n_alt, h->stream));
     return MCMC_HIP_OK;
 }
 
@@ -89,23 +69,20 @@ int mcmc_hip_importance_configure(mcmc_hip_ctx* h, int32_t n_alt, const int32_t*
                         mcmc::kImMaxCovDim);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    im_release(h);
-    if (n_alt == 0) return MCMC_HIP_OK;
     auto& F = h->imp;
+    F.release();
+    if (n_alt == 0) return MCMC_HIP_OK;
     F.n_alt = n_alt;
     for (int k = 0; k < mcmc::kImMaxAlt; ++k) F.cov[k] = k < n_alt && cov[k] ? 1 : 0;
-    if (!F.ev) HIP_TRY(h, hipEventCreateWithFlags(&F.ev, hipEventDisableTiming));
-    if (int rc = im_resize_groups(h, h->gs)) return rc;
-    F.on = true;
-    return MCMC_HIP_OK;
+    return im_resize_groups(h, h->gs);
 }
 
 int mcmc_hip_importance_set_group_size(mcmc_hip_ctx* h, int32_t group_size)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->imp;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "importance_configure must precede importance_set_group_size");
-    if (F.pending) return fail(h, MCMC_HIP_ERR_STATE, "an importance request is pending (fetch it first)");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "importance_configure must precede importance_set_group_size");
+    if (F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "an importance request is pending (fetch it first)");
     if (group_size < 1 || h->W % group_size)
         return fail(h, MCMC_HIP_ERR_ARG, "group_size = %d must divide n_walkers = %d", group_size, h->W);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -119,13 +96,13 @@ int mcmc_hip_importance_layout(const mcmc_hip_ctx* h, int32_t* n_alt, int32_t* n
     if (!h) return MCMC_HIP_ERR_ARG;
     const auto& F = h->imp;
     if (n_alt) *n_alt = F.n_alt;
-    if (n_groups) *n_groups = F.on ? F.G : 0;
+    if (n_groups) *n_groups = F.ro.on() ? F.G : 0;
     if (n_sums) *n_sums = (int64_t)F.n_sums;
     for (int k = 0; k < mcmc::kImMaxAlt; ++k) {
         if (offsets) offsets[k] = k < F.n_alt ? (int64_t)F.off[k] : 0;
         if (cov) cov[k] = k < F.n_alt ? F.cov[k] : 0;
     }
-    if (n_accumulations) *n_accumulations = F.n_acc;
+    if (n_accumulations) *n_accumulations = F.ro.n_acc;
     if (x_device_ptr) *x_device_ptr = (uint64_t)(uintptr_t)h->x.p;
     return MCMC_HIP_OK;
 }
@@ -134,16 +111,16 @@ int mcmc_hip_importance_accumulate(mcmc_hip_ctx* h, uint64_t delta_device_ptr)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->imp;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "importance_configure must precede importance_accumulate");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "importance_configure must precede importance_accumulate");
     if (!h->have_state) return fail(h, MCMC_HIP_ERR_STATE, "no state");
     if (!delta_device_ptr || delta_device_ptr % sizeof(double))
         return fail(h, MCMC_HIP_ERR_ARG, "delta_device_ptr = %llu is not the device pointer of doubles",
                     (unsigned long long)delta_device_ptr);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const mcmc::ImArgs a = im_args(h, (const double*)(uintptr_t)delta_device_ptr);
-    if (F.n_acc == 0) HIP_TRY(h, mcmc_hip_launch_importance_max(&a, h->stream));   // the interval opens
+    if (F.ro.n_acc == 0) HIP_TRY(h, mcmc_hip_launch_importance_max(&a, h->stream));   // the interval opens
     HIP_TRY(h, mcmc_hip_launch_importance(&a, h->stream));
-    F.n_acc += 1;
+    F.ro.n_acc += 1;
     return MCMC_HIP_OK;
 }
 
@@ -151,18 +128,11 @@ int mcmc_hip_importance_request(mcmc_hip_ctx* h, int32_t close)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->imp;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "importance_configure must precede importance_request");
-    if (F.pending) return fail(h, MCMC_HIP_ERR_STATE, "an importance request is already pending");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "importance_configure must precede importance_request");
+    if (F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "an importance request is already pending");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t bytes = sizeof(unsigned long long) * F.n_words;
-    HIP_TRY(h, hipMemcpyAsync(F.pin, F.slab.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    F.pend_n = F.n_acc;
-    if (close) {
-        HIP_TRY(h, hipMemsetAsync(F.slab.p, 0, bytes, h->stream));
-        F.n_acc = 0;
-    }
-    HIP_TRY(h, hipEventRecord(F.ev, h->stream));
-    F.pending = true;
+    HIP_TRY(h, F.ro.copy_out(h->stream, close ? F.ro.n_words : 0));
+    HIP_TRY(h, F.ro.mark(h->stream));
     return MCMC_HIP_OK;
 }
 
@@ -171,17 +141,17 @@ int mcmc_hip_importance_fetch(mcmc_hip_ctx* h, double* sums, int64_t n_sums, uin
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->imp;
-    if (!F.pending) return fail(h, MCMC_HIP_ERR_STATE, "no importance request is pending");
+    if (!F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "no importance request is pending");
     if (int rc = im_sizes_ok(h, "importance_fetch", sums, n, counters, c, n_sums, n_groups)) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipEventSynchronize(F.ev));
-    F.pending = false;
+    HIP_TRY(h, F.ro.wait());
     const size_t ng = im_n_groups(h);
-    std::memcpy(sums, F.pin, sizeof(double) * F.n_sums);
-    std::memcpy(n, F.pin + F.n_sums, sizeof(uint64_t) * ng);
-    std::memcpy(counters, F.pin + F.n_sums + ng, sizeof(uint64_t) * 3 * F.n_alt);
-    for (int k = 0; k < F.n_alt; ++k) c[k] = mcmc::im_value(F.pin[F.n_sums + ng + 3 * (size_t)F.n_alt + k]);
-    if (n_accumulations) *n_accumulations = F.pend_n;
+    const unsigned long long* words = F.ro.host();
+    std::memcpy(sums, words, sizeof(double) * F.n_sums);
+    std::memcpy(n, words + F.n_sums, sizeof(uint64_t) * ng);
+    std::memcpy(counters, words + F.n_sums + ng, sizeof(uint64_t) * 3 * F.n_alt);
+    for (int k = 0; k < F.n_alt; ++k) c[k] = mcmc::im_value(words[F.n_sums + ng + 3 * (size_t)F.n_alt + k]);
+    if (n_accumulations) *n_accumulations = F.ro.pend_n;
     return MCMC_HIP_OK;
 }
 
@@ -190,15 +160,15 @@ int mcmc_hip_importance_set(mcmc_hip_ctx* h, const double* sums, int64_t n_sums,
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& F = h->imp;
-    if (!F.on) return fail(h, MCMC_HIP_ERR_STATE, "importance_configure must precede importance_set");
-    if (F.pending) return fail(h, MCMC_HIP_ERR_STATE, "an importance request is pending (fetch it first)");
+    if (!F.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "importance_configure must precede importance_set");
+    if (F.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "an importance request is pending (fetch it first)");
     if (int rc = im_sizes_ok(h, "importance_set", sums, n, counters, c, n_sums, n_groups)) return rc;
     if (n_accumulations < 0)
         return fail(h, MCMC_HIP_ERR_ARG, "n_accumulations = %lld must be >= 0", (long long)n_accumulations);
     for (int k = 0; k < F.n_alt; ++k)
         if (!std::isfinite(c[k])) return fail(h, MCMC_HIP_ERR_ARG, "c[%d] = %g is not finite", k, c[k]);
     const size_t ng = im_n_groups(h);
-    std::vector<unsigned long long> words(F.n_words, 0ull);
+    std::vector<unsigned long long> words(F.ro.n_words, 0ull);
     std::memcpy(words.data(), sums, sizeof(double) * F.n_sums);
     std::memcpy(words.data() + F.n_sums, n, sizeof(uint64_t) * ng);
     std::memcpy(words.data() + F.n_sums + ng, counters, sizeof(uint64_t) * 3 * F.n_alt);
@@ -206,8 +176,8 @@ int mcmc_hip_importance_set(mcmc_hip_ctx* h, const double* sums, int64_t n_sums,
     for (int k = 0; k < F.n_alt; ++k) words[F.n_sums + ng + 3 * (size_t)F.n_alt + k] = mcmc::im_key(c[k]);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(F.slab.p, words.data(), sizeof(unsigned long long) * F.n_words, hipMemcpyHostToDevice));
-    F.n_acc = n_accumulations;
+    HIP_TRY(h, F.ro.upload(words.data()));
+    F.ro.n_acc = n_accumulations;
     return MCMC_HIP_OK;
 }
 

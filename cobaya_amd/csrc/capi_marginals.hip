@@ -1,25 +1,11 @@
 // libmcmc_hip.so: streaming 1-D and 2-D marginal histograms of the ensemble (marginal_kernels.hip).
-// Life cycle of the moments: configure once, accumulate beside every moment snapshot, request /
-// fetch at a checkpoint (the hot loop is never stalled), set on resume.
+// The life cycle is the Readout's (readout.h).
 #include "ctx.h"
 
 namespace {
 
 size_t marg_counters_1d(int bins1) { return (size_t)bins1 + 2; }
 size_t marg_counters_2d(int bins2) { return (size_t)bins2 * bins2 + 1; }
-
-void marg_release(mcmc_hip_ctx* h)
-{
-    auto& M = h->mg;
-    M.slab.release();
-    M.entries.release();
-    if (M.pin) (void)hipHostFree(M.pin);
-    M.pin = nullptr;
-    M.n_counters = M.off_pairs = 0;
-    M.n1 = M.n2 = M.bins1 = M.bins2 = M.n_entries = M.lds_words = 0;
-    M.n_acc = M.pend_n = 0;
-    M.pending = false;
-}
 
 }  // namespace
 
@@ -35,7 +21,7 @@ int mcmc_hip_marginals_configure(mcmc_hip_ctx* h, int32_t n1, const int32_t* dim
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (n1 == 0 && n2 == 0) {
-        marg_release(h);
+        h->mg.release();
         return MCMC_HIP_OK;
     }
     if (n1 > 0 && !dims1) return fail(h, MCMC_HIP_ERR_ARG, "dims1 is null");
@@ -68,8 +54,8 @@ int mcmc_hip_marginals_configure(mcmc_hip_ctx* h, int32_t n1, const int32_t* dim
         if (int rc = range_ok(i, bins2, "pairs", k)) return rc;
         if (int rc = range_ok(j, bins2, "pairs", k)) return rc;
     }
-    marg_release(h);
     auto& M = h->mg;
+    M.release();
     const size_t c1 = n1 ? marg_counters_1d(bins1) : 0, c2 = n2 ? marg_counters_2d(bins2) : 0;
     std::vector<mcmc::MargEntry> E((size_t)n1 + n2);
     for (int k = 0; k < n1; ++k) {
@@ -90,13 +76,9 @@ int mcmc_hip_marginals_configure(mcmc_hip_ctx* h, int32_t n1, const int32_t* dim
         e.offset = (long long)(c1 * n1 + c2 * k);
     }
     const size_t n = c1 * n1 + c2 * n2;
-    HIP_TRY(h, M.slab.resize(n));
-    HIP_TRY(h, M.entries.resize(E.size()));
-    HIP_TRY(h, hipHostMalloc((void**)&M.pin, sizeof(unsigned long long) * n, hipHostMallocDefault));
-    if (!M.ev) HIP_TRY(h, hipEventCreateWithFlags(&M.ev, hipEventDisableTiming));
-    HIP_TRY(h, hipMemcpy(M.entries.p, E.data(), sizeof(mcmc::MargEntry) * E.size(), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemset(M.slab.p, 0, sizeof(unsigned long long) * n));
-    M.n_counters = n;
+    HIP_TRY_BUILD(h, M, M.ro.alloc(n, h->stream));
+    HIP_TRY_BUILD(h, M, M.entries.resize(E.size()));
+    HIP_TRY_BUILD(h, M, hipMemcpy(M.entries.p, E.data(), sizeof(mcmc::MargEntry) * E.size(), hipMemcpyHostToDevice));
     M.off_pairs = c1 * n1;
     M.n1 = n1; M.n2 = n2; M.bins1 = n1 ? bins1 : 0; M.bins2 = n2 ? bins2 : 0;
     M.n_entries = n1 + n2;
@@ -109,7 +91,7 @@ int mcmc_hip_marginals_layout(const mcmc_hip_ctx* h, int64_t* n_counters, int32_
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     const auto& M = h->mg;
-    if (n_counters) *n_counters = (int64_t)M.n_counters;
+    if (n_counters) *n_counters = (int64_t)M.ro.n_words;
     if (n1) *n1 = M.n1;
     if (bins1) *bins1 = M.bins1;
     if (n2) *n2 = M.n2;
@@ -122,11 +104,11 @@ int mcmc_hip_marginals_accumulate(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& M = h->mg;
-    if (!M.slab.p) return fail(h, MCMC_HIP_ERR_STATE, "marginals_configure must precede marginals_accumulate");
+    if (!M.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "marginals_configure must precede marginals_accumulate");
     if (!h->have_state) return fail(h, MCMC_HIP_ERR_STATE, "no state");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     mcmc::MargArgs a{};
-    a.x = h->x.p; a.z = h->dv.z.p; a.d = h->d; a.entries = M.entries.p; a.slab = M.slab.p; a.W = h->W; a.n_entries = M.n_entries;
+    a.x = h->x.p; a.z = h->dv.z.p; a.d = h->d; a.entries = M.entries.p; a.slab = M.ro.dev(); a.W = h->W; a.n_entries = M.n_entries;
     // a slice of 4096 walkers (16 per thread) amortises the flush of the LDS histogram; with few
     // entries the slices shrink (to 1024) so that the launch still spreads over the chip.  The
     // counts do not depend on it.
@@ -135,7 +117,7 @@ int mcmc_hip_marginals_accumulate(mcmc_hip_ctx* h)
     a.slice = slice;
     a.n_slices = (h->W + slice - 1) / slice;
     HIP_TRY(h, mcmc_hip_launch_marginals(&a, M.lds_words, h->stream));
-    M.n_acc += 1;
+    M.ro.n_acc += 1;
     return MCMC_HIP_OK;
 }
 
@@ -143,16 +125,11 @@ int mcmc_hip_marginals_request(mcmc_hip_ctx* h)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& M = h->mg;
-    if (!M.slab.p) return fail(h, MCMC_HIP_ERR_STATE, "marginals_configure must precede marginals_request");
-    if (M.pending) return fail(h, MCMC_HIP_ERR_STATE, "a marginals request is already pending");
+    if (!M.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "marginals_configure must precede marginals_request");
+    if (M.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "a marginals request is already pending");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t bytes = sizeof(unsigned long long) * M.n_counters;
-    HIP_TRY(h, hipMemcpyAsync(M.pin, M.slab.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemsetAsync(M.slab.p, 0, bytes, h->stream));
-    HIP_TRY(h, hipEventRecord(M.ev, h->stream));
-    M.pend_n = M.n_acc;
-    M.n_acc = 0;
-    M.pending = true;
+    HIP_TRY(h, M.ro.copy_out(h->stream, M.ro.n_words));
+    HIP_TRY(h, M.ro.mark(h->stream));
     return MCMC_HIP_OK;
 }
 
@@ -160,14 +137,13 @@ int mcmc_hip_marginals_fetch(mcmc_hip_ctx* h, uint64_t* counts, int64_t n, int64
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& M = h->mg;
-    if (!M.pending) return fail(h, MCMC_HIP_ERR_STATE, "no marginals request is pending");
-    if (!counts || (size_t)n != M.n_counters)
-        return fail(h, MCMC_HIP_ERR_ARG, "counts: the slab holds %zu counters, not %lld", M.n_counters, (long long)n);
+    if (!M.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "no marginals request is pending");
+    if (!counts || (size_t)n != M.ro.n_words)
+        return fail(h, MCMC_HIP_ERR_ARG, "counts: the slab holds %zu counters, not %lld", M.ro.n_words, (long long)n);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipEventSynchronize(M.ev));
-    M.pending = false;
-    std::copy(M.pin, M.pin + M.n_counters, counts);
-    if (n_accumulations) *n_accumulations = M.pend_n;
+    HIP_TRY(h, M.ro.wait());
+    std::copy(M.ro.host(), M.ro.host() + M.ro.n_words, counts);
+    if (n_accumulations) *n_accumulations = M.ro.pend_n;
     return MCMC_HIP_OK;
 }
 
@@ -175,15 +151,15 @@ int mcmc_hip_marginals_set(mcmc_hip_ctx* h, const uint64_t* counts, int64_t n, i
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     auto& M = h->mg;
-    if (!M.slab.p) return fail(h, MCMC_HIP_ERR_STATE, "marginals_configure must precede marginals_set");
-    if (M.pending) return fail(h, MCMC_HIP_ERR_STATE, "a marginals request is pending (fetch it first)");
-    if (!counts || (size_t)n != M.n_counters)
-        return fail(h, MCMC_HIP_ERR_ARG, "counts: the slab holds %zu counters, not %lld", M.n_counters, (long long)n);
+    if (!M.ro.on()) return fail(h, MCMC_HIP_ERR_STATE, "marginals_configure must precede marginals_set");
+    if (M.ro.pending) return fail(h, MCMC_HIP_ERR_STATE, "a marginals request is pending (fetch it first)");
+    if (!counts || (size_t)n != M.ro.n_words)
+        return fail(h, MCMC_HIP_ERR_ARG, "counts: the slab holds %zu counters, not %lld", M.ro.n_words, (long long)n);
     if (n_accumulations < 0) return fail(h, MCMC_HIP_ERR_ARG, "n_accumulations = %lld must be >= 0", (long long)n_accumulations);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(M.slab.p, counts, sizeof(unsigned long long) * M.n_counters, hipMemcpyHostToDevice));
-    M.n_acc = n_accumulations;
+    HIP_TRY(h, M.ro.upload(counts));
+    M.ro.n_acc = n_accumulations;
     return MCMC_HIP_OK;
 }
 

@@ -29,6 +29,7 @@
 #include "importance_args.h"
 #include "comm.h"
 #include "inc_choice.h"
+#include "readout.h"
 
 MCMC_DECLARE_DIM(1) MCMC_DECLARE_DIM(2) MCMC_DECLARE_DIM(3) MCMC_DECLARE_DIM(4)
 MCMC_DECLARE_DIM(5) MCMC_DECLARE_DIM(6) MCMC_DECLARE_DIM(7) MCMC_DECLARE_DIM(8)
@@ -266,100 +267,117 @@ struct mcmc_hip_ctx {
         int n_slots = 0;
         double* pin = nullptr;     // [1 + 4 d + G d 2]
     } bd;
-    // streaming marginal histograms (mcmc_hip_marginals_*; marginal_kernels.hip): the uint64 slab
-    // [1-D entries: under, over, bins1 | pairs: outside, bins2 x bins2], its pinned read-out
+    // The six device products.  Each keeps its slab of 64-bit words, the pinned read-out and the
+    // request / fetch / set state in `ro` (readout.h: the life cycle, once) and here only what is its
+    // own; release(): back to "not configured" (ro.slab == nullptr), the event stays for the next
+    // configure; mcmc_hip_destroy ends each with release() and ro.destroy().
+    //
+    // streaming marginal histograms (mcmc_hip_marginals_*; marginal_kernels.hip): the slab
+    // [1-D entries: under, over, bins1 | pairs: outside, bins2 x bins2]
     struct Marginals {
-        DevBuf<unsigned long long> slab;
+        Readout ro;
         DevBuf<mcmc::MargEntry> entries;
-        unsigned long long* pin = nullptr;     // [n_counters]
-        size_t n_counters = 0, off_pairs = 0;
+        size_t off_pairs = 0;
         int n1 = 0, n2 = 0, bins1 = 0, bins2 = 0, n_entries = 0, lds_words = 0;
-        int64_t n_acc = 0;                     // accumulations since the last request / set
-        int64_t pend_n = 0;                    // ... of the pending read-out
-        hipEvent_t ev = nullptr;
-        bool pending = false;
+        void release()
+        {
+            ro.release();
+            entries.release();
+            off_pairs = 0;
+            n1 = n2 = bins1 = bins2 = n_entries = lds_words = 0;
+        }
     } mg;
     // lagged cross-products for the autocorrelation time (mcmc_hip_autocorr_*; autocorr_kernels.hip):
-    // the ring of the last lags + 1 snapshots with their group sums, the accumulators
-    // [3][lags + 1][n] (P, A, B) and their pinned read-out; the pair counts live on the host
+    // the ring of the last lags + 1 snapshots with their group sums and the slab of doubles
+    // [3][lags + 1][n] (P, A, B).  It counts pairs per lag, on the host, not accumulations
     struct AutoCorr {
-        DevBuf<double> ring, ringS, Pg, acc;
+        Readout ro;
+        DevBuf<double> ring, ringS, Pg;
         DevBuf<int> dims;
-        double* pin = nullptr;                 // [3][lags + 1][n]
         int n = 0, lags = 0, rows_per_pass = 0;
         int held = 0;                          // snapshots the ring holds (<= lags + 1)
         int head = 0;                          // slot of the NEXT snapshot
         std::vector<int64_t> n_pairs, pend_pairs;   // [lags + 1]: open, of the pending read-out
-        hipEvent_t ev = nullptr;
-        bool pending = false;
+        void release()
+        {
+            ro.release();
+            ring.release(); ringS.release(); Pg.release(); dims.release();
+            n = lags = rows_per_pass = held = head = 0;
+            n_pairs.clear(); pend_pairs.clear();
+        }
     } ac;
-    // best fit, MAP and profile likelihoods (mcmc_hip_bestfit_*; bestfit_kernels.hip): the uint64
-    // slab of keys [n][bins], the two records [2][6 + d] (key, walker, step, logpost, logprior,
-    // loglike, x[d] as 64-bit words), the slices' candidates, and the pinned read-out of slab + records
+    // best fit, MAP and profile likelihoods (mcmc_hip_bestfit_*; bestfit_kernels.hip): the slab of
+    // keys [n][bins] | the two records [2][6 + d] (key, walker, step, logpost, logprior, loglike,
+    // x[d] as 64-bit words) at word n_slab, and the slices' candidates
     struct BestFit {
-        DevBuf<unsigned long long> slab, records, cand;
+        Readout ro;
+        DevBuf<unsigned long long> cand;
         DevBuf<mcmc::BfEntry> entries;
-        unsigned long long* pin = nullptr;     // [n_slab + n_rec]
         size_t n_slab = 0, n_rec = 0;
         int n = 0, bins = 0, quantity = 0;
-        bool on = false;
-        int64_t n_acc = 0;                     // accumulations since the last request / set
-        int64_t pend_n = 0;                    // ... of the pending read-out
-        hipEvent_t ev = nullptr;
-        bool pending = false;
+        void release()
+        {
+            ro.release();
+            cand.release(); entries.release();
+            n_slab = n_rec = 0;
+            n = bins = quantity = 0;
+        }
     } bf;
-    // evidence of the run (mcmc_hip_evidence_*; evidence_kernels.hip): the slab of 64-bit words
+    // evidence of the run (mcmc_hip_evidence_*; evidence_kernels.hip): the slab
     // acc[G][n_r] doubles | cnt[G][n_r] uint64 | clamped uint64 | the key of c, the active ellipsoid
     // m[d] | Linv[d][d] on the device, the staged one in pinned memory until a closing request
     // uploads it in stream order; host copies of both travel with every read-out
     struct Evidence {
-        DevBuf<double> slab, ell, s;           // [2 G n_r + 2], [d + d d], [W]
-        double* pin = nullptr;                 // the slab's read-out
+        Readout ro;                            // [2 G n_r + 2]
+        DevBuf<double> ell, s;                 // [d + d d], [W]
         double* pin_ell = nullptr;             // [d + d d] the ellipsoid on its way to the device
         std::vector<double> active, staged;    // [d + d d] each (empty: none)
         std::vector<double> pend_active, pend_staged;   // ... as they were at the pending request
         double r2[mcmc::kEvMaxRadii] = {};
-        size_t n_words = 0;
         int n_r = 0;
-        bool on = false;
-        int64_t n_acc = 0;                     // accumulations since the last closing request / set
-        int64_t pend_n = 0;                    // ... of the pending read-out
-        hipEvent_t ev = nullptr;
-        bool pending = false;
+        void release()
+        {
+            ro.release();
+            ell.release(); s.release();
+            if (pin_ell) (void)hipHostFree(pin_ell);
+            pin_ell = nullptr;
+            active.clear(); staged.clear(); pend_active.clear(); pend_staged.clear();
+            n_r = 0;
+        }
     } evd;
     // derived parameters (mcmc_hip_derived_*; derived_kernels.hip): the rows z[m][W] the caller fills
-    // on the engine's stream, this accumulation's group chains, and the slab of 64-bit words
-    // N | S[m][n_col] doubles | bad[m] | kmax[m] | kmin[m] (derived_args.h) with its pinned read-out
+    // on the engine's stream, this accumulation's group chains, and the slab
+    // N | S[m][n_col] doubles | bad[m] | kmax[m] | kmin[m] (derived_args.h)
     struct Derived {
+        Readout ro;
         DevBuf<double> z, Sg, shift;           // [m][W], [G][m][n_col], [m]
-        DevBuf<unsigned long long> Ng, slab;   // [G], [n_words]
+        DevBuf<unsigned long long> Ng;         // [G]
         DevBuf<int> cross;                     // [n_cross]
-        unsigned long long* pin = nullptr;     // [n_words]
-        size_t n_words = 0;
         int m = 0, n_cross = 0, n_col = 0;
         int gs = 0, G = 0;                     // the groups of the sums (default: the engine's)
-        bool on = false;
-        int64_t n_acc = 0;                     // accumulations since the last request / set
-        int64_t pend_n = 0;                    // ... of the pending read-out
-        hipEvent_t ev = nullptr;
-        bool pending = false;
+        void release()
+        {
+            ro.release();
+            z.release(); Sg.release(); shift.release(); Ng.release(); cross.release();
+            m = n_cross = n_col = gs = G = 0;
+        }
     } dv;
-    // importance reweighting (mcmc_hip_importance_*; importance_kernels.hip): the slab of 64-bit words
+    // importance reweighting (mcmc_hip_importance_*; importance_kernels.hip): the slab
     // sums (alternative k at off[k]: [G][n_chains_k] doubles) | n[n_alt][G] | counters[n_alt][3] | the
-    // keys of c [n_alt], with its pinned read-out.  The log-weights live with the caller
+    // keys of c [n_alt].  The log-weights live with the caller
     struct Importance {
-        DevBuf<unsigned long long> slab;
-        unsigned long long* pin = nullptr;     // [n_words]
-        size_t n_words = 0, n_sums = 0;
+        Readout ro;
+        size_t n_sums = 0;
         unsigned long long off[mcmc::kImMaxAlt] = {};
         int cov[mcmc::kImMaxAlt] = {};
         int n_alt = 0;
         int gs = 0, G = 0;                     // the groups of the sums (default: the engine's)
-        bool on = false;
-        int64_t n_acc = 0;                     // accumulations since the last closing request / set
-        int64_t pend_n = 0;                    // ... of the pending read-out
-        hipEvent_t ev = nullptr;
-        bool pending = false;
+        void release()
+        {
+            ro.release();
+            n_sums = 0;
+            n_alt = gs = G = 0;
+        }
     } imp;
     // the walker shards' communicator (comm.hip; not owned): the device checkpoint all-reduces
     // its payload over it in stream order
@@ -392,6 +410,14 @@ struct mcmc_hip_ctx {
     } fnt;
 };
 
+// the end of a device product (mcmc_hip_destroy): what it holds, then the event of its read-out
+template <class P>
+inline void destroy_product(P& p)
+{
+    p.release();
+    p.ro.destroy();
+}
+
 // what the last step launcher said it was about to launch (mcmc_hip_note_step_kernel)
 inline thread_local const char* g_noted_kernel = nullptr;
 
@@ -418,12 +444,17 @@ inline int fail(mcmc_hip_ctx* h, int code, const char* fmt, ...)
     return code;
 }
 
-#define HIP_TRY(h, call)                                                                      \
+#define HIP_TRY_ELSE(h, call, undo)                                                           \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
+        if (e_ != hipSuccess) {                                                               \
+            undo;                                                                             \
             return fail(h, MCMC_HIP_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
+        }                                                                                     \
     } while (0)
+#define HIP_TRY(h, call) HIP_TRY_ELSE(h, call, (void)0)
+// inside the configure of a device product P: a failure leaves it released, not half-built
+#define HIP_TRY_BUILD(h, P, call) HIP_TRY_ELSE(h, call, (P).release())
 
 inline hipEvent_t get_event(mcmc_hip_ctx* h)
 {

@@ -27,6 +27,7 @@ from __future__ import annotations
 import numpy as np
 
 from .engine import ERR_CALLBACK, EngineError
+from .product import DeviceProduct, option_dict
 
 MAX_NAMES = 32              # derived_args.h: kDvMaxNames
 OPTION_KEYS = ("cross",)
@@ -220,13 +221,8 @@ def parse_option(opt, sampled):
     if opt is False:
         return False
     sampled = list(sampled)
-    if opt is None or opt is True:
-        opt = {"cross": "all"}
-    if not isinstance(opt, dict):
-        raise DerivedError(f"derived_stats: expected None, False or a dict, got {opt!r}")
-    unknown = sorted(set(opt) - set(OPTION_KEYS))
-    if unknown:
-        raise DerivedError(f"derived_stats: unknown key(s) {unknown}; valid keys: {list(OPTION_KEYS)}")
+    opt = option_dict(True if opt is None else opt, "derived_stats", OPTION_KEYS, DerivedError, {"cross": "all"},
+                      expected="None, False or a dict")
     cross = opt.get("cross", "all")
     if isinstance(cross, str):
         if cross != "all":
@@ -265,27 +261,22 @@ ENGINE_METHODS = ("configure_derived", "derived_row_views", "derived_get_values"
                   "request_derived", "fetch_derived", "derived_set")
 
 
-class DerivedAccumulator:
-    """What the sampler holds of the derived parameters while it runs: a device product.  It exists
-    whenever the model has function-derived parameters, whatever `derived_stats` says (False: the
-    functions are still evaluated, for the stored rows and the marginals; nothing is summed).
-
-    HERE the sums are floats and the unfinished interval is NEVER split: it stays on the device,
-    `_peek` reads it without disturbing it, and an interval's sums are the requested read-out alone.
+class DerivedAccumulator(DeviceProduct):
+    """What the sampler holds of the derived parameters while it runs: a device product whose
+    unfinished interval is never split (the peek reads out and sets back).  It exists whenever the
+    model has function-derived parameters, whatever `derived_stats` says (False: the functions are
+    still evaluated, for the stored rows and the marginals; nothing is summed: `live` is False).
     `current`: the rows of z hold the values of the state as it is; the sampler calls `stale()`
     whenever the walkers have moved."""
 
-    name, reports = "derived", True
-    option = "derived_stats"
+    name, option = "derived", "derived_stats"
 
     def __init__(self, cfg, spec, host):
-        self.cfg, self.spec, self.host, self.engine = cfg, spec, host, None
+        super().__init__(cfg, spec, host)
         self.funcs = list(spec.derived_functions)
         self.names = [f.name for f in self.funcs]
-        self.stats = cfg is not False
-        self.reports = self.stats
+        self.stats = self.live = self.reports = cfg is not False
         self.cross = list(cfg["cross"]) if self.stats else []
-        self.ivs, self.open, self.fetched = [], None, None
         self.shift, self.current = None, False
 
     @classmethod
@@ -375,40 +366,6 @@ class DerivedAccumulator:
         if self.stats:
             self.engine.accumulate_derived()
 
-    def request(self):
-        if self.stats:
-            self.engine.request_derived()
-
-    def fetch_requested(self):
-        if self.stats and self.fetched is None:
-            self.fetched = self.engine.fetch_derived()
-
-    def _peek(self, pending):
-        """The sums of the unfinished interval, read WITHOUT disturbing them: read out (which zeroes
-        them in stream order) and set back to the same values."""
-        eng = self.engine
-        if eng is not None and self.stats:
-            if pending:
-                self.fetch_requested()
-            eng.request_derived()
-            self.open = eng.fetch_derived()
-            eng.derived_set(self.open)
-        return self.open
-
-    def file(self, n_snap):
-        """The interval's sums: what the request at this checkpoint read out."""
-        if not self.stats:
-            return
-        fetched, self.fetched = self.fetched, None
-        if fetched is None:    # (no read-out was queued: request and fetch now)
-            self.engine.request_derived()
-            fetched = self.engine.fetch_derived()
-        if n_snap:
-            self.ivs.append(fetched)
-
-    def drop(self, k):
-        self.ivs = self.ivs[k:]
-
     def _xshift(self):
         ix = self.spec.sampled.index
         full = np.zeros(self.spec.d) if self.xshift is None else self.xshift
@@ -418,13 +375,7 @@ class DerivedAccumulator:
         """The intervals of the window, in their order, plus the unfinished interval."""
         host, m, nc = self.host, len(self.names), len(self.cross)
         total = zero_part(m, nc)
-        parts = list(self.ivs)
-        if self.fetched is not None:   # (requested, not filed yet: the newest interval)
-            parts.append(self.fetched)
-        last = self._peek(pending)
-        if last is not None:
-            parts.append(last)
-        for p in parts:
+        for p in self._parts(pending):
             total = add_parts(total, p)
         out = Derived(self.names, self.cross, self.shift, self._xshift(), total["n"] * int(host.n_walkers),
                       total["N"], total["A"], total["B"], total["C"], total["X"], total["V"], total["bad"],
@@ -509,8 +460,3 @@ class DerivedAccumulator:
             self.engine.derived_set(self.open)
         except EngineError as e:
             fail("derived_stats: %s", str(e), cause=e)
-
-    def detach(self, pending=False):
-        if self.engine is not None and self.stats:
-            self._peek(pending)       # (kept for product() after the engine is gone)
-        self.engine = None

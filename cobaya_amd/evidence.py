@@ -31,6 +31,7 @@ import math
 import numpy as np
 
 from .engine import EngineError
+from .product import DeviceProduct, option_dict, option_int
 
 MAX_RADII = 8               # evidence_args.h: kEvMaxRadii
 MAX_DIM = 256               # evidence_args.h: kEvMaxDim
@@ -245,15 +246,9 @@ def parse_option(opt):
     """The sampler option `evidence` -> None (off) or {"radii": [f_r], "every": k}.  `True` = the
     default ladder beside every moment snapshot.  Refuses, by the option's name, unknown keys,
     radii that are not 1..8 ascending positive numbers and an `every` below 1."""
-    if opt is None or opt is False:
+    opt = option_dict(opt, "evidence", OPTION_KEYS, EvidenceError)
+    if opt is None:
         return None
-    if opt is True:
-        opt = {}
-    if not isinstance(opt, dict):
-        raise EvidenceError(f"evidence: expected True, None or a dict, got {opt!r}")
-    unknown = sorted(set(opt) - set(OPTION_KEYS))
-    if unknown:
-        raise EvidenceError(f"evidence: unknown key(s) {unknown}; valid keys: {list(OPTION_KEYS)}")
     radii = opt.get("radii", DEFAULT_RADII)
     try:
         ok = not isinstance(radii, (str, bytes)) and all(
@@ -265,11 +260,8 @@ def parse_option(opt):
             or any(b <= a for a, b in zip(radii, radii[1:])):
         raise EvidenceError(f"evidence: radii must be 1..{MAX_RADII} ascending positive numbers, got "
                             f"{opt.get('radii')!r}")
-    every = opt.get("every", 1)
-    if isinstance(every, bool) or not isinstance(every, (int, np.integer, float)) or int(every) != every \
-            or int(every) < 1:
-        raise EvidenceError(f"evidence: every must be an integer >= 1, got {every!r}")
-    return {"radii": radii, "every": int(every)}
+    every = option_int(opt.get("every", 1), "evidence: every", 1, None, EvidenceError)
+    return {"radii": radii, "every": every}
 
 
 # ---------------------------------------------------------------------------------- the sampler's side
@@ -277,44 +269,26 @@ ENGINE_METHODS = ("configure_evidence", "evidence_set_ellipsoid", "accumulate_ev
                   "fetch_evidence", "evidence_set", "evidence_layout")
 
 
-class EvidenceAccumulator:
-    """What the sampler holds of the sums while it runs: a device product, with the methods
-    `marginals.MarginalsAccumulator` states and one more, `learned(centre, covmat)`, which the
-    sampler calls after every checkpoint that yields a positive-definite covariance.
+class EvidenceAccumulator(DeviceProduct):
+    """What the sampler holds of the sums while it runs: a device product whose unfinished interval
+    is never split, and the one with `learned(centre, covmat)`.  A part is the closing request's
+    read-out: sums, counts, `n` and the ellipsoid it was taken under; the peek is a request that does
+    not close.  The ellipsoid handed to `learned` is only staged; the engine activates it, with a
+    fresh c, inside the next closing request, so no interval mixes two ellipsoids."""
 
-    HERE the sums are floats and the unfinished interval is NEVER split: it stays on the device,
-    `_peek` reads it without disturbing it (a request that does not close), and an interval is the
-    closing request's read-out alone: sums, counts, `n` and the ellipsoid it was taken under.  The
-    ellipsoid handed to `learned` is only staged; the engine activates it, with a fresh c, inside
-    the next closing request, so no interval mixes two ellipsoids.  `open`: the open interval as
-    last read, which is what a product is formed from once the engine is gone."""
-
-    name, reports = "evidence", True
+    name, closes, error, ENGINE_METHODS, MAX_DIM = "evidence", True, EvidenceError, ENGINE_METHODS, MAX_DIM
+    tempered = ("evidence: the sums weigh the walkers as they are, which at temperature %g follow "
+                "the tempered law, not the posterior; use temperature: 1 or turn evidence off")
+    predates = "evidence: this engine keeps no evidence sums (its library predates mcmc_hip_evidence_*)"
 
     def __init__(self, cfg, spec, host):
-        self.cfg, self.spec, self.host, self.engine = cfg, spec, host, None
-        self.ivs, self.open, self.fetched = [], None, None
+        super().__init__(cfg, spec, host)
         self.phase, self.centre = 0, None
         self.r2 = np.array([f * spec.d for f in cfg["radii"]], dtype=np.float64)
 
-    @classmethod
-    def from_option(cls, opt, spec, engine_factory, host):
-        try:
-            cfg = parse_option(opt)
-        except EvidenceError as e:
-            host.fail("%s", str(e), cause=e)
-        if cfg is None:
-            return None
-        if host.temperature != 1:
-            host.fail("evidence: the sums weigh the walkers as they are, which at temperature %g follow "
-                      "the tempered law, not the posterior; use temperature: 1 or turn evidence off",
-                      host.temperature)
-        if not all(hasattr(engine_factory, m) for m in ENGINE_METHODS):
-            host.fail("evidence: this engine keeps no evidence sums (its library predates "
-                      "mcmc_hip_evidence_*)")
-        if spec.d > MAX_DIM:
-            host.fail("evidence: the evidence kernel serves at most %d parameters, not %d", MAX_DIM, spec.d)
-        return cls(cfg, spec, host)
+    @staticmethod
+    def parse(opt, spec):
+        return parse_option(opt)
 
     def attach(self, engine, resumed=False, centre=None, covmat=None):
         """Hand the radii to the engine and activate the first ellipsoid: the initial points' mean
@@ -337,9 +311,6 @@ class EvidenceAccumulator:
         if self.phase % self.cfg["every"] == 0:
             self.engine.accumulate_evidence()
 
-    def request(self):
-        self.engine.request_evidence(True)
-
     def learned(self, centre, covmat):
         """Stage the ellipsoid of the window's pooled mean and covariance (no mean: the centre
         stays).  A covariance the library cannot factorise leaves the ellipsoids as they are."""
@@ -349,32 +320,6 @@ class EvidenceAccumulator:
             self.engine.evidence_set_ellipsoid(self.centre, covmat)
         except EngineError:
             pass
-
-    def fetch_requested(self):
-        if self.fetched is None:
-            self.fetched = self.engine.fetch_evidence()
-
-    def _peek(self, pending):
-        """The open interval, read WITHOUT disturbing it."""
-        eng = self.engine
-        if eng is not None:
-            if pending:
-                self.fetch_requested()
-            eng.request_evidence(False)
-            self.open = eng.fetch_evidence()
-        return self.open
-
-    def file(self, n_snap):
-        """The interval: what the closing request at this checkpoint read out."""
-        fetched, self.fetched = self.fetched, None
-        if fetched is None:    # (no read-out was queued: request and fetch now)
-            self.engine.request_evidence(True)
-            fetched = self.engine.fetch_evidence()
-        if n_snap:
-            self.ivs.append(fetched)
-
-    def drop(self, k):
-        self.ivs = self.ivs[k:]
 
     def _meta(self, part):
         """(ln volume, clipped) per radius of a part's ellipsoid, worked out once."""
@@ -387,12 +332,7 @@ class EvidenceAccumulator:
     def product(self, intervals, combined=False, pending=False):
         """The intervals of the window, in their order, plus the unfinished interval."""
         host, d, n_r = self.host, self.spec.d, len(self.r2)
-        parts = list(self.ivs)
-        if self.fetched is not None:   # (requested, not filed yet: the newest interval)
-            parts.append(self.fetched)
-        last = self._peek(pending)
-        if last is not None:
-            parts.append(last)
+        parts, last = self._parts(pending), self.open
         parts = [p for p in parts if p["n"] > 0 and p["active"] is not None]
         n, G = len(parts), (last["sums"].shape[0] if last is not None else 0)
         sums = np.array([p["sums"] for p in parts], dtype=np.float64).reshape(n, G, n_r)
@@ -468,8 +408,3 @@ class EvidenceAccumulator:
                                      int(z["ev_open_n"][0]), act, stg)
         except EngineError as e:
             fail("evidence: %s", str(e), cause=e)
-
-    def detach(self, pending=False):
-        if self.engine is not None:
-            self._peek(pending)       # (kept for product() after the engine is gone)
-        self.engine = None

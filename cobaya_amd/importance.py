@@ -38,6 +38,7 @@ import numpy as np
 from .derived import check_values
 from .engine import ERR_CALLBACK, EngineError
 from .model import UnsupportedModel, parse_derived_function
+from .product import DeviceProduct, known_keys
 
 MAX_ALT = 8                 # importance_args.h: kImMaxAlt
 MAX_DIM = 256               # importance_args.h: kImMaxDim
@@ -355,9 +356,7 @@ def parse_option(opt, sampled, derived=()):
         what = f"importance: alternative {str(name)!r}"
         if not isinstance(alt, dict):
             raise ImportanceError(f"{what}: expected a dict with the key 'function' (and 'cov'), got {alt!r}")
-        unknown = sorted(set(alt) - set(OPTION_KEYS))
-        if unknown:
-            raise ImportanceError(f"{what}: unknown key(s) {unknown}; valid keys: {list(OPTION_KEYS)}")
+        known_keys(alt, what, OPTION_KEYS, ImportanceError)
         if alt.get("function") is None:
             raise ImportanceError(f"{what}: no 'function' (the log-weight: a callable, a 'lambda ...' string or a "
                                   "'package.module:name' string)")
@@ -390,42 +389,26 @@ ENGINE_METHODS = ("configure_importance", "importance_layout", "importance_row_v
                   "request_importance", "fetch_importance", "importance_set")
 
 
-class ImportanceAccumulator:
-    """What the sampler holds of the sums while it runs: a device product.
+class ImportanceAccumulator(DeviceProduct):
+    """What the sampler holds of the sums while it runs: a device product whose unfinished interval
+    is never split.  A part is the closing request's read-out: sums, counts and the c it was taken
+    under; the peek is a request that does not close.  `eval_seconds`: host time spent in the
+    log-weight functions (queueing their torch operations)."""
 
-    The sums are floats and the unfinished interval is NEVER split: it stays on the device, `_peek`
-    reads it without disturbing it (a request that does not close), and an interval is the closing
-    request's read-out alone: sums, counts and the c it was taken under.  `open`: the open interval as
-    last read, which is what a product is formed from once the engine is gone.  `eval_seconds`: host
-    time spent in the log-weight functions (queueing their torch operations)."""
-
-    name, reports = "importance", True
+    name, closes, error, ENGINE_METHODS, MAX_DIM = "importance", True, ImportanceError, ENGINE_METHODS, MAX_DIM
+    tempered = ("importance: the sums weigh the walkers as they are, which at temperature %g follow "
+                "the tempered law, not the posterior; use temperature: 1 or turn importance off")
+    predates = "importance: this engine keeps no importance sums (its library predates mcmc_hip_importance_*)"
 
     def __init__(self, cfg, spec, host):
-        self.cfg, self.spec, self.host, self.engine = cfg, spec, host, None
+        super().__init__(cfg, spec, host)
         self.names = [a["name"] for a in cfg]
         self.cov = [bool(a["cov"]) for a in cfg]
-        self.ivs, self.open, self.fetched = [], None, None
         self.shift, self.G, self.eval_seconds = None, 0, 0.0
 
-    @classmethod
-    def from_option(cls, opt, spec, engine_factory, host):
-        try:
-            cfg = parse_option(opt, spec.sampled, [f.name for f in getattr(spec, "derived_functions", None) or []])
-        except ImportanceError as e:
-            host.fail("%s", str(e), cause=e)
-        if cfg is None:
-            return None
-        if host.temperature != 1:
-            host.fail("importance: the sums weigh the walkers as they are, which at temperature %g follow "
-                      "the tempered law, not the posterior; use temperature: 1 or turn importance off",
-                      host.temperature)
-        if not all(hasattr(engine_factory, m) for m in ENGINE_METHODS):
-            host.fail("importance: this engine keeps no importance sums (its library predates "
-                      "mcmc_hip_importance_*)")
-        if spec.d > MAX_DIM:
-            host.fail("importance: the importance kernel serves at most %d parameters, not %d", MAX_DIM, spec.d)
-        return cls(cfg, spec, host)
+    @staticmethod
+    def parse(opt, spec):
+        return parse_option(opt, spec.sampled, [f.name for f in getattr(spec, "derived_functions", None) or []])
 
     def attach(self, engine, resumed=False, centre=None, covmat=None):
         """Hand the alternatives to the engine.  The sums are taken about the moment shift (`centre`);
@@ -468,44 +451,9 @@ class ImportanceAccumulator:
     def accumulate(self):
         self.engine.accumulate_importance(self.evaluate())
 
-    def request(self):
-        self.engine.request_importance(True)
-
-    def fetch_requested(self):
-        if self.fetched is None:
-            self.fetched = self.engine.fetch_importance()
-
-    def _peek(self, pending):
-        """The open interval, read WITHOUT disturbing it."""
-        eng = self.engine
-        if eng is not None:
-            if pending:
-                self.fetch_requested()
-            eng.request_importance(False)
-            self.open = eng.fetch_importance()
-        return self.open
-
-    def file(self, n_snap):
-        """The interval: what the closing request at this checkpoint read out."""
-        fetched, self.fetched = self.fetched, None
-        if fetched is None:    # (no read-out was queued: request and fetch now)
-            self.engine.request_importance(True)
-            fetched = self.engine.fetch_importance()
-        if n_snap:
-            self.ivs.append(fetched)
-
-    def drop(self, k):
-        self.ivs = self.ivs[k:]
-
     def product(self, intervals, combined=False, pending=False):
         """The intervals of the window, in their order, plus the unfinished interval."""
-        host = self.host
-        parts = list(self.ivs)
-        if self.fetched is not None:   # (requested, not filed yet: the newest interval)
-            parts.append(self.fetched)
-        last = self._peek(pending)
-        if last is not None:
-            parts.append(last)
+        host, parts = self.host, self._parts(pending)
         shift = np.zeros(self.spec.d) if self.shift is None else self.shift
         out = Importance.from_parts(self.names, self.spec.sampled, shift, self.cov, int(host.n_walkers), parts, self.G)
         if combined and host.size > 1:
@@ -591,8 +539,3 @@ class ImportanceAccumulator:
             self.engine.importance_set(self.open)
         except EngineError as e:
             fail("importance: %s", str(e), cause=e)
-
-    def detach(self, pending=False):
-        if self.engine is not None:
-            self._peek(pending)       # (kept for product() after the engine is gone)
-        self.engine = None

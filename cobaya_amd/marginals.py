@@ -18,6 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from .engine import EngineError
+from .product import DeviceProduct, option_dict, option_int, option_ranges
 
 MAX_BINS_1D = 1024          # marginal_args.h: kMargMaxBins1
 MAX_BINS_2D = 64            # marginal_args.h: kMargMaxBins2
@@ -200,17 +201,11 @@ def parse_option(opt, sampled, derived=()):
     64 MiB.  `derived`: the names of function-derived parameters, which `params`, `pairs` and
     `ranges` may list beside the sampled ones ("all" stays the sampled ones); each needs an explicit
     `ranges` entry."""
-    if opt is None or opt is False:
+    opt = option_dict(opt, "marginals", OPTION_KEYS, MarginalsError, {"params": "all"})
+    if opt is None:
         return None
     sampled, derived = list(sampled), [str(n) for n in derived]
     known = sampled + derived
-    if opt is True:
-        opt = {"params": "all"}
-    if not isinstance(opt, dict):
-        raise MarginalsError(f"marginals: expected True, None or a dict, got {opt!r}")
-    unknown = sorted(set(opt) - set(OPTION_KEYS))
-    if unknown:
-        raise MarginalsError(f"marginals: unknown key(s) {unknown}; valid keys: {list(OPTION_KEYS)}")
     params = opt.get("params", "all")
     if isinstance(params, str):
         if params != "all":
@@ -240,38 +235,14 @@ def parse_option(opt, sampled, derived=()):
     if not params and not out_pairs:
         raise MarginalsError("marginals: neither params nor pairs lists anything (use None to turn "
                              "the option off)")
-    bins, bins2d = opt.get("bins", 128), opt.get("bins2d", 32)
-    for key, v, cap in (("bins", bins, MAX_BINS_1D), ("bins2d", bins2d, MAX_BINS_2D)):
-        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= cap:
-            raise MarginalsError(f"marginals: {key} must be an integer in 1..{cap}, got {v!r}")
-    bins, bins2d = int(bins), int(bins2d)
+    bins = option_int(opt.get("bins", 128), "marginals: bins", 1, MAX_BINS_1D, MarginalsError)
+    bins2d = option_int(opt.get("bins2d", 32), "marginals: bins2d", 1, MAX_BINS_2D, MarginalsError)
     nbytes = 8 * slab_size(len(params), bins, len(out_pairs), bins2d)
     if nbytes > MAX_SLAB_BYTES:
         raise MarginalsError(f"marginals: {len(params)} parameters x {bins} bins and {len(out_pairs)} "
                              f"pairs x {bins2d}^2 bins take {nbytes} bytes of counters, above the "
                              f"{MAX_SLAB_BYTES} allowed: list fewer pairs or lower bins2d")
-    ranges = opt.get("ranges", "prior")
-    if isinstance(ranges, str):
-        if ranges not in ("prior", "covmat"):
-            raise MarginalsError(f"marginals: ranges must be a dict, 'prior' or 'covmat', got {ranges!r}")
-    elif isinstance(ranges, dict):
-        bad = sorted(str(n) for n in ranges if n not in known)
-        if bad:
-            raise MarginalsError(f"marginals: ranges names unknown parameter(s) {bad}")
-        clean = {}
-        for n, r in ranges.items():
-            try:
-                lo, hi = float(r[0]), float(r[1])
-                ok = len(r) == 2
-            except (TypeError, ValueError, IndexError):
-                ok = False
-            if not ok or not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
-                raise MarginalsError(f"marginals: ranges[{n!r}] must be a finite [lo, hi] with lo < hi, "
-                                     f"got {r!r}")
-            clean[str(n)] = (lo, hi)
-        ranges = clean
-    else:
-        raise MarginalsError(f"marginals: ranges must be a dict, 'prior' or 'covmat', got {ranges!r}")
+    ranges = option_ranges(opt.get("ranges", "prior"), "marginals", known, MarginalsError)
     in_use = params + [n for pr in out_pairs for n in pr]
     unranged = sorted({n for n in in_use if n in derived and not (isinstance(ranges, dict) and n in ranges)})
     if unranged:
@@ -324,62 +295,34 @@ ENGINE_METHODS = ("configure_marginals", "accumulate_marginals", "request_margin
                   "fetch_marginals", "marginals_set")
 
 
-class MarginalsAccumulator:
-    """What the sampler holds of the histograms while it runs.  A DEVICE PRODUCT is a class with
-    these methods, listed in `EnsembleMCMC.PRODUCT_CLASSES` (the others:
-    `AutoCorrAccumulator`, `BestFitAccumulator`, `EvidenceAccumulator`):
+class MarginalsAccumulator(DeviceProduct):
+    """What the sampler holds of the histograms while it runs: a device product whose unfinished
+    interval is split.  A part is (counts, accumulations); `ivs` keeps the counts.  Where the
+    counts are held changes no sum."""
 
-      from_option(opt, spec, engine_factory, host) -> the object, or None where the option is off;
-          refuses by the option's name BEFORE the engine is created.  `host` is what the sampler hands
-          in: fail(msg, *args, cause=None), n_walkers, size, rank, all_reduce_sum, temperature,
-          snapshot_steps (the steps between two moment snapshots)
-      attach(engine, resumed, centre, covmat): configure the engine, cross-check its layout
-      accumulate(), request(): beside every moment snapshot; beside every checkpoint request
-      fetch_requested(): the requested read-out, kept in `fetched` until file(n_snap) closes the
-          interval (an entry of `ivs` if n_snap is non-zero: one per interval of the window)
-      drop(k): the window moved forward by k intervals
-      save(pending) -> arrays for the state file, load(z, n_intervals): from it
-      product(intervals, combined, pending); detach(pending): the engine goes, product() still works
-      name, reports: the option, the key in products() and the file `prefix.<name>.npz`; whether the
-          product has a summary() for the log
-      learned(centre, covmat) -- OPTIONAL: after every checkpoint that yields a positive-definite
-          covariance, the window's pooled mean (None where the host does not know it) and
-          `mean_of_covs`
-    `pending`: a checkpoint is requested and not processed yet -- its read-out is then fetched before
-    anything else is read, and a product counts it as the newest interval.
+    name, reports, split, error, ENGINE_METHODS = "marginals", False, True, MarginalsError, ENGINE_METHODS
+    tempered = ("marginals: the histograms count the walkers as they are, which at temperature %g "
+                "follow the tempered law, not the posterior; use temperature: 1 or turn marginals off")
+    predates = "marginals: this engine has no marginal histograms (its library predates mcmc_hip_marginals_*)"
 
-    HERE the counts are integers and the unfinished interval is split: `open` is the host's part
-    (counts, accumulations), the device holds the rest, and `_drain` moves that over (which zeroes
-    it on the device).  Where the counts are held changes no sum."""
+    @staticmethod
+    def parse(opt, spec):
+        return parse_option(opt, spec.sampled, [f.name for f in getattr(spec, "derived_functions", ())])
 
-    name, reports = "marginals", False
+    @staticmethod
+    def _merge(a, b):
+        return a[0] + b[0], int(a[1]) + int(b[1])
 
-    def __init__(self, cfg, spec, host):
-        self.cfg, self.spec, self.host, self.engine = cfg, spec, host, None
-        self.ivs, self.open, self.fetched = [], None, None
+    def _empty(self):
+        return np.zeros(self.cfg["n_counters"], np.uint64), 0
 
-    @classmethod
-    def from_option(cls, opt, spec, engine_factory, host):
-        try:
-            cfg = parse_option(opt, spec.sampled, [f.name for f in getattr(spec, "derived_functions", ())])
-        except MarginalsError as e:
-            host.fail("%s", str(e), cause=e)
-        if cfg is None:
-            return None
-        if host.temperature != 1:
-            host.fail("marginals: the histograms count the walkers as they are, which at temperature %g "
-                      "follow the tempered law, not the posterior; use temperature: 1 or turn "
-                      "marginals off", host.temperature)
-        if not all(hasattr(engine_factory, m) for m in ENGINE_METHODS):
-            host.fail("marginals: this engine has no marginal histograms (its library predates "
-                      "mcmc_hip_marginals_*)")
-        return cls(cfg, spec, host)
+    def _kept(self, part):
+        return part[0]
 
     def attach(self, engine, resumed=False, centre=None, covmat=None):
         """Fix the ranges and hand the layout to the engine.  A resumed run repeats the ranges of
         the state file: `load` configures the engine."""
         self.engine = engine
-        self.accumulate, self.request = engine.accumulate_marginals, engine.request_marginals
         if resumed:
             return
         try:
@@ -410,42 +353,11 @@ class MarginalsAccumulator:
                     cfg["n_counters"], slab_size(len(cfg["params"]), cfg["bins"], 0, 0)):
                 fail("marginals: the engine lays its counters out differently (%r) from the "
                      "product (%d counters)", lay, cfg["n_counters"])
-        self.open = (np.zeros(cfg["n_counters"], np.uint64), 0)
-
-    def fetch_requested(self):
-        if self.fetched is None:
-            self.fetched = self.engine.fetch_marginals()
-
-    def _drain(self, pending):
-        """Move what the device holds of the unfinished interval into `open`."""
-        if pending:
-            self.fetch_requested()
-        self.engine.request_marginals()
-        c, n = self.engine.fetch_marginals()
-        self.open = (self.open[0] + c, self.open[1] + n)
-
-    def file(self, n_snap):
-        """The interval's counts: what the request read out plus what the host held of it."""
-        counts = self.open[0] + (self.fetched[0] if self.fetched is not None else 0)
-        self.fetched = None
-        self.open = (np.zeros_like(counts), 0)
-        if n_snap:
-            self.ivs.append(counts)
-
-    def drop(self, k):
-        self.ivs = self.ivs[k:]
+        self.open = self._empty()
 
     def product(self, intervals, combined=False, pending=False):
         cfg = self.cfg
-        if self.engine is not None:
-            self._drain(pending)
-        slab, n_acc = self.open[0].copy(), int(self.open[1])
-        if self.fetched is not None:   # (requested, not filed yet: the newest interval)
-            slab += self.fetched[0]
-            n_acc += int(self.fetched[1])
-        for (n_snap, _, _), c in zip(intervals, self.ivs):
-            slab += c
-            n_acc += int(n_snap)
+        slab, n_acc = self._merged(intervals, pending)
         n_samples = n_acc * int(self.host.n_walkers)
         if combined and self.host.size > 1:
             # ONE host all-reduce of integers (exact in float64 below 2^53), here and not in the loop
@@ -499,8 +411,3 @@ class MarginalsAccumulator:
                  len(self.ivs), n_intervals)
         # the unfinished interval goes back to the device, where the next accumulation adds to it
         self.engine.marginals_set(z["marg_open"], int(z["marg_open_n"]))
-
-    def detach(self, pending=False):
-        if self.engine is not None and self.open is not None:
-            self._drain(pending)     # (the device's part of the unfinished interval)
-        self.engine = self.accumulate = self.request = None
