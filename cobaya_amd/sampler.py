@@ -287,6 +287,7 @@ class EnsembleMCMC:
                        EvidenceAccumulator, ImportanceAccumulator)
     _products = ()
     _derived = None      # the DerivedAccumulator, where the model has function-derived parameters
+    _derived_at_close = None   # the likelihood's derived columns of the stored rows, kept by close()
 
     def _max_dim(self):
         """The cap of the engine behind the seam: its max_dim() where it has one, else 128 (the
@@ -1546,9 +1547,11 @@ class EnsembleMCMC:
         if len(rows):
             x = rows[:, 5:5 + spec.d]
             derived = None
-            if spec.derived:
-                derived = np.vstack([self.engine.evaluate(x[i:i + 65536], derived=True)[2]
-                                     for i in range(0, len(rows), 65536)])
+            if spec.derived and self.engine is None:
+                # (after close(): the likelihood's derived columns of the stored rows, as kept there)
+                derived = self._derived_at_close
+            elif spec.derived:
+                derived = self._likelihood_derived(x)
             elif spec.derived_functions:   # (they came with the row: `_snapshot`)
                 derived = rows[:, 5 + spec.d:]
             parts = (spec.component_loglikes(x) if len(spec.components) > 1 else None)
@@ -1556,6 +1559,11 @@ class EnsembleMCMC:
                           parts)
         coll.chain_ids = rows[:, 0].astype(np.int64) if len(rows) else np.zeros(0, np.int64)
         return coll
+
+    def _likelihood_derived(self, x):
+        """The likelihood's derived parameters of the points x[n, d], from the engine."""
+        return np.vstack([self.engine.evaluate(x[i:i + 65536], derived=True)[2]
+                          for i in range(0, len(x), 65536)])
 
     def _build_collection(self):
         """All rows this process holds: those of earlier legs (read back from the chain file
@@ -1670,6 +1678,10 @@ class EnsembleMCMC:
                 p.detach(self._ckpt_pending)
             self._bounds.engine = None
             self._materialise_row_views()   # products()/samples() stay valid after close
+            if self.spec.derived and self._rows:
+                # (the likelihood's derived parameters of a stored row are evaluated by the engine)
+                self._derived_at_close = np.vstack([self._likelihood_derived(r[:, 5:5 + self.spec.d])
+                                                    for r in self._rows])
             self.engine.close()
             self.engine = None
 
