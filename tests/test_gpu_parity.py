@@ -36,6 +36,33 @@ def random_target(d, K, rng, spread=0.05):
     return means, np.array(covs)
 
 
+def start_points(rng, d, W, means, covs, kinds, a, b, periodic):
+    """x0 of make_pair, drawn from `rng` as random_target left it: around the first mode, inside
+    the uniform intervals, normal priors from their own distribution, periodic parameters
+    wrapped into their interval.  (Shared with tests/instantiations.py: the oracle alone starts
+    where engine and oracle start here.)"""
+    K = 0 if means is None else len(means)
+    m0 = means[0] if K else np.full(d, 0.5)
+    s0 = np.sqrt(np.diag(covs[0])) if K else np.full(d, 0.1)
+    x0 = np.clip(m0 + rng.normal(size=(W, d)) * s0, 1e-3, 1 - 1e-3)
+    # (intervals narrower than [0, 1]: the walkers start inside them)
+    av, bv = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
+    uni = np.asarray(kinds) == 0
+    if periodic is not None:   # (a periodic parameter is wrapped into its interval below)
+        uni &= np.asarray(periodic) == 0
+    x0[:, uni] = np.clip(x0[:, uni], np.maximum(1e-3, av + 1e-3 * (bv - av))[uni],
+                         np.minimum(1 - 1e-3, bv - 1e-3 * (bv - av))[uni])
+    if kinds is not None:
+        for i, k in enumerate(kinds):
+            if k == 1:
+                x0[:, i] = a[i] + rng.normal(size=W) * b[i]
+    if periodic is not None:   # a periodic parameter starts inside its interval
+        for i, per in enumerate(periodic):
+            if per and (a[i], b[i]) != (0.0, 1.0):
+                x0[:, i] = a[i] + (x0[:, i] - a[i]) % (b[i] - a[i])
+    return x0
+
+
 def make_pair(d, W, gs, K=1, kinds=None, a=None, b=None, periodic=None, seed=7, T=1.0,
               burn_in=0, cap=0, weights=None, normalized=True, rng=None, walker_offset=0,
               max_tries=None, blocks=None, over=None, drag_last_slow=-1, drag_steps=0,
@@ -85,24 +112,7 @@ def make_pair(d, W, gs, K=1, kinds=None, a=None, b=None, periodic=None, seed=7, 
                      incremental=incremental,
                      # (which mixtures carry the log-density of every mode is the engine's rule)
                      carry_modes=eng.carries_modes(), carry_periodic=eng.carries_periodic())
-    m0 = means[0] if K else np.full(d, 0.5)
-    s0 = np.sqrt(np.diag(covs[0])) if K else np.full(d, 0.1)
-    x0 = np.clip(m0 + rng.normal(size=(W, d)) * s0, 1e-3, 1 - 1e-3)
-    # (intervals narrower than [0, 1]: the walkers start inside them)
-    av, bv = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    uni = np.asarray(kinds) == 0
-    if periodic is not None:   # (a periodic parameter is wrapped into its interval below)
-        uni &= np.asarray(periodic) == 0
-    x0[:, uni] = np.clip(x0[:, uni], np.maximum(1e-3, av + 1e-3 * (bv - av))[uni],
-                         np.minimum(1 - 1e-3, bv - 1e-3 * (bv - av))[uni])
-    if kinds is not None:
-        for i, k in enumerate(kinds):
-            if k == 1:
-                x0[:, i] = a[i] + rng.normal(size=W) * b[i]
-    if periodic is not None:   # a periodic parameter starts inside its interval
-        for i, per in enumerate(periodic):
-            if per and (a[i], b[i]) != (0.0, 1.0):
-                x0[:, i] = a[i] + (x0[:, i] - a[i]) % (b[i] - a[i])
+    x0 = start_points(rng, d, W, means, covs, kinds, a, b, periodic)
     eng.set_state(x0)
     st = O.State(prob, x0, burn_in=burn_in, row_cap=cap)
     return eng, prob, st
