@@ -110,6 +110,7 @@ def translation_units(dims, big=True):
             ("evidence_kernels.hip", "evidence", []),   # the sums of the truncated harmonic mean (evidence)
             ("derived_kernels.hip", "derived", []),     # moments of the derived rows
             ("importance_kernels.hip", "importance", []),   # weighted moments under exp(log-weight)
+            ("importance_hist_kernels.hip", "importance_hist", []),   # ... and their marginal histograms
             ("comm.hip", "comm", [])]   # the RCCL communicator (bound at run time)
     tus += [("incremental_kernels.hip", f"incremental_{lo}", [f"-DMCMC_DQ_LO={lo}", f"-DMCMC_DQ_HI={hi}"])
             for lo, hi in INC_DQ_RANGES]

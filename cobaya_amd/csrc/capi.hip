@@ -418,6 +418,7 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     if (h->ck.pin_out) (void)hipHostFree(h->ck.pin_out);
     destroy_product(h->mg); destroy_product(h->ac); destroy_product(h->bf);
     destroy_product(h->evd); destroy_product(h->dv); destroy_product(h->imp);
+    h->imp.hist.destroy();   // (the second read-out of the importance: its reweighted histograms)
     if (h->ck.ev) (void)hipEventDestroy(h->ck.ev);
     if (h->pin_mom) (void)hipHostFree(h->pin_mom);
     if (h->pin_T) (void)hipHostFree(h->pin_T);

@@ -22,6 +22,7 @@ int mcmc_hip_marginals_configure(mcmc_hip_ctx* h, int32_t n1, const int32_t* dim
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (n1 == 0 && n2 == 0) {
         h->mg.release();
+        h->imp.release_hist();
         return MCMC_HIP_OK;
     }
     if (n1 > 0 && !dims1) return fail(h, MCMC_HIP_ERR_ARG, "dims1 is null");
@@ -56,6 +57,7 @@ int mcmc_hip_marginals_configure(mcmc_hip_ctx* h, int32_t n1, const int32_t* dim
     }
     auto& M = h->mg;
     M.release();
+    h->imp.release_hist();   // (the reweighted histograms of the importance follow this layout)
     const size_t c1 = n1 ? marg_counters_1d(bins1) : 0, c2 = n2 ? marg_counters_2d(bins2) : 0;
     std::vector<mcmc::MargEntry> E((size_t)n1 + n2);
     for (int k = 0; k < n1; ++k) {

@@ -27,6 +27,7 @@
 #include "evidence_args.h"
 #include "derived_args.h"
 #include "importance_args.h"
+#include "importance_hist_args.h"
 #include "comm.h"
 #include "inc_choice.h"
 #include "readout.h"
@@ -364,17 +365,34 @@ struct mcmc_hip_ctx {
     } dv;
     // importance reweighting (mcmc_hip_importance_*; importance_kernels.hip): the slab
     // sums (alternative k at off[k]: [G][n_chains_k] doubles) | n[n_alt][G] | counters[n_alt][3] | the
-    // keys of c [n_alt].  The log-weights live with the caller
+    // keys of c [n_alt].  The log-weights live with the caller.
+    // The reweighted marginal histograms (mcmc_hip_importance_hist_*; importance_hist_kernels.hip) are a
+    // second slab, `hist`: per alternative with histograms, ascending, lo[n_counters] | hi[n_counters]
+    // (the words of 128-bit counters in the layout of the marginals slab), behind them saturated[n_hist].
+    // Its intervals are the sums': it is copied out and zeroed by the same request, behind the same event
+    // (`ro.ev`); of `hist` only the slab, the mirror, `pending` and `pend_n` are in use
     struct Importance {
-        Readout ro;
-        size_t n_sums = 0;
+        Readout ro, hist;
+        DevBuf<unsigned long long> q;          // [n_hist][W] the quantised weights of an accumulation
+        size_t n_sums = 0, n_counters = 0;
         unsigned long long off[mcmc::kImMaxAlt] = {};
         int cov[mcmc::kImMaxAlt] = {};
-        int n_alt = 0;
+        int hist_on[mcmc::kImMaxAlt] = {};     // per alternative
+        int hist_alt[mcmc::kImMaxAlt] = {};    // the alternative of histogram set h
+        int n_alt = 0, n_hist = 0;
         int gs = 0, G = 0;                     // the groups of the sums (default: the engine's)
+        void release_hist()
+        {
+            hist.release();
+            q.release();
+            n_counters = 0;
+            n_hist = 0;
+            for (int k = 0; k < mcmc::kImMaxAlt; ++k) hist_on[k] = hist_alt[k] = 0;
+        }
         void release()
         {
             ro.release();
+            release_hist();
             n_sums = 0;
             n_alt = gs = G = 0;
         }

@@ -186,6 +186,10 @@ SYMBOLS = [
                                             c_double_p, c_int64_p]),
     ("mcmc_hip_importance_set", C.c_int, [_H, c_double_p, C.c_int64, c_uint64_p, C.c_int64, c_uint64_p,
                                           c_double_p, C.c_int64]),
+    ("mcmc_hip_importance_hist_configure", C.c_int, [_H, c_int32_p]),
+    ("mcmc_hip_importance_hist_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int64_p, c_int64_p]),
+    ("mcmc_hip_importance_hist_fetch", C.c_int, [_H, c_uint64_p, c_uint64_p, C.c_int64, c_uint64_p, c_int64_p]),
+    ("mcmc_hip_importance_hist_set", C.c_int, [_H, c_uint64_p, c_uint64_p, C.c_int64, c_uint64_p]),
     ("mcmc_hip_derived_configure", C.c_int, [_H, C.c_int32, C.c_int32, c_int32_p, c_double_p]),
     ("mcmc_hip_derived_set_group_size", C.c_int, [_H, C.c_int32]),
     ("mcmc_hip_derived_layout", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p, c_int64_p]),
@@ -1250,6 +1254,48 @@ class Engine:
         self._check(self._lib.mcmc_hip_importance_set(
             self._h, _dp(s), len(s) if ok else -1, n.ctypes.data_as(c_uint64_p), len(n),
             cnt.ctypes.data_as(c_uint64_p), _dp(c), int(part["n_acc"])))
+
+    # -- ... and their reweighted marginal histograms (128-bit fixed-point counters as words lo, hi)
+    def configure_importance_hist(self, on):
+        """`on` [n_alt]: truthy where the alternative keeps a weighted copy of the histograms of
+        `configure_marginals` (mcmc_hip_importance_hist_configure); after `configure_importance` and
+        `configure_marginals`.  None truthy: off, everything is freed."""
+        on = np.ascontiguousarray([1 if v else 0 for v in on], dtype=np.int32)
+        n_alt = self.importance_layout()["n_alt"]
+        if len(on) != n_alt:
+            raise EngineError(ERR_ARG, f"configure_importance_hist: {len(on)} flags for {n_alt} alternatives")
+        self._check(self._lib.mcmc_hip_importance_hist_configure(self._h, _ip(on) if len(on) else None))
+
+    def importance_hist_layout(self):
+        """{"n_hist", "on" [n_alt], "n_counters", "n_words"} (mcmc_hip_importance_hist_layout); n_words
+        == 0: off.  The slab: per alternative with histograms, ascending, lo[n_counters] |
+        hi[n_counters]; behind them saturated[n_hist]."""
+        nh, nc, nw, on = C.c_int32(), C.c_int64(), C.c_int64(), np.zeros(8, np.int32)
+        self._check(self._lib.mcmc_hip_importance_hist_layout(self._h, C.byref(nh), _ip(on), C.byref(nc), C.byref(nw)))
+        return {"n_hist": nh.value, "on": [bool(v) for v in on[:self.importance_layout()["n_alt"]]],
+                "n_counters": nc.value, "n_words": nw.value}
+
+    def fetch_importance_hist(self):
+        """{"lo", "hi" [n_hist, n_counters] uint64, "saturated" [n_hist] uint64, "n_acc"} of the last
+        `request_importance`; waits for the copy only."""
+        lay = self.importance_hist_layout()
+        lo = np.zeros((lay["n_hist"], lay["n_counters"]), np.uint64)
+        hi, sat, k = np.zeros_like(lo), np.zeros(lay["n_hist"], np.uint64), C.c_int64()
+        self._check(self._lib.mcmc_hip_importance_hist_fetch(
+            self._h, lo.ctypes.data_as(c_uint64_p), hi.ctypes.data_as(c_uint64_p), lo.size,
+            sat.ctypes.data_as(c_uint64_p), C.byref(k)))
+        return {"lo": lo, "hi": hi, "saturated": sat, "n_acc": int(k.value)}
+
+    def importance_hist_set(self, part):
+        """Restore the histograms of an unfinished interval (resume): a dict as `fetch_importance_hist`
+        gives, behind `importance_set`, which carries c and the accumulations."""
+        lo = np.ascontiguousarray(part["lo"], dtype=np.uint64).reshape(-1)
+        hi = np.ascontiguousarray(part["hi"], dtype=np.uint64).reshape(-1)
+        sat = np.ascontiguousarray(part["saturated"], dtype=np.uint64).reshape(-1)
+        ok = len(lo) == len(hi) and len(sat) == self.importance_hist_layout()["n_hist"]
+        self._check(self._lib.mcmc_hip_importance_hist_set(
+            self._h, lo.ctypes.data_as(c_uint64_p), hi.ctypes.data_as(c_uint64_p), len(lo) if ok else -1,
+            sat.ctypes.data_as(c_uint64_p)))
 
     # -- the checkpoint on the device
     def checkpoint_set_ring(self, intervals=(), min_capacity=16, first_index=0):

@@ -25,8 +25,15 @@ float64 (S2, a sum of squares, by its square) and added in interval order, and
 the standard errors are delete-one-group jackknives (groups are independent chains, so they absorb the
 correlation between snapshots).
 
-Out of scope: reweighted marginal histograms, derived or bestfit products under the new weights,
-function-derived names as arguments, `temperature != 1`, and writing reweighted chains.
+An alternative with `"marginals": True` also keeps a weighted copy of the run's `marginals` histograms
+("Importance marginals"; importance_hist_kernels.hip): a used walker adds the
+fixed-point weight q = floor(min(e, 2^16) * 2^32) where the unweighted histogram adds 1, into 128-bit
+counters kept as words (lo, hi), with the intervals and the c of the sums.  On the host a counter is worth
+(hi 2^64 + lo) 2^-32; the intervals are scaled by exp(c - C) and added in interval order, like S1.
+`Importance.marginals(name)` gives them as a `marginals.WeightedMarginals`.
+
+Out of scope: derived or bestfit products under the new weights, function-derived names as arguments,
+per-alternative bins or ranges, `temperature != 1`, and writing reweighted chains.
 """
 from __future__ import annotations
 
@@ -37,6 +44,7 @@ import numpy as np
 
 from .derived import check_values
 from .engine import ERR_CALLBACK, EngineError
+from .marginals import MAX_SLAB_BYTES, WeightedMarginals, slab_size
 from .model import UnsupportedModel, parse_derived_function
 from .product import DeviceProduct, known_keys
 
@@ -44,8 +52,12 @@ MAX_ALT = 8                 # importance_args.h: kImMaxAlt
 MAX_DIM = 256               # importance_args.h: kImMaxDim
 MAX_COV_DIM = 128           # importance_args.h: kImMaxCovDim
 CLAMP = 700.0               # importance_args.h: kImClamp
-OPTION_KEYS = ("function", "cov")
+OPTION_KEYS = ("function", "cov", "marginals")
 LOW_ESS = 0.05              # an ESS fraction below this is warned about
+HIST_CAP = 65536.0          # importance_hist_args.h: kImHistCap, the largest e a histogram takes in
+HIST_METHODS = ("configure_importance_hist", "importance_hist_layout", "fetch_importance_hist",
+                "importance_hist_set")
+MARG_KEYS = ("params", "pairs", "bins", "bins2d", "ranges")
 
 
 class ImportanceError(ValueError):
@@ -65,6 +77,12 @@ def scaled(S, f):
         out = f * S
         out[:, 1] = (f * f) * S[:, 1]
     return out
+
+
+def hist_value(lo, hi):
+    """The 128-bit fixed-point counters (words lo, hi) as float64 weights: (hi 2^64 + lo) 2^-32."""
+    return (np.asarray(hi, np.uint64).astype(np.float64) * 2.0 ** 64
+            + np.asarray(lo, np.uint64).astype(np.float64)) * 2.0 ** -32
 
 
 def split_sums(flat, d, cov, G):
@@ -90,13 +108,32 @@ class Importance:
     about; `cov` [n_alt]: whether Q is kept; `n_walkers`: the walkers of the G groups held; `n_acc`:
     accumulations of the window; `C` [n_alt]: the centring constant the sums are scaled to; `sums`: per
     alternative float64 [G, n_chains], the window's total per group; `n` uint64 [n_alt, G]: the used
-    walkers; `n_zero`, `n_nonfinite`, `n_clamped` int64 [n_alt]."""
+    walkers; `n_zero`, `n_nonfinite`, `n_clamped` int64 [n_alt].  `hist` (None: no alternative keeps
+    reweighted marginals): {"layout": the `params`, `pairs`, `bins`, `bins2d`, `ranges` of the run's
+    marginals, "weights": per alternative None or float64 [n_counters] in units of exp(C), "saturated"
+    [n_alt]}."""
 
     reports = True
 
-    def __init__(self, names, params, shift, cov, n_walkers, n_acc, C, sums, n, n_zero, n_nonfinite, n_clamped):
+    def __init__(self, names, params, shift, cov, n_walkers, n_acc, C, sums, n, n_zero, n_nonfinite, n_clamped,
+                 hist=None):
         self.names, self.params = [str(v) for v in names], [str(v) for v in params]
         na, d = len(self.names), len(self.params)
+        self.marg, self.hist, self.n_saturated = None, [None] * na, np.zeros(na, np.int64)
+        if hist is not None and any(w is not None for w in hist["weights"]):
+            lay = hist["layout"]
+            self.marg = {"params": [str(v) for v in lay["params"]], "pairs": [(str(a), str(b)) for a, b in lay["pairs"]],
+                         "bins": int(lay["bins"]), "bins2d": int(lay["bins2d"]),
+                         "ranges": {str(k): (float(v[0]), float(v[1])) for k, v in lay["ranges"].items()}}
+            nc = slab_size(len(self.marg["params"]), self.marg["bins"], len(self.marg["pairs"]), self.marg["bins2d"])
+            if len(hist["weights"]) != na:
+                raise ImportanceError(f"importance: {len(hist['weights'])} sets of histograms for {na} alternatives")
+            try:
+                self.hist = [None if w is None else np.array(w, dtype=np.float64).reshape(nc) for w in hist["weights"]]
+                self.n_saturated = np.array(hist["saturated"], dtype=np.int64).reshape(na)
+            except ValueError as e:
+                raise ImportanceError(f"importance: the reweighted histograms do not fit their layout of {nc} "
+                                      f"counters ({e})") from None
         self.d, self.n_walkers, self.n_acc = d, int(n_walkers), int(n_acc)
         try:
             self.shift = np.array(shift, dtype=np.float64).reshape(d)
@@ -115,10 +152,11 @@ class Importance:
                                   f"together ({e})") from None
 
     @classmethod
-    def from_parts(cls, names, params, shift, cov, n_walkers, parts, n_groups=None):
+    def from_parts(cls, names, params, shift, cov, n_walkers, parts, n_groups=None, marg=None):
         """From the read-outs of the window's intervals, in their order: dicts {"sums" (flat), "n"
         [n_alt, G], "counters" [n_alt, 3], "c" [n_alt], "n_acc"}.  Intervals without an accumulation
-        are skipped."""
+        are skipped.  `marg` (with reweighted marginals): the layout of the run's marginals plus "on"
+        [n_alt]; every part then has "hist": {"lo", "hi" [n_hist, n_counters], "saturated" [n_hist]}."""
         na, d = len(names), len(params)
         parts = [p for p in parts if int(p["n_acc"]) > 0]
         G = int(np.asarray(parts[0]["n"]).reshape(na, -1).shape[1]) if parts else int(n_groups or 0)
@@ -126,7 +164,18 @@ class Importance:
         C = c.max(axis=0) if len(parts) else np.zeros(na)
         sums = [np.zeros((G, n_chains(d, cv))) for cv in cov]
         n, cnt = np.zeros((na, G), np.uint64), np.zeros((na, 3), np.int64)
+        on = [k for k in range(na) if marg is not None and marg["on"][k]]
+        weights, sat = [None] * na, np.zeros(na, np.int64)
+        if on:
+            nc = slab_size(len(marg["params"]), marg["bins"], len(marg["pairs"]), marg["bins2d"])
+            for k in on:
+                weights[k] = np.zeros(nc)
         for p, ci in zip(parts, c):
+            for h, k in enumerate(on):     # (the scaling of S1: to the common C, in interval order)
+                v = hist_value(np.asarray(p["hist"]["lo"]).reshape(len(on), -1)[h],
+                               np.asarray(p["hist"]["hi"]).reshape(len(on), -1)[h])
+                weights[k] = weights[k] + math.exp(ci[k] - C[k]) * v
+                sat[k] += int(np.asarray(p["hist"]["saturated"]).reshape(-1)[h])
             split = split_sums(p["sums"], d, cov, G)
             for k in range(na):
                 with np.errstate(invalid="ignore", over="ignore"):
@@ -134,7 +183,8 @@ class Importance:
             n = n + np.asarray(p["n"], np.uint64).reshape(na, G)
             cnt = cnt + np.asarray(p["counters"]).reshape(na, 3).astype(np.int64)
         return cls(names, params, shift, cov, n_walkers, sum(int(p["n_acc"]) for p in parts), C, sums, n,
-                   cnt[:, 0], cnt[:, 1], cnt[:, 2])
+                   cnt[:, 0], cnt[:, 1], cnt[:, 2],
+                   {"layout": marg, "weights": weights, "saturated": sat} if on else None)
 
     # -- look-ups
     def _k(self, name):
@@ -167,6 +217,21 @@ class Importance:
     def clamped(self, name):
         """Walkers whose log-weight lay more than 700 above its interval's c."""
         return int(self.n_clamped[self._k(name)])
+
+    def saturated(self, name):
+        """Used walkers whose weight lay above 2^16 times the largest their interval opened with: they
+        entered the reweighted histograms as 2^16 (0 for an alternative without histograms)."""
+        return int(self.n_saturated[self._k(name)])
+
+    def marginals(self, name):
+        """The run's marginal histograms under the weights of `name`: a `WeightedMarginals`."""
+        k = self._k(name)
+        if self.hist[k] is None:
+            raise ImportanceError(f"importance: alternative {name!r} keeps no reweighted marginals (give it "
+                                  "'marginals': True beside the sampler option `marginals`)")
+        m = self.marg
+        return WeightedMarginals(m["params"], m["pairs"], m["bins"], m["bins2d"], m["ranges"], self.hist[k],
+                                 self.n_acc, self.n_samples, self.saturated(name), self.C[k])
 
     # -- the estimates
     def _tot(self, k):
@@ -252,12 +317,16 @@ class Importance:
             return full / St[0] - np.outer(m, m)
 
     def warnings(self, name):
-        """What the run's last log lines warn about: a low ESS fraction, clamped weights."""
+        """What the run's last log lines warn about: a low ESS fraction, clamped weights, weights that
+        saturated the reweighted histograms."""
         out, f = [], self.ess_fraction(name)
         if self.n_used(name) and f < LOW_ESS:
             out.append("ESS fraction %.3g is below %g: the sampled posterior barely covers this one" % (f, LOW_ESS))
         if self.clamped(name):
             out.append("%d weights were clamped at exp(%g) above their interval's largest" % (self.clamped(name), CLAMP))
+        if self.saturated(name):
+            out.append("%d weights entered the reweighted marginals saturated at %g times their interval's largest"
+                       % (self.saturated(name), HIST_CAP))
         return out
 
     def lines(self):
@@ -286,7 +355,23 @@ class Importance:
 
     # -- arithmetic, files
     def _layout(self):
-        return (tuple(self.names), tuple(self.params), self.shift.tobytes(), tuple(self.cov_kept), self.n_acc)
+        base = (tuple(self.names), tuple(self.params), self.shift.tobytes(), tuple(self.cov_kept), self.n_acc)
+        if self.marg is None:
+            return base
+        m = self.marg
+        return base + (tuple(w is not None for w in self.hist), tuple(m["params"]), tuple(m["pairs"]), m["bins"],
+                       m["bins2d"], tuple(sorted(m["ranges"].items())))
+
+    def _hist(self, weights=None, saturated=None):
+        """The constructor's `hist` (None: no histograms)."""
+        if self.marg is None:
+            return None
+        return {"layout": self.marg, "weights": self.hist if weights is None else weights,
+                "saturated": self.n_saturated if saturated is None else saturated}
+
+    def hist_scaled_to(self, C):
+        """The reweighted histograms per alternative (None: none), scaled from self.C to C >= self.C."""
+        return [None if w is None else math.exp(self.C[k] - C[k]) * w for k, w in enumerate(self.hist)]
 
     def scaled_to(self, C):
         """The sums per alternative, scaled from self.C to the centring constants C >= self.C."""
@@ -302,7 +387,10 @@ class Importance:
         return Importance(self.names, self.params, self.shift, self.cov_kept, self.n_walkers + other.n_walkers,
                           self.n_acc, C, sums, np.concatenate((self.n, other.n), axis=1),
                           self.n_zero + other.n_zero, self.n_nonfinite + other.n_nonfinite,
-                          self.n_clamped + other.n_clamped)
+                          self.n_clamped + other.n_clamped,
+                          self._hist([None if a is None else a + b
+                                      for a, b in zip(self.hist_scaled_to(C), other.hist_scaled_to(C))],
+                                     self.n_saturated + other.n_saturated))
 
     def __eq__(self, other):
         return (isinstance(other, Importance) and self._layout() == other._layout()
@@ -310,7 +398,9 @@ class Importance:
                 and np.array_equal(self.n, other.n)
                 and all(np.array_equal(a, b, equal_nan=True) for a, b in zip(self.sums, other.sums))
                 and all(np.array_equal(getattr(self, k), getattr(other, k))
-                        for k in ("n_zero", "n_nonfinite", "n_clamped")))
+                        for k in ("n_zero", "n_nonfinite", "n_clamped", "n_saturated"))
+                and all((a is None) == (b is None) and (a is None or np.array_equal(a, b, equal_nan=True))
+                        for a, b in zip(self.hist, other.hist)))
 
     __hash__ = None
 
@@ -322,6 +412,15 @@ class Importance:
                          ess=np.array([self.ess(v) for v in self.names]),
                          mean=np.array([self.mean(v) for v in self.names]),
                          std=np.array([self.std(v) for v in self.names]))
+        if self.marg is not None:      # (only then: a file without histograms is what it always was)
+            m, names = self.marg, list(self.marg["ranges"])
+            extra.update(hist_on=np.array([w is not None for w in self.hist], dtype=np.int64),
+                         hist_weights=np.array([w for w in self.hist if w is not None], dtype=np.float64),
+                         hist_saturated=self.n_saturated, marg_params=np.array(m["params"], dtype=str),
+                         marg_pairs=np.array(m["pairs"], dtype=str).reshape(-1, 2),
+                         marg_bins=np.array([m["bins"], m["bins2d"]], dtype=np.int64),
+                         marg_range_names=np.array(names, dtype=str),
+                         marg_ranges=np.array([m["ranges"][v] for v in names], dtype=np.float64).reshape(-1, 2))
         with open(path, "wb") as f:   # (np.savez would append ".npz" to a bare name)
             np.savez(f, names=np.array(self.names, dtype=str), params=np.array(self.params, dtype=str),
                      shift=self.shift, cov_kept=np.array(self.cov_kept, dtype=np.int64),
@@ -333,15 +432,23 @@ class Importance:
         z = np.load(path, allow_pickle=False)
         names = [str(v) for v in z["names"]]
         cnt = z["counters"].reshape(len(names), 3)
+        hist = None
+        if "hist_on" in z.files:
+            rows = iter(z["hist_weights"])
+            hist = {"layout": {"params": z["marg_params"], "pairs": z["marg_pairs"], "bins": z["marg_bins"][0],
+                               "bins2d": z["marg_bins"][1],
+                               "ranges": {str(v): r for v, r in zip(z["marg_range_names"], z["marg_ranges"])}},
+                    "weights": [next(rows) if v else None for v in z["hist_on"]], "saturated": z["hist_saturated"]}
         return cls(names, [str(v) for v in z["params"]], z["shift"], z["cov_kept"], int(z["geometry"][0]),
                    int(z["geometry"][1]), z["C"], [z["sums_%d" % k] for k in range(len(names))], z["n"],
-                   cnt[:, 0], cnt[:, 1], cnt[:, 2])
+                   cnt[:, 0], cnt[:, 1], cnt[:, 2], hist)
 
 
 # ---------------------------------------------------------------------------------- the option
 def parse_option(opt, sampled, derived=()):
     """The sampler option `importance` -> None (off) or a list of {"name", "function" (a
-    `model.DerivedFunction`: callable and argument names), "cov"}.  `sampled`: the sampled parameters
+    `model.DerivedFunction`: callable and argument names), "cov", "marginals" (whether the alternative
+    keeps a weighted copy of the run's marginal histograms)}.  `sampled`: the sampled parameters
     the arguments are bound to by name; `derived`: the function-derived names, which are refused as
     arguments.  Refuses, by the option's name, anything else that cannot be served."""
     if opt is None or opt is False:
@@ -355,7 +462,7 @@ def parse_option(opt, sampled, derived=()):
     for name, alt in opt.items():
         what = f"importance: alternative {str(name)!r}"
         if not isinstance(alt, dict):
-            raise ImportanceError(f"{what}: expected a dict with the key 'function' (and 'cov'), got {alt!r}")
+            raise ImportanceError(f"{what}: expected a dict with the key 'function' (and 'cov', 'marginals'), got {alt!r}")
         known_keys(alt, what, OPTION_KEYS, ImportanceError)
         if alt.get("function") is None:
             raise ImportanceError(f"{what}: no 'function' (the log-weight: a callable, a 'lambda ...' string or a "
@@ -380,7 +487,11 @@ def parse_option(opt, sampled, derived=()):
         if cov and d > MAX_COV_DIM:
             raise ImportanceError(f"{what}: cov: True needs d <= {MAX_COV_DIM}, not d = {d} (means and variances "
                                   "are kept at any d)")
-        out.append({"name": str(name), "function": fn, "cov": bool(d <= MAX_COV_DIM if cov is None else cov)})
+        marg = alt.get("marginals")
+        if marg is not None and not isinstance(marg, (bool, np.bool_)):
+            raise ImportanceError(f"{what}: marginals must be True, False or None, got {marg!r}")
+        out.append({"name": str(name), "function": fn, "cov": bool(d <= MAX_COV_DIM if cov is None else cov),
+                    "marginals": bool(marg)})
     return out
 
 
@@ -404,7 +515,56 @@ class ImportanceAccumulator(DeviceProduct):
         super().__init__(cfg, spec, host)
         self.names = [a["name"] for a in cfg]
         self.cov = [bool(a["cov"]) for a in cfg]
+        self.want = [bool(a.get("marginals")) for a in cfg]      # reweighted marginals, per alternative
+        self.marg = None                                         # the MarginalsAccumulator they follow
         self.shift, self.G, self.eval_seconds = None, 0, 0.0
+
+    def pair_with(self, marginals, engine_factory):
+        """The sampler hands over its `MarginalsAccumulator` (None: the option is off) once both are
+        made, BEFORE the engine is created: an alternative that asks for marginals is refused by name
+        without the sampler option, on an engine without the entry points, or above the slab allowed."""
+        if not any(self.want):
+            return
+        first = self.names[self.want.index(True)]
+        if marginals is None:
+            self.host.fail("importance: alternative %r: marginals: True needs the sampler option `marginals` "
+                           "(its parameters, pairs, bins and ranges are the ones reweighted)", first)
+        if not all(hasattr(engine_factory, m) for m in HIST_METHODS):
+            self.host.fail("importance: alternative %r: marginals: True: this engine keeps no reweighted marginal "
+                           "histograms (its library predates mcmc_hip_importance_hist_*)", first)
+        c = marginals.cfg
+        nbytes = 16 * sum(self.want) * slab_size(len(c["params"]), c["bins"], len(c["pairs"]), c["bins2d"])
+        if nbytes > MAX_SLAB_BYTES:
+            self.host.fail("importance: marginals: True for %d alternatives takes %d bytes of 128-bit counters, "
+                           "above the %d allowed: ask fewer alternatives for them, or fewer pairs or bins of "
+                           "`marginals`", sum(self.want), nbytes, MAX_SLAB_BYTES)
+        self.marg = marginals
+
+    def _configure_hist(self):
+        """Once the layout of the marginals is known to the engine (`attach` on a fresh run, `load` on a
+        resume: `MarginalsAccumulator` comes first in either)."""
+        try:
+            self.engine.configure_importance_hist(self.want)
+            lay = self.engine.importance_hist_layout()
+        except EngineError as e:
+            self.host.fail("importance: %s", str(e), cause=e)
+        nc = int(self.marg.cfg["n_counters"])
+        if ([bool(v) for v in lay["on"]], int(lay["n_counters"])) != (self.want, nc):
+            self.host.fail("importance: the engine lays its reweighted histograms out differently (%r) from the "
+                           "marginals (%d counters)", lay, nc)
+
+    def _fetch(self):
+        part = self.engine.fetch_importance()
+        if self.marg is not None:      # (the same request copied out both slabs)
+            part["hist"] = self.engine.fetch_importance_hist()
+        return part
+
+    def _marg_layout(self):
+        if self.marg is None:
+            return None
+        c = self.marg.cfg
+        return {"params": c["params"], "pairs": c["pairs"], "bins": c["bins"], "bins2d": c["bins2d"],
+                "ranges": c["resolved"], "on": self.want}
 
     @staticmethod
     def parse(opt, spec):
@@ -425,6 +585,8 @@ class ImportanceAccumulator(DeviceProduct):
         want = sum(self.G * n_chains(self.spec.d, c) for c in self.cov)
         if (lay["n_alt"], [bool(c) for c in lay["cov"]], lay["n_sums"]) != (len(self.cov), self.cov, want):
             self.host.fail("importance: the engine lays its sums out differently (%r) from the product", lay)
+        if self.marg is not None and not resumed:
+            self._configure_hist()
 
     # -- evaluation
     def evaluate(self):
@@ -455,7 +617,8 @@ class ImportanceAccumulator(DeviceProduct):
         """The intervals of the window, in their order, plus the unfinished interval."""
         host, parts = self.host, self._parts(pending)
         shift = np.zeros(self.spec.d) if self.shift is None else self.shift
-        out = Importance.from_parts(self.names, self.spec.sampled, shift, self.cov, int(host.n_walkers), parts, self.G)
+        out = Importance.from_parts(self.names, self.spec.sampled, shift, self.cov, int(host.n_walkers), parts, self.G,
+                                    self._marg_layout())
         if combined and host.size > 1:
             out = self._combined(out)
         return out
@@ -479,34 +642,56 @@ class ImportanceAccumulator(DeviceProduct):
             host.fail("importance: the processes hold different windows (accumulations, groups: %r)",
                       head[:, na:].tolist())
         C = head[:, :na].max(axis=0)
+        held = [w for w in own.hist_scaled_to(C) if w is not None]
         row = np.concatenate([s.reshape(-1) for s in own.scaled_to(C)]
                              + [own.n.astype(np.float64).reshape(-1), own.n_zero.astype(np.float64),
-                                own.n_nonfinite.astype(np.float64), own.n_clamped.astype(np.float64)])
+                                own.n_nonfinite.astype(np.float64), own.n_clamped.astype(np.float64)]
+                             + held + ([own.n_saturated.astype(np.float64)] if held else []))
         buf = np.zeros((size, len(row)))
         buf[rank] = row
         buf = self._reduced(buf.reshape(-1)).reshape(size, len(row))
         n_sums = sum(s.size for s in own.sums)
         sums = [np.concatenate(s, axis=0) for s in zip(*(split_sums(b[:n_sums], own.d, self.cov, G) for b in buf))]
         n = np.concatenate([b[n_sums:n_sums + na * G].astype(np.uint64).reshape(na, G) for b in buf], axis=1)
-        cnt = buf[:, n_sums + na * G:].sum(axis=0).astype(np.int64).reshape(3, na)
+        at = n_sums + na * G
+        cnt = buf[:, at:at + 3 * na].sum(axis=0).astype(np.int64).reshape(3, na)
+        hist = None
+        if held:    # (the rows are added in rank order)
+            tot, at = buf[:, at + 3 * na:].sum(axis=0), 0
+            weights = [None] * na
+            for k, w in enumerate(own.hist):
+                if w is not None:
+                    weights[k], at = tot[at:at + len(w)], at + len(w)
+            hist = own._hist(weights, tot[at:].astype(np.int64))
         return Importance(self.names, own.params, own.shift, self.cov, own.n_walkers * size, own.n_acc, C, sums, n,
-                          cnt[0], cnt[1], cnt[2])
+                          cnt[0], cnt[1], cnt[2], hist)
 
     # -- the state file
     def _stack(self, parts):
         k, na, G = len(parts), len(self.names), self.G
         n_sums = sum(G * n_chains(self.spec.d, c) for c in self.cov)
-        return {"sums": np.array([p["sums"] for p in parts], dtype=np.float64).reshape(k, n_sums),
-                "n": np.array([p["n"] for p in parts], dtype=np.uint64).reshape(k, na, G),
-                "counters": np.array([p["counters"] for p in parts], dtype=np.uint64).reshape(k, na, 3),
-                "c": np.array([p["c"] for p in parts], dtype=np.float64).reshape(k, na),
-                "nacc": np.array([p["n_acc"] for p in parts], dtype=np.int64).reshape(k)}
+        out = {"sums": np.array([p["sums"] for p in parts], dtype=np.float64).reshape(k, n_sums),
+               "n": np.array([p["n"] for p in parts], dtype=np.uint64).reshape(k, na, G),
+               "counters": np.array([p["counters"] for p in parts], dtype=np.uint64).reshape(k, na, 3),
+               "c": np.array([p["c"] for p in parts], dtype=np.float64).reshape(k, na),
+               "nacc": np.array([p["n_acc"] for p in parts], dtype=np.int64).reshape(k)}
+        if self.marg is not None:      # (written only when on)
+            nh, nc = sum(self.want), int(self.marg.cfg["n_counters"])
+            out.update(hlo=np.array([p["hist"]["lo"] for p in parts], dtype=np.uint64).reshape(k, nh, nc),
+                       hhi=np.array([p["hist"]["hi"] for p in parts], dtype=np.uint64).reshape(k, nh, nc),
+                       hsat=np.array([p["hist"]["saturated"] for p in parts], dtype=np.uint64).reshape(k, nh))
+        return out
 
     @staticmethod
     def _unstack(z, prefix):
-        return [{"sums": np.array(z[prefix + "sums"][i]), "n": np.array(z[prefix + "n"][i]),
-                 "counters": np.array(z[prefix + "counters"][i]), "c": np.array(z[prefix + "c"][i]),
-                 "n_acc": int(z[prefix + "nacc"][i])} for i in range(len(z[prefix + "nacc"]))]
+        out = [{"sums": np.array(z[prefix + "sums"][i]), "n": np.array(z[prefix + "n"][i]),
+                "counters": np.array(z[prefix + "counters"][i]), "c": np.array(z[prefix + "c"][i]),
+                "n_acc": int(z[prefix + "nacc"][i])} for i in range(len(z[prefix + "nacc"]))]
+        if prefix + "hlo" in z:
+            for i, p in enumerate(out):
+                p["hist"] = {"lo": np.array(z[prefix + "hlo"][i]), "hi": np.array(z[prefix + "hhi"][i]),
+                             "saturated": np.array(z[prefix + "hsat"][i]), "n_acc": p["n_acc"]}
+        return out
 
     def save(self, pending):
         """What a resumed run must repeat (the alternatives' names and `cov`) and what it goes on from:
@@ -514,6 +699,8 @@ class ImportanceAccumulator(DeviceProduct):
         o = self._peek(pending)
         out = {"iw_names": np.array(self.names, dtype=str), "iw_cov": np.array(self.cov, dtype=np.int64),
                "iw_shift": np.zeros(self.spec.d) if self.shift is None else self.shift}
+        if self.marg is not None:
+            out["iw_hist_on"] = np.array(self.want, dtype=np.int64)
         out.update({"iw_iv_" + k: v for k, v in self._stack(self.ivs).items()})
         out.update({"iw_open_" + k: v for k, v in self._stack([o]).items()})
         return out
@@ -530,6 +717,12 @@ class ImportanceAccumulator(DeviceProduct):
         if saved != (self.names, self.cov):
             fail("importance: cannot resume -- the run was written with the alternatives %r (cov: %r), and now "
                  "has %r (cov: %r): sums of different weights do not add up", *saved, self.names, self.cov)
+        had = [bool(v) for v in z["iw_hist_on"]] if "iw_hist_on" in z else [False] * len(self.want)
+        if had != self.want:
+            fail("importance: cannot resume -- the run was written with marginals: %r per alternative, and now has "
+                 "%r: a reweighted histogram cannot begin or end in mid-run", had, self.want)
+        if self.marg is not None:      # (the marginals have configured the engine in their `load`)
+            self._configure_hist()
         self.shift = np.array(z["iw_shift"], dtype=np.float64)
         self.ivs = self._unstack(z, "iw_iv_")
         if len(self.ivs) != n_intervals:
@@ -537,5 +730,7 @@ class ImportanceAccumulator(DeviceProduct):
         self.open = self._unstack(z, "iw_open_")[0]
         try:
             self.engine.importance_set(self.open)
+            if self.marg is not None:
+                self.engine.importance_hist_set(self.open["hist"])
         except EngineError as e:
             fail("importance: %s", str(e), cause=e)

@@ -12,6 +12,9 @@ Function-derived parameters (`cobaya_amd.derived`) are histogrammed like sampled
 the engine keeps of them; each needs an explicit `ranges` entry (it has no prior).  Only they can be
 NaN: a NaN compares false with everything, so in a 1-D entry it is counted NOWHERE (neither in a bin
 nor under nor over), and in a pair it is counted `outside`.
+
+`WeightedMarginals` holds the same histograms under the weights of an importance alternative
+(`cobaya_amd.importance`; DESIGN.md section 2, "Importance marginals").
 """
 from __future__ import annotations
 
@@ -190,6 +193,84 @@ class Marginals:
         return cls([str(p) for p in z["params"]], [(str(a), str(b)) for a, b in z["pairs"]],
                    int(z["bins"][0]), int(z["bins"][1]), ranges, z["slab"], int(z["n"][0]),
                    int(z["n"][1]))
+
+
+class WeightedMarginals(Marginals):
+    """The histograms of `Marginals` under the weights of an importance alternative
+    (`Importance.marginals(name)`): float64 weights in the same layout -- names, pairs, bins and ranges
+    are those of the run's `marginals`, so both overlay bin for bin -- and the arithmetic of `Marginals`
+    (`edges`, `density`, `density2d`, `mean`, `quantile`).
+
+    `slab`: float64, the sums of the weights in units of exp(`log_scale`) (the centring constant C of
+    the alternative; no ratio -- density, mean, quantile -- depends on it); `saturated`: used walkers whose
+    weight lay above 2^16 times the largest one their interval opened with, and entered as 2^16;
+    `n_accumulations`, `n_samples`: snapshots and walkers looked at."""
+
+    def __init__(self, params, pairs, bins, bins2d, ranges, slab=None, n_accumulations=0, n_samples=0,
+                 saturated=0, log_scale=0.0):
+        super().__init__(params, pairs, bins, bins2d, ranges, None, n_accumulations, n_samples)
+        if slab is not None:
+            slab = np.array(slab, dtype=np.float64).reshape(-1)
+            if len(slab) != len(self.slab):
+                raise MarginalsError(f"marginals: this layout holds {len(self.slab)} weights, got {len(slab)}")
+        self.slab = np.zeros(len(self.slab)) if slab is None else slab
+        self.saturated, self.log_scale = int(saturated), float(log_scale)
+
+    def weights(self, name):
+        """float64 [bins]: the sum of the weights per bin of `name`."""
+        return self.counts(name)
+
+    def weights2d(self, a, b):
+        """float64 [bins2d, bins2d]: rows follow `a`, columns `b`."""
+        return self.counts2d(a, b)
+
+    def outside(self, name, b=None):
+        """As `Marginals.outside`, as weights."""
+        if b is not None:
+            return float(self._entry2d(name, b)[0])
+        e = self._entry(name)
+        return float(e[0]), float(e[1])
+
+    def merge(self, other):
+        """The weights of two shards of one run, added at their common scale."""
+        if not isinstance(other, WeightedMarginals) or self._layout() != other._layout() \
+                or self.n_accumulations != other.n_accumulations:
+            raise MarginalsError("marginals: only weighted histograms of one run (layout and accumulations) merge")
+        C = max(self.log_scale, other.log_scale)
+        slab = self.slab * np.exp(self.log_scale - C) + other.slab * np.exp(other.log_scale - C)
+        return WeightedMarginals(self.params, self.pairs, self.bins, self.bins2d, self.ranges, slab,
+                                 self.n_accumulations, self.n_samples + other.n_samples,
+                                 self.saturated + other.saturated, C)
+
+    def __add__(self, other):
+        return self.merge(other) if isinstance(other, WeightedMarginals) else NotImplemented
+
+    def __eq__(self, other):
+        return (isinstance(other, WeightedMarginals) and self._layout() == other._layout()
+                and np.array_equal(self.slab, other.slab, equal_nan=True)
+                and (self.n_accumulations, self.n_samples, self.saturated, self.log_scale)
+                == (other.n_accumulations, other.n_samples, other.saturated, other.log_scale))
+
+    __hash__ = None
+
+    def save(self, path):
+        names = self.names_in_use()
+        with open(path, "wb") as f:
+            np.savez(f, params=np.array(self.params, dtype=str),
+                     pairs=np.array(self.pairs, dtype=str).reshape(-1, 2),
+                     bins=np.array([self.bins, self.bins2d], dtype=np.int64),
+                     range_names=np.array(names, dtype=str),
+                     ranges=np.array([self.ranges[n] for n in names], dtype=np.float64).reshape(-1, 2),
+                     weights=self.slab, log_scale=np.float64(self.log_scale),
+                     n=np.array([self.n_accumulations, self.n_samples, self.saturated], dtype=np.int64))
+
+    @classmethod
+    def load(cls, path):
+        z = np.load(path, allow_pickle=False)
+        ranges = {str(n): (float(r[0]), float(r[1])) for n, r in zip(z["range_names"], z["ranges"])}
+        return cls([str(p) for p in z["params"]], [(str(a), str(b)) for a, b in z["pairs"]],
+                   int(z["bins"][0]), int(z["bins"][1]), ranges, z["weights"], int(z["n"][0]), int(z["n"][1]),
+                   int(z["n"][2]), float(z["log_scale"]))
 
 
 # ---------------------------------------------------------------------------------- the option

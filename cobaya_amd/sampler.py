@@ -197,7 +197,9 @@ HIP_DEFAULTS = {
                               # (cov: the default for d <= 128) covariances, the effective sample size and
                               # ln(Z_new / Z) with jackknife errors, summed on the device from EVERY walker
                               # of every moment snapshot of the window -- products()["importance"], a
-                              # `cobaya_amd.importance.Importance`.  None: off.  Needs temperature: 1
+                              # `cobaya_amd.importance.Importance`.  With `marginals` on, "marginals": True
+                              # in an alternative keeps a weighted copy of those histograms
+                              # (`Importance.marginals(name)`).  None: off.  Needs temperature: 1
     "shared_basis": True,     # True: the walkers of a group share one Haar basis per cycle;
                               # False: every walker draws its own (proposal.py:59-69 to the
                               # letter: the reference-faithful control, much slower)
@@ -510,6 +512,10 @@ class EnsembleMCMC:
                 for c in self.PRODUCT_CLASSES]
         self._products = [p for p in made if p is not None]
         self._derived = next((p for p in self._products if isinstance(p, DerivedAccumulator)), None)
+        for p in self._products:    # (the importance reads the layout of the marginals it reweights)
+            if isinstance(p, ImportanceAccumulator):
+                p.pair_with(next((m for m in self._products if isinstance(m, MarginalsAccumulator)), None),
+                            self._engine_factory)
         try:
             self.engine = self._engine_factory(d, W, group_size=int(self.group_size), device=int(device),
                                  seed=self.seed, walker_offset=self.rank * W,

@@ -557,6 +557,33 @@ MCMC_HIP_API int mcmc_hip_importance_set(mcmc_hip_ctx* h, const double* sums, in
                             int64_t n_groups, const uint64_t* counters, const double* c,
                             int64_t n_accumulations);
 
+/* Reweighted marginal histograms of the importance alternatives (importance_hist_kernels.hip).  The rule
+ * ("Importance marginals"): the entries, ranges and bins are those of
+ * mcmc_hip_marginals_configure; a used walker of alternative k adds the fixed-point weight
+ * q = floor(min(e, 2^16) * 2^32), e being the weight the sums use, where marginals_accumulate adds 1;
+ * saturated[k] counts e > 2^16.  Every counter is a 128-bit unsigned integer kept as two words (lo, hi):
+ * its value is (hi * 2^64 + lo) * 2^-32 at the scale exp(c[k]) of its interval.
+ * hist_configure: on[n_alt], != 0: alternative k keeps histograms.  After BOTH importance_configure and
+ *   marginals_configure (MCMC_HIP_ERR_STATE otherwise); all zeros releases everything, and so do
+ *   marginals_configure and importance_configure.  The slab: per alternative with on[k], ascending,
+ *   lo[n_counters] | hi[n_counters] in the layout of the marginals slab, then saturated[n_hist].
+ * The intervals are the sums': importance_accumulate adds to both (and launches nothing new when the
+ *   histograms are off), importance_request copies out both and with close != 0 zeroes both; a request is
+ *   refused while a histogram read-out of the last one has not been fetched; importance_set_group_size
+ *   empties both.
+ * hist_fetch: the read-out of the last importance_request (before or after importance_fetch); lo and hi
+ *   hold n = n_hist * n_counters words each, saturated n_hist.
+ * hist_set: restores an unfinished interval (resume), behind importance_set, which carries c and
+ *   n_accumulations.
+ * hist_layout: any pointer may be NULL (on: 8 entries); n_words == 0: off. */
+MCMC_HIP_API int mcmc_hip_importance_hist_configure(mcmc_hip_ctx* h, const int32_t* on);
+MCMC_HIP_API int mcmc_hip_importance_hist_layout(const mcmc_hip_ctx* h, int32_t* n_hist, int32_t* on,
+                                    int64_t* n_counters, int64_t* n_words);
+MCMC_HIP_API int mcmc_hip_importance_hist_fetch(mcmc_hip_ctx* h, uint64_t* lo, uint64_t* hi, int64_t n,
+                                   uint64_t* saturated, int64_t* n_accumulations);
+MCMC_HIP_API int mcmc_hip_importance_hist_set(mcmc_hip_ctx* h, const uint64_t* lo, const uint64_t* hi, int64_t n,
+                                 const uint64_t* saturated);
+
 /* The learn / convergence checkpoint ON THE DEVICE (MCMC.check_convergence_and_learn_proposal,
  * mcmc.py:773-1032; checkpoint_kernels.hip): the intervals between checkpoints are kept in a
  * device ring, the statistics of the window (the later half of the run, mcmc.py:787-790) are
