@@ -39,6 +39,7 @@ __global__ void __launch_bounds__(64) basis_blocked_kernel(const BlockedBasisArg
     const int pg = blockIdx.x / a.ncyc, pc = blockIdx.x % a.ncyc;
     const uint32_t group = a.group0 + (uint32_t)pg;
     const uint32_t cycle = a.cycle0 + (uint32_t)pc;
+    const uint32_t sgroup = a.shuffle_group1 ? a.shuffle_group1 - 1u : group;   // the shuffle's counter
     double* __restrict__ Vout = a.V + ((size_t)pg * a.ncyc + pc) * a.slab;
     int* __restrict__ Fout = a.vflag ? a.vflag + ((size_t)pg * a.ncyc + pc) * L : nullptr;
 
@@ -52,7 +53,7 @@ __global__ void __launch_bounds__(64) basis_blocked_kernel(const BlockedBasisArg
     // Philox words of the shuffle, in parallel; the swaps themselves are sequential
     if (L > 2)
         for (int i = 1 + t; i < L; i += 64)
-            sw[i] = philox4x32_10(a.key0, a.key1, group, kStreamPerm | ((uint32_t)a.which << 8),
+            sw[i] = philox4x32_10(a.key0, a.key1, sgroup, kStreamPerm | ((uint32_t)a.which << 8),
                                   cycle, (uint32_t)i).w0;
     __syncthreads();
     if (t == 0) {
@@ -229,6 +230,7 @@ __global__ void __launch_bounds__(256) basis_blocked_big_kernel(const BlockedBas
     const int pg = blockIdx.x / a.ncyc, pc = blockIdx.x % a.ncyc;
     const uint32_t group = a.group0 + (uint32_t)pg;
     const uint32_t cycle = a.cycle0 + (uint32_t)pc;
+    const uint32_t sgroup = a.shuffle_group1 ? a.shuffle_group1 - 1u : group;   // the shuffle's counter
     double* __restrict__ Vout = a.V + ((size_t)pg * a.ncyc + pc) * a.slab;
     int* __restrict__ Fout = a.vflag ? a.vflag + ((size_t)pg * a.ncyc + pc) * L : nullptr;
     const int ld = a.ld;
@@ -240,7 +242,7 @@ __global__ void __launch_bounds__(256) basis_blocked_big_kernel(const BlockedBas
     }
     if (L > 2)
         for (int i = 1 + t; i < L; i += 256)
-            sw[i] = philox4x32_10(a.key0, a.key1, group, kStreamPerm | ((uint32_t)a.which << 8),
+            sw[i] = philox4x32_10(a.key0, a.key1, sgroup, kStreamPerm | ((uint32_t)a.which << 8),
                                   cycle, (uint32_t)i).w0;
     __syncthreads();
     if (t == 0) {

@@ -437,6 +437,9 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     }
     h->fnt.points.release(); h->fnt.lp_t.release(); h->fnt.Ea.release(); h->fnt.ll_t.release();
     h->fnt.bad.release();
+    h->fnt.dinputs.release(); h->fnt.ll_new.release(); h->fnt.ll_c.release();
+    h->fnt.epts.release(); h->fnt.ell.release();
+    for (auto& b : h->fnt.pts) b.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -729,7 +732,7 @@ int mcmc_hip_evaluate(mcmc_hip_ctx* h, int32_t n, const double* x, double* logpr
     } else {
         HIP_TRY(h, h->k->evaluate(a, h->stream));
     }
-    if (h->fnt.on) {   // the log-prior is the `one` target's; the log-likelihood is the function's
+    if (h->fnt.on && h->fnt.n_fn == 0) {   // the log-prior is the `one` target's; the log-likelihood is the function's
         const int rc = function_call(h, n, h->ex.p, h->ell.p);
         if (rc) return rc;
     }
@@ -739,6 +742,19 @@ int mcmc_hip_evaluate(mcmc_hip_ctx* h, int32_t n, const double* x, double* logpr
         HIP_TRY(h, hipMemcpyAsync(derived, h->eder.p, sizeof(double) * n * Kd, hipMemcpyDeviceToHost,
                                   h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->fnt.on && h->fnt.n_fn > 0) {   // several functions: every one is called, summed left to right
+        auto& F = h->fnt;
+        F.last_eval_n = 0;
+        F.last_eval.resize((size_t)F.n_fn * n);
+        const int rc = functions_evaluate(h, n, x, F.last_eval.data());
+        if (rc) return rc;
+        for (int w = 0; w < n; ++w) {
+            double ll = F.last_eval[w];
+            for (int c = 1; c < F.n_fn; ++c) ll = ll + F.last_eval[(size_t)c * n + w];
+            loglike[w] = ll;
+        }
+        F.last_eval_n = n;
+    }
     if (h->fnt.on)
         for (int w = 0; w < n; ++w) {
             // (the likelihood is skipped outside the prior support, model.py:650-653: what the
@@ -786,6 +802,12 @@ int mcmc_hip_set_state(mcmc_hip_ctx* h, const double* x, int32_t* n_bad)
         HIP_TRY(h, hipMemcpyAsync(h->nrows.p, zeros.data(), sizeof(int) * W, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemsetAsync(h->stuck.p, 0, sizeof(int), s));
     if (h->fnt.bad.p) HIP_TRY(h, hipMemsetAsync(h->fnt.bad.p, 0, sizeof(int), s));
+    if (h->fnt.on && h->fnt.n_fn > 0) {   // the components of the evaluation above are the state's
+        auto& F = h->fnt;
+        if (F.last_eval_n != (int)W) return fail(h, MCMC_HIP_ERR_STATE, "no component log-likelihoods of the state");
+        HIP_TRY(h, hipMemcpyAsync(F.ll_c.p, F.last_eval.data(), sizeof(double) * F.n_fn * W, hipMemcpyHostToDevice, s));
+        F.llc_valid = true;
+    }
     HIP_TRY(h, hipMemsetAsync(h->acc_total.p, 0, sizeof(unsigned long long), s));
     // a fresh start: no thinning remainders from an earlier run (the oracle's State starts at zero;
     // mcmc_hip_set_full_state leaves them alone -- mcmc_hip_set_thin_carry follows it)
@@ -869,6 +891,7 @@ int mcmc_hip_set_full_state(mcmc_hip_ctx* h, const double* x, const double* logp
     if (h->nrows.p) HIP_TRY(h, hipMemset(h->nrows.p, 0, sizeof(int) * W));
     HIP_TRY(h, hipMemset(h->stuck.p, 0, sizeof(int)));
     if (h->fnt.bad.p) HIP_TRY(h, hipMemset(h->fnt.bad.p, 0, sizeof(int)));
+    h->fnt.llc_valid = false;   // several functions: mcmc_hip_set_component_loglikes follows, or they are formed again
     {
         unsigned long long tot = 0;
         for (size_t w = 0; w < W; ++w) tot += (unsigned long long)n_accept[w];
@@ -888,7 +911,7 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
     if (n_steps <= 0) return fail(h, MCMC_HIP_ERR_ARG, "n_steps must be > 0");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (h->bg.on) return step_binned(h, n_steps);
-    if (h->fnt.on) return step_function(h, n_steps);
+    if (h->fnt.on) return h->fnt.n_fn > 0 ? step_functions(h, n_steps) : step_function(h, n_steps);
     if (h->incremental && h->huge) return step_huge(h, n_steps);
     if (h->incremental) return step_incremental(h, n_steps);
     if (h->emit_thin > 1)

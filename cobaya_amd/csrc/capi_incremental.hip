@@ -4,9 +4,10 @@
 #include "ctx.h"
 
 // fills `V` (and `flag` when the sequence has one-parameter blocks) with the directions of
-// cycles [c0, c0 + ncyc) of sequence `which` of the blocked proposer
+// cycles [c0, c0 + ncyc) of sequence `which` of the blocked proposer; shared_schedule: every group
+// takes its slots in the order of global group 0
 int blocked_basis(mcmc_hip_ctx* h, int which, unsigned long long c0, int ncyc, int L, size_t slab,
-                  DevBuf<double>& V, DevBuf<int>& flag, bool& any_1d, hipStream_t st)
+                  DevBuf<double>& V, DevBuf<int>& flag, bool& any_1d, hipStream_t st, bool shared_schedule)
 {
     if (!st) st = h->stream;
     const int nb = (int)h->blk_size.size();
@@ -28,6 +29,8 @@ int blocked_basis(mcmc_hip_ctx* h, int which, unsigned long long c0, int ncyc, i
     b.cycle0 = (uint32_t)c0;
     b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
     b.ncyc = ncyc;
+    // one slot schedule for the whole ensemble: the shuffle of GLOBAL group 0 (function targets)
+    b.shuffle_group1 = shared_schedule ? 1u : 0u;
     HIP_TRY(h, mcmc_hip_launch_blocked_basis(&b, h->BG, st));
     return MCMC_HIP_OK;
 }

@@ -278,6 +278,215 @@ int step_function(mcmc_hip_ctx* h, int n_steps)
     return rc;
 }
 
+namespace {
+
+// ------------------------------------------------------------------ several functions over blocks
+int functions_refusals(mcmc_hip_ctx* h)
+{
+    if (h->drag_last_slow >= 0)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "function targets are sampled with Metropolis steps (dragging is not served)");
+    if (h->any_periodic)
+        return fail(h, MCMC_HIP_ERR_ARG, "a function target does not serve periodic parameters");
+    return MCMC_HIP_OK;
+}
+
+// word 0 of Philox4x32-10 (det_math.h: philox4x32_10), on the host: the slot shuffle decides which
+// functions a step calls, so the host forms it too
+uint32_t philox_w0(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3)
+{
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+// the block of every slot of `cycle` in the schedule all groups share: the Fisher-Yates shuffle of
+// basis_blocked_kernel (sequence 0) with GLOBAL group 0 in its counter
+void shared_schedule(mcmc_hip_ctx* h, unsigned long long cycle, int L)
+{
+    auto& F = h->fnt;
+    if (F.sched_cycle == cycle && F.sched_epoch == h->dir_epoch && (int)F.sched.size() == L) return;
+    F.sched.clear();
+    for (size_t b = 0; b < h->blk_size.size(); ++b)
+        F.sched.insert(F.sched.end(), (size_t)h->blk_over[b] * h->blk_size[b], (short)b);
+    const uint32_t k0 = (uint32_t)h->cfg.seed, k1 = (uint32_t)(h->cfg.seed >> 32);
+    if (L > 2)
+        for (int i = L - 1; i >= 1; --i) {
+            const uint32_t w0 = philox_w0(k0, k1, 0u, 2u, (uint32_t)cycle, (uint32_t)i);
+            const int j = (int)(((unsigned long long)w0 * (unsigned long long)(i + 1)) >> 32);
+            std::swap(F.sched[i], F.sched[j]);
+        }
+    F.sched_cycle = cycle;
+    F.sched_epoch = h->dir_epoch;
+}
+
+int functions_call_one(mcmc_hip_ctx* h, int c, int n, const double* points, double* loglike)
+{
+    auto& F = h->fnt;
+    const int rc = F.fns[c](F.users[c], n, (int)F.inputs[c].size(), points, loglike, (void*)h->stream);
+    if (rc)
+        return fail(h, MCMC_HIP_ERR_CALLBACK, "the callback of function %d of the function target returned %d", c, rc);
+    return MCMC_HIP_OK;
+}
+
+}  // namespace
+
+int functions_evaluate(mcmc_hip_ctx* h, int n, const double* x, double* comps)
+{
+    auto& F = h->fnt;
+    const size_t d = h->d;
+    HIP_TRY(h, F.ell.resize(n));
+    std::vector<double> in;
+    for (int c = 0; c < F.n_fn; ++c) {
+        const size_t dc = F.inputs[c].size();
+        in.resize((size_t)n * dc);
+        for (size_t w = 0; w < (size_t)n; ++w)
+            for (size_t k = 0; k < dc; ++k) in[w * dc + k] = x[w * d + F.inputs[c][k]];
+        HIP_TRY(h, F.epts.resize((size_t)n * dc));
+        HIP_TRY(h, hipMemcpyAsync(F.epts.p, in.data(), sizeof(double) * n * dc, hipMemcpyHostToDevice, h->stream));
+        const int rc = functions_call_one(h, c, n, F.epts.p, F.ell.p);
+        if (rc) return rc;
+        HIP_TRY(h, hipMemcpyAsync(comps + (size_t)c * n, F.ell.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // (`in` and the scratch are reused)
+    }
+    return MCMC_HIP_OK;
+}
+
+// mcmc_hip_step with several functions: per step  [accept of the previous trial +] proposal of the
+// slot -> the DUE functions on their inputs; a call ends with the accept of its last trial.  Which
+// functions are due is the host's knowledge (the shared schedule); nothing waits for the device.
+int step_functions(mcmc_hip_ctx* h, int n_steps)
+{
+    auto& F = h->fnt;
+    const int d = h->d, W = h->W, nf = F.n_fn;
+    int rc = functions_refusals(h);
+    if (rc) return rc;
+    const bool blocked = h->blocked;
+    const int L = block_slots(h, 0);
+    // the fastest block each function reads: it is due at the slots of that block and of slower ones
+    int last_block[mcmc::kFnMaxFunctions] = {};
+    if (blocked) {
+        std::vector<int> block_of(d, 0);
+        int j = 0;
+        for (size_t b = 0; b < h->blk_size.size(); ++b)
+            for (int k = 0; k < h->blk_size[b]; ++k, ++j) block_of[h->i_of_j[j]] = (int)b;
+        for (int c = 0; c < nf; ++c)
+            for (int i : F.inputs[c]) last_block[c] = std::max(last_block[c], block_of[i]);
+    }
+    if (!F.llc_valid) {   // a state that came without its components: every function, on the state
+        std::vector<double> x((size_t)W * d), comps((size_t)nf * W);
+        rc = mcmc_hip_get_state(h, x.data(), nullptr, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        rc = functions_evaluate(h, W, x.data(), comps.data());
+        if (rc) return rc;
+        HIP_TRY(h, F.ll_c.resize((size_t)nf * W));
+        HIP_TRY(h, hipMemcpy(F.ll_c.p, comps.data(), sizeof(double) * nf * W, hipMemcpyHostToDevice));
+        F.llc_valid = true;
+    }
+    HIP_TRY(h, F.points.resize((size_t)d * W));
+    HIP_TRY(h, F.lp_t.resize(W));
+    HIP_TRY(h, F.Ea.resize(W));
+    HIP_TRY(h, F.ll_new.resize((size_t)nf * W));
+    const size_t dd = blocked ? (size_t)mcmc::v_slab_cols(L, d)
+                              : (h->kb ? (size_t)mcmc::v_slab_big(d) : (size_t)mcmc::v_slab(d));
+    const int max_cyc = (int)std::max<size_t>(1, (64u << 20) / (sizeof(double) * dd * (size_t)h->G));
+    mcmc::FnBlockedArgs a{};
+    mcmc::StepArgs& s = a.w.s;
+    s.x = h->x.p; s.logpost = h->logpost.p; s.logprior = h->logprior.p;
+    s.loglike = h->loglike.p; s.weight = h->weight_i.p; s.prior_rej = h->prej.p;
+    s.burn_left = h->burn.p; s.n_accept = h->nacc.p; s.stuck = h->stuck.p;
+    s.accept_total = h->acc_total.p;
+    s.cblock = h->cblock.p; s.W = W; s.group_size = h->gs; s.n_modes = 0;
+    s.norm_mask = h->norm_mask; s.walker0 = h->cfg.walker_offset;
+    s.key0 = (uint32_t)h->cfg.seed; s.key1 = (uint32_t)(h->cfg.seed >> 32);
+    s.uniform_logp = h->uniform_logp; s.temperature = h->cfg.temperature;
+    s.max_tries = h->cfg.max_tries; s.cps = L; s.slab = (int)dd;
+    a.w.d = d; a.w.ld = blocked ? d : (h->kb ? mcmc::v_ld(d) : d);
+    for (int q = 0; q < 4; ++q) a.w.norm_mask4[q] = h->norm_mask4[q];
+    a.w.points = F.points.p; a.w.lp_t = F.lp_t.p; a.w.Ea = F.Ea.p; a.w.ll_t = nullptr; a.w.bad = F.bad.p;
+    a.n_fn = nf; a.inputs = F.dinputs.p; a.ll_c = F.ll_c.p;
+    for (int c = 0, off = 0; c < nf; ++c) {
+        const int dc = (int)F.inputs[c].size();
+        HIP_TRY(h, F.pts[c].resize((size_t)dc * W));
+        a.in_off[c] = off; a.n_in[c] = dc; a.pts[c] = F.pts[c].p;
+        a.ll_new[c] = F.ll_new.p + (size_t)c * W;
+        off += dc;
+    }
+    const unsigned long long Lu = (unsigned long long)L;
+    int left = n_steps;
+    bool pending = false;   // a trial has been proposed and evaluated, not yet accepted / rejected
+    rc = MCMC_HIP_OK;
+    while (left > 0 && rc == MCMC_HIP_OK) {
+        const unsigned long long c0 = h->step / Lu;
+        const unsigned long long room = (c0 + (unsigned long long)max_cyc) * Lu - h->step;
+        const int n = (int)std::min<unsigned long long>((unsigned long long)left, room);
+        const int ncyc = (int)((h->step + (unsigned long long)n - 1) / Lu - c0 + 1);
+        {
+            Timed t(h, 1);
+            if (blocked) {
+                bool any_1d = false;
+                const int brc = blocked_basis(h, 0, c0, ncyc, L, dd, h->V, h->vflag, any_1d, nullptr, true);
+                if (brc) return brc;
+            } else {
+                HIP_TRY(h, h->V.resize((size_t)h->G * ncyc * dd));
+                mcmc::BasisArgs b{};
+                b.T = h->dT.p; b.V = h->V.p;
+                b.group0 = h->cfg.walker_offset / (uint32_t)h->gs;
+                b.cycle0 = (uint32_t)c0;
+                b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
+                b.ncyc = ncyc;
+                if (h->kb) HIP_TRY(h, h->kb->basis(b, h->G, d, h->stream));
+                else HIP_TRY(h, h->k->basis(b, h->G, h->stream));
+            }
+        }
+        s.V = h->V.p; s.ncyc = ncyc;
+        for (int q = 0; q < n; ++q) {
+            const unsigned long long cycle = h->step / Lu;
+            const int slot = (int)(h->step % Lu);
+            unsigned due = (1u << nf) - 1u;
+            a.oned = d == 1;
+            if (blocked) {
+                // (the cycle index is kept modulo 2^32, as the direction kernels keep it)
+                shared_schedule(h, cycle & 0xFFFFFFFFull, L);
+                const int b = F.sched[slot];
+                due = 0;
+                for (int c = 0; c < nf; ++c)
+                    if (last_block[c] >= b) due |= 1u << c;
+                a.oned = h->blk_size[b] == 1;
+            }
+            s.step0 = h->step;
+            a.w.cyc = (int)(cycle - c0);
+            a.w.col = slot;
+            a.due = due;
+            {
+                Timed t(h, 0);
+                HIP_TRY(h, mcmc_hip_launch_fn_blocked_walker(&a, pending ? 1 : 0, 1, h->stream));
+            }
+            h->n_step_launches += 1;
+            // (the launch has settled the previous trial; a callback that fails drops THIS one:
+            // state and step counter stay as of the last completed step)
+            pending = false;
+            for (int c = 0; c < nf && rc == MCMC_HIP_OK; ++c)
+                if ((due >> c) & 1u) rc = functions_call_one(h, c, W, F.pts[c].p, F.ll_new.p + (size_t)c * W);
+            if (rc) break;
+            pending = true;
+            a.due_prev = due;
+            h->step += 1;
+        }
+        left -= n;
+    }
+    if (pending) {
+        Timed t(h, 0);
+        HIP_TRY(h, mcmc_hip_launch_fn_blocked_walker(&a, 1, 0, h->stream));
+    }
+    take_noted_kernel(h);
+    return rc;
+}
+
 // the flag of a function target that returned NaN or +inf inside the support (1 + walker, 0: none)
 int function_target_error(mcmc_hip_ctx* h, int bad)
 {
@@ -314,6 +523,7 @@ int mcmc_hip_set_target_function(mcmc_hip_ctx* h, mcmc_hip_loglike_fn fn, void* 
     h->fnt.fn = fn;
     h->fnt.user = user;
     h->fnt.on = true;
+    h->fnt.n_fn = 0;
     h->K = 0;
     h->bg.on = false;
     h->mean.clear(); h->Linv.clear(); h->cnorm.clear(); h->weight.clear();
@@ -321,6 +531,115 @@ int mcmc_hip_set_target_function(mcmc_hip_ctx* h, mcmc_hip_loglike_fn fn, void* 
     ++h->dir_epoch;
     h->have_state = false;
     return upload_constants(h);
+}
+
+int mcmc_hip_set_target_functions(mcmc_hip_ctx* h, int32_t n, const mcmc_hip_loglike_fn* fns,
+                                  void* const* users, const int32_t* n_inputs, const int32_t* inputs)
+{
+    if (!h) return MCMC_HIP_ERR_ARG;
+    if (!fns || !n_inputs || !inputs) return fail(h, MCMC_HIP_ERR_ARG, "null argument");
+    if (n < 1 || n > mcmc::kFnMaxFunctions)
+        return fail(h, MCMC_HIP_ERR_ARG, "a function target takes 1..%d functions, got %d",
+                    mcmc::kFnMaxFunctions, n);
+    if (h->d > kMaxDimBig)
+        return fail(h, MCMC_HIP_ERR_ARG, "a function target serves d <= %d, got d=%d", kMaxDimBig, h->d);
+    if (h->cfg.flags & MCMC_HIP_FLAG_INCREMENTAL)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target is evaluated from scratch (incremental evaluation, "
+                    "MCMC_HIP_FLAG_INCREMENTAL, is not served)");
+    if (h->cfg.flags & MCMC_HIP_FLAG_OWN_BASIS)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target needs the shared basis (own basis, MCMC_HIP_FLAG_OWN_BASIS / "
+                    "shared_basis: False, is not served)");
+    if (h->cfg.emit_capacity > 0)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target emits no rows on the device (emit_capacity > 0 / emit: chains is "
+                    "not served; use emit: snapshots)");
+    int rc = functions_refusals(h);
+    if (rc) return rc;
+    std::vector<char> fed(h->d, 0);
+    std::vector<int> flat;
+    for (int c = 0, off = 0; c < n; off += n_inputs[c], ++c) {
+        if (!fns[c]) return fail(h, MCMC_HIP_ERR_ARG, "null argument");
+        if (n_inputs[c] < 1 || n_inputs[c] > h->d)
+            return fail(h, MCMC_HIP_ERR_ARG, "function %d takes %d inputs: it must take 1..d = %d of the "
+                        "sampled parameters", c, n_inputs[c], h->d);
+        std::vector<char> mine(h->d, 0);
+        for (int k = 0; k < n_inputs[c]; ++k) {
+            const int i = inputs[off + k];
+            if (i < 0 || i >= h->d || mine[i])
+                return fail(h, MCMC_HIP_ERR_ARG, "input %d of function %d is %d: not a sampled parameter "
+                            "(0..%d), or listed twice", k, c, i, h->d - 1);
+            mine[i] = fed[i] = 1;
+            flat.push_back(i);
+        }
+    }
+    for (int i = 0; i < h->d; ++i)
+        if (!fed[i])
+            return fail(h, MCMC_HIP_ERR_ARG, "sampled parameter %d feeds no function: every sampled "
+                        "parameter must be an input of at least one", i);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    auto& F = h->fnt;
+    HIP_TRY(h, F.bad.resize(1));
+    HIP_TRY(h, hipMemsetAsync(F.bad.p, 0, sizeof(int), h->stream));
+    HIP_TRY(h, F.dinputs.resize(flat.size()));
+    HIP_TRY(h, hipMemcpy(F.dinputs.p, flat.data(), sizeof(int) * flat.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h, F.ll_c.resize((size_t)n * h->W));
+    for (int c = 0, off = 0; c < n; off += n_inputs[c], ++c) {
+        F.fns[c] = fns[c];
+        F.users[c] = users ? users[c] : nullptr;
+        F.inputs[c].assign(inputs + off, inputs + off + n_inputs[c]);
+    }
+    F.n_fn = n;
+    F.fn = nullptr; F.user = nullptr;
+    F.llc_valid = false;
+    F.last_eval_n = 0;
+    F.on = true;
+    h->K = 0;
+    h->bg.on = false;
+    h->mean.clear(); h->Linv.clear(); h->cnorm.clear(); h->weight.clear();
+    h->have_target = true;
+    ++h->dir_epoch;
+    h->have_state = false;
+    return upload_constants(h);
+}
+
+int mcmc_hip_get_component_loglikes(mcmc_hip_ctx* h, double* ll)
+{
+    if (!h) return MCMC_HIP_ERR_ARG;
+    if (!ll) return fail(h, MCMC_HIP_ERR_ARG, "null argument");
+    auto& F = h->fnt;
+    if (!F.on || F.n_fn < 1 || !h->have_state)
+        return fail(h, MCMC_HIP_ERR_STATE, "no component log-likelihoods: set_target_functions and a state first");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (!F.llc_valid) {   // a full state set without them: what the next launch would form
+        std::vector<double> x((size_t)h->W * h->d);
+        int rc = mcmc_hip_get_state(h, x.data(), nullptr, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        rc = functions_evaluate(h, h->W, x.data(), ll);
+        if (rc) return rc;
+        HIP_TRY(h, hipMemcpy(F.ll_c.p, ll, sizeof(double) * F.n_fn * h->W, hipMemcpyHostToDevice));
+        F.llc_valid = true;
+        return MCMC_HIP_OK;
+    }
+    HIP_TRY(h, hipMemcpy(ll, F.ll_c.p, sizeof(double) * F.n_fn * h->W, hipMemcpyDeviceToHost));
+    return MCMC_HIP_OK;
+}
+
+int mcmc_hip_set_component_loglikes(mcmc_hip_ctx* h, const double* ll)
+{
+    if (!h) return MCMC_HIP_ERR_ARG;
+    if (!ll) return fail(h, MCMC_HIP_ERR_ARG, "null argument");
+    auto& F = h->fnt;
+    if (!F.on || F.n_fn < 1 || !h->have_state)
+        return fail(h, MCMC_HIP_ERR_STATE, "set_target_functions and a state must precede set_component_loglikes");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(F.ll_c.p, ll, sizeof(double) * F.n_fn * h->W, hipMemcpyHostToDevice));
+    F.llc_valid = true;
+    return MCMC_HIP_OK;
 }
 
 int mcmc_hip_set_target_binned_gaussian(mcmc_hip_ctx* h, int32_t n_bins, const int32_t* bins,

@@ -425,6 +425,21 @@ struct mcmc_hip_ctx {
         void* user = nullptr;
         DevBuf<double> points, lp_t, Ea, ll_t;   // step scratch: trial [W][d], its log-prior, E_a, the function's values
         DevBuf<int> bad;                         // [1] 1 + global id of the first walker with NaN / +inf inside the support
+        // several functions over parameter blocks (mcmc_hip_set_target_functions; n_fn == 0: the one
+        // function above): function c reads the sampled parameters inputs[c], in that order
+        int n_fn = 0;
+        mcmc_hip_loglike_fn fns[mcmc::kFnMaxFunctions] = {};
+        void* users[mcmc::kFnMaxFunctions] = {};
+        std::vector<int32_t> inputs[mcmc::kFnMaxFunctions];
+        DevBuf<int> dinputs;                     // the inputs, function after function
+        DevBuf<double> pts[mcmc::kFnMaxFunctions];   // step scratch: [W][d_c] the inputs of function c
+        DevBuf<double> ll_new, ll_c;             // [n_fn][W]: what the functions returned; the carried values
+        DevBuf<double> epts, ell;                // evaluate scratch: [n][d_c], [n]
+        bool llc_valid = false;                  // ll_c belongs to the state (else: re-evaluated at the next launch)
+        std::vector<double> last_eval;           // [n_fn][n] of the last mcmc_hip_evaluate (set_state keeps them)
+        int last_eval_n = 0;
+        unsigned long long sched_cycle = ~0ull, sched_epoch = ~0ull;
+        std::vector<short> sched;                // block of every slot of cycle sched_cycle
     } fnt;
 };
 
@@ -537,12 +552,16 @@ int upload_constants(mcmc_hip_ctx* h);
 // capi_targets.hip: the binned Gaussian target and function targets
 int step_binned(mcmc_hip_ctx* h, int n_steps);
 int step_function(mcmc_hip_ctx* h, int n_steps);
+int step_functions(mcmc_hip_ctx* h, int n_steps);
+// several functions: component values [n_fn][n] of the host points x[n][d] (every function called)
+int functions_evaluate(mcmc_hip_ctx* h, int n, const double* x, double* comps);
 int evaluate_binned_points(mcmc_hip_ctx* h, int n, const double* x, double* logprior, double* loglike);
 int function_call(mcmc_hip_ctx* h, int n, const double* points, double* loglike);
 int function_target_error(mcmc_hip_ctx* h, int bad);
 // capi_incremental.hip: incremental evaluation (d <= 128: step_incremental; above: step_huge)
 int blocked_basis(mcmc_hip_ctx* h, int which, unsigned long long c0, int ncyc, int L, size_t slab,
-                  DevBuf<double>& V, DevBuf<int>& flag, bool& any_1d, hipStream_t st = nullptr);
+                  DevBuf<double>& V, DevBuf<int>& flag, bool& any_1d, hipStream_t st = nullptr,
+                  bool shared_schedule = false);
 int step_huge(mcmc_hip_ctx* h, int n_steps);
 int step_incremental(mcmc_hip_ctx* h, int n_steps);
 // the kernel that serves this engine's incremental steps and what it carries (inc_choice.h);

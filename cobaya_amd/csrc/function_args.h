@@ -25,9 +25,32 @@ struct FnWalkerArgs {
                            // was NaN or +inf (0: none)
 };
 
+// ---- several functions over parameter blocks (fn_blocked_walker_kernel; DESIGN.md section 2,
+// "Function targets with parameter blocks"): the step of ONE slot of the blocked cycle.  The slot
+// schedule is the same for every group, so whether function c is called at a slot ("due": it has an
+// input in the slot's block or a faster one) is one bit per launch; a function that is not due
+// keeps its carried value ll_c[c][w].  The full trial goes to w.points as in fn_walker_kernel (the
+// accept half commits it from there); each DUE function's inputs go to its own point-major buffer.
+constexpr int kFnMaxFunctions = 8;
+struct FnBlockedArgs {
+    FnWalkerArgs w;        // w.col = the slot, w.ld = column stride of the directions of a cycle,
+                           // w.points = the FULL trial [W][d]; w.ll_t is not read
+    int oned;              // the slot moves a one-parameter block: RandProposer1D variates (the slot's flag)
+    int n_fn;
+    unsigned due;          // bit c: function c is called for the trial this launch PROPOSES
+    unsigned due_prev;     // ... was called for the trial this launch ACCEPTS or rejects
+    const int* inputs;     // sampler indices of the inputs, function after function
+    int in_off[kFnMaxFunctions], n_in[kFnMaxFunctions];   // function c reads inputs[in_off[c] .. + n_in[c])
+    double* pts[kFnMaxFunctions];            // [W][n_in[c]] the inputs of function c, point-major
+    const double* ll_new[kFnMaxFunctions];   // [W] what function c returned for the trial to accept
+    double* ll_c;          // [n_fn][W] the carried per-function log-likelihoods of the state
+};
+
 }  // namespace mcmc
 
-// the launcher of function_kernels.hip: declared here alone, for the kernels' translation unit
+// the launchers of function_kernels.hip: declared here alone, for the kernels' translation unit
 // and the host side
 extern "C" hipError_t mcmc_hip_launch_fn_walker(const mcmc::FnWalkerArgs* a, int accept, int propose,
                                                 hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_fn_blocked_walker(const mcmc::FnBlockedArgs* a, int accept,
+                                                        int propose, hipStream_t st);

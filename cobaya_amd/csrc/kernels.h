@@ -133,6 +133,9 @@ struct BlockedBasisArgs {
     int ncyc;
     int ld;                 // column stride of V (d <= 32: d)
     int nmax;               // largest block (the d > 32 kernel sizes its LDS by it)
+    uint32_t shuffle_group1;  // 1 + the group whose counter the slot shuffle uses; 0 (the default):
+                              // every group its own index.  A fixed group gives all groups ONE slot
+                              // schedule (function targets with blocks); the Haar bases stay per group
 };
 
 struct BasisArgs {

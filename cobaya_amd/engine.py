@@ -93,6 +93,10 @@ SYMBOLS = [
     ("mcmc_hip_set_target_gaussian", C.c_int, [_H, c_double_p, c_double_p, C.c_int32]),
     ("mcmc_hip_set_target_one", C.c_int, [_H]),
     ("mcmc_hip_set_target_function", C.c_int, [_H, LOGLIKE_FN, C.c_void_p]),
+    ("mcmc_hip_set_target_functions", C.c_int, [_H, C.c_int32, C.POINTER(LOGLIKE_FN),
+                                                C.POINTER(C.c_void_p), c_int32_p, c_int32_p]),
+    ("mcmc_hip_get_component_loglikes", C.c_int, [_H, c_double_p]),
+    ("mcmc_hip_set_component_loglikes", C.c_int, [_H, c_double_p]),
     ("mcmc_hip_checkpoint_set_ring", C.c_int, [_H, C.c_int32, c_double_p, c_double_p, C.c_int32]),
     ("mcmc_hip_checkpoint_set_accepted", C.c_int, [_H, C.c_int64]),
     ("mcmc_hip_checkpoint_begin", C.c_int, [_H, C.c_int32, C.c_int64, C.c_double,
@@ -569,6 +573,15 @@ class Engine:
         runtime, which the process must load first."""
         if not callable(fn):
             raise EngineError(ERR_ARG, f"set_target_function needs a callable, got {fn!r}")
+        stream, make = self._function_callbacks()
+        cb = LOGLIKE_FN(make(fn, pass_out))
+        self._check(self._lib.mcmc_hip_set_target_function(self._h, cb, None))
+        self._fn_callback = (cb, fn, stream)   # alive as long as the engine
+        self.K = 0
+        self.n_functions = 0
+
+    def _function_callbacks(self):
+        """(the engine's stream as PyTorch sees it, make(fn, pass_out) -> the C callback's body)."""
         import torch   # (only function targets need it)
         dev = torch.device("cuda", int(self.cfg.device))
         try:
@@ -581,7 +594,6 @@ class Engine:
                               "before the first Engine is created (before libmcmc_hip.so is loaded), so "
                               "that both use one HIP runtime") from e
         views = {}
-        pass_out = bool(pass_out)
 
         class _View:   # __cuda_array_interface__ of n float64 at a device pointer: no copy
             def __init__(self, ptr, shape):
@@ -597,36 +609,70 @@ class Engine:
                 t = views[key] = torch.as_tensor(_View(ptr, shape), device=dev)
             return t
 
-        def callback(_user, n, d, points, loglike, _stream):
-            try:
-                with torch.cuda.stream(stream):
-                    out_buf = view(loglike, (n,))
-                    pts = view(points, (n, d))
-                    out = fn(pts, out_buf) if pass_out else fn(pts)
-                    if not isinstance(out, torch.Tensor):
-                        raise TypeError("the target function must return a torch.Tensor, got "
-                                        f"{type(out).__name__}")
-                    if tuple(out.shape) != (n,):
-                        raise ValueError(f"the target function must return shape ({n},), got shape "
-                                         f"{tuple(out.shape)}")
-                    if out.dtype != torch.float64:
-                        raise TypeError("the target function must return dtype torch.float64, got "
-                                        f"dtype {out.dtype}")
-                    if out.device != dev:
-                        raise ValueError(f"the target function must return a tensor on device {dev}, "
-                                         f"got device {out.device}")
-                    if out.data_ptr() != loglike or not out.is_contiguous():
-                        out_buf.copy_(out)
-                return 0
-            except BaseException as e:   # (cannot cross ctypes: kept for _check, which re-raises
-                # a KeyboardInterrupt / SystemExit as it is)
-                self._fn_exc = e
-                return 1
+        def make(fn, pass_out):
+            pass_out = bool(pass_out)
 
-        cb = LOGLIKE_FN(callback)
-        self._check(self._lib.mcmc_hip_set_target_function(self._h, cb, None))
-        self._fn_callback = (cb, fn, stream)   # alive as long as the engine
+            def callback(_user, n, d, points, loglike, _stream):
+                try:
+                    with torch.cuda.stream(stream):
+                        out_buf = view(loglike, (n,))
+                        pts = view(points, (n, d))
+                        out = fn(pts, out_buf) if pass_out else fn(pts)
+                        if not isinstance(out, torch.Tensor):
+                            raise TypeError("the target function must return a torch.Tensor, got "
+                                            f"{type(out).__name__}")
+                        if tuple(out.shape) != (n,):
+                            raise ValueError(f"the target function must return shape ({n},), got shape "
+                                             f"{tuple(out.shape)}")
+                        if out.dtype != torch.float64:
+                            raise TypeError("the target function must return dtype torch.float64, got "
+                                            f"dtype {out.dtype}")
+                        if out.device != dev:
+                            raise ValueError(f"the target function must return a tensor on device {dev}, "
+                                             f"got device {out.device}")
+                        if out.data_ptr() != loglike or not out.is_contiguous():
+                            out_buf.copy_(out)
+                    return 0
+                except BaseException as e:   # (cannot cross ctypes: kept for _check, which re-raises
+                    # a KeyboardInterrupt / SystemExit as it is)
+                    self._fn_exc = e
+                    return 1
+            return callback
+
+        return stream, make
+
+    n_functions = 0    # (set_target_functions)
+
+    def set_target_functions(self, fns, inputs, pass_out=False):
+        """Target kind `function` with several functions over parameter blocks
+        (mcmc_hip_set_target_functions): the log-likelihood is the sum of 1..8 batched device
+        functions.  `inputs[c]`: the sampler indices function c reads; `fns[c](points)` receives them
+        as a torch.float64 tensor (n, len(inputs[c])) in that order and returns (n,) float64, under
+        the conventions of `set_target_function`.  The subsets may overlap; every sampled parameter
+        feeds at least one function.  Accepts `set_blocking` (no dragging): at a slot of block b only
+        the functions with an input in a block >= b are called, the others keep their carried value
+        (`get_full_state()["ll_c"]`)."""
+        fns, inputs = list(fns), [[int(i) for i in idx] for idx in inputs]
+        if len(fns) != len(inputs) or not all(callable(f) for f in fns):
+            raise EngineError(ERR_ARG, "set_target_functions needs one list of inputs per callable")
+        stream, make = self._function_callbacks()
+        cbs = [LOGLIKE_FN(make(f, pass_out)) for f in fns]
+        arr = (LOGLIKE_FN * len(cbs))(*cbs)
+        n_in = np.array([len(i) for i in inputs], dtype=np.int32)
+        flat = np.array([i for idx in inputs for i in idx], dtype=np.int32)
+        self._check(self._lib.mcmc_hip_set_target_functions(self._h, len(cbs), arr, None, _ip(n_in), _ip(flat)))
+        self._fn_callback = (cbs, arr, fns, stream)   # alive as long as the engine
         self.K = 0
+        self.n_functions = len(cbs)
+
+    def get_component_loglikes(self):
+        """ll_c[n_functions][n_walkers]: the carried per-function log-likelihoods of the state."""
+        out = np.empty((self.n_functions, self.W))
+        self._check(self._lib.mcmc_hip_get_component_loglikes(self._h, _dp(out)))
+        return out
+
+    def set_component_loglikes(self, ll_c):
+        self._check(self._lib.mcmc_hip_set_component_loglikes(self._h, _dp(_f64(ll_c, (self.n_functions, self.W)))))
 
     def derived_constants(self):
         d, K = self.d, max(self.K or 0, 0)
@@ -716,6 +762,8 @@ class Engine:
                     out["amode"] = am
         if self.emit_thin > 1:   # thinned emission on the device: the per-walker remainders
             out["thin_carry"] = self.get_thin_carry()
+        if self.n_functions:     # several functions: the carried per-function values
+            out["ll_c"] = self.get_component_loglikes()
         return out
 
     def set_full_state(self, st):
@@ -737,6 +785,8 @@ class Engine:
                 self._check(self._lib.mcmc_hip_set_mode_logdensities(self._h, _dp(am)))
         if self.emit_thin > 1 and "thin_carry" in st:
             self.set_thin_carry(st["thin_carry"])
+        if self.n_functions and "ll_c" in st:   # (absent: every function is called at the next launch)
+            self.set_component_loglikes(st["ll_c"])
 
     def carries_modes(self):
         """Mixtures in incremental mode: does the step kernel this configuration selects carry the

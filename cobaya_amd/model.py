@@ -30,6 +30,7 @@ import numpy as np
 
 OVERHEAD_TIME = 0.0003  # conventions.py:141
 MAX_DERIVED_FUNCTIONS = 32  # derived_args.h: kDvMaxNames
+MAX_FUNCTIONS = 8           # function_args.h: kFnMaxFunctions
 
 
 def sort_parameter_blocks(blocks, speeds, footprints, oversample_power=0.0):
@@ -348,7 +349,12 @@ class ProblemSpec:
         likes = info.get("likelihood") or {}
         if not likes:
             raise UnsupportedModel("no likelihood given (use `one` for prior-only sampling)")
-        comps = [cls._parse_likelihood(lname, linfo, sampled, derived, single=len(likes) == 1)
+        # several likelihoods of class device_function, and no other class beside them: each takes
+        # its own inputs ("Function targets with parameter blocks")
+        functions_only = len(likes) > 1 and all(
+            cls._class_key(lname, linfo) == "devicefunction" for lname, linfo in likes.items())
+        comps = [cls._parse_likelihood(lname, linfo, sampled, derived, single=len(likes) == 1,
+                                       functions_only=functions_only)
                  for lname, linfo in likes.items()]
         spec = spec._with_components(comps)
         if spec.derived_functions and spec.derived:
@@ -383,6 +389,21 @@ class ProblemSpec:
         # ONE mixture whose modes are all combinations of the components' modes, with
         # block-diagonal covariances (what the device evaluates); the per-likelihood chi2
         # columns of the output are recomputed on the host (component_loglikes).
+        if all(c["kind"] == "device_function" for c in comps):
+            # several batched device functions over overlapping subsets of the sampled parameters:
+            # the posterior is their product, each evaluated by its own function
+            if len(comps) > MAX_FUNCTIONS:
+                raise UnsupportedModel(f"{len(comps)} device_function likelihoods: mcmc_hip samples "
+                                       f"at most {MAX_FUNCTIONS} of them together")
+            unfed = [p for i, p in enumerate(spec.sampled) if not any(i in c["idx"] for c in comps)]
+            if unfed:
+                raise UnsupportedModel(f"the sampled parameters {unfed} feed no likelihood: every sampled "
+                                       "parameter must be an input of at least one device_function")
+            spec.like_name, spec.like_kind = comps[0]["name"], "device_function"
+            spec.means = spec.covs = spec.weights = None
+            spec.normalized, spec.has_derived = True, False
+            spec.function = None
+            return spec
         claimed = [i for c in comps for i in c["idx"]]
         if sorted(claimed) != list(range(spec.d)):
             raise UnsupportedModel(
@@ -423,8 +444,12 @@ class ProblemSpec:
     # an `*.updated.yaml` -- or `model.info()` -- can be fed back in
     _FRAMEWORK_KEYS = ("delay", "type", "version", "stop_at_error", "python_path", "params")
 
+    @staticmethod
+    def _class_key(lname, linfo):
+        return str((linfo or {}).get("class", lname)).split(".")[-1].lower().replace("_", "")
+
     @classmethod
-    def _parse_likelihood(cls, lname, linfo, sampled, derived, single):
+    def _parse_likelihood(cls, lname, linfo, sampled, derived, single, functions_only=False):
         """One entry of the `likelihood` block -> component dict (see `_component`).
         Parameter routing: an explicit `input_params` / `output_params` list
         (model.py:1155-1167), else `input_params_prefix` / `output_params_prefix`
@@ -445,7 +470,7 @@ class ProblemSpec:
             return cls._pliklite_component(lname, linfo, sampled, derived, speed)
         if lclass == "devicefunction":
             return cls._function_component(lname, linfo, inputs, in_prefix, sampled, derived,
-                                           single, speed)
+                                           single, speed, functions_only)
         if lclass not in ("gaussianmixture", "gaussian"):
             raise UnsupportedModel(f"likelihood '{lname}' is not one of gaussian_mixture, "
                                    "gaussian, one, planck_pliklite")
@@ -469,14 +494,17 @@ class ProblemSpec:
                               single, speed=speed, **kw)
 
     @staticmethod
-    def _function_component(lname, linfo, inputs, in_prefix, sampled, derived, single, speed):
+    def _function_component(lname, linfo, inputs, in_prefix, sampled, derived, single, speed,
+                            functions_only=False):
         """`device_function`: the batched counterpart of an external likelihood function
         (likelihood.py:150-255).  `function` is a callable that maps a float64 device tensor of
         points (n, d) -- the sampled parameters in sampled order -- to (n,) log-likelihoods on the
         same device, or a "package.module:name" string resolved with importlib (YAML inputs,
         resumed runs).  It is called with every trial point, the ones outside the prior support
         included (their values are ignored).  It has no derived parameters and is the only
-        likelihood."""
+        likelihood -- or one of two to eight of this class (`functions_only`), each of which takes
+        its own `input_params` (or `input_params_prefix`): any subset of the sampled parameters, as
+        an (n, d_c) tensor in the order listed; the subsets may overlap."""
         linfo = dict(linfo)
         fn = linfo.pop("function", None)
         if isinstance(fn, str):
@@ -509,11 +537,21 @@ class ProblemSpec:
         if derived:
             raise UnsupportedModel(f"likelihood '{lname}' (device_function) has no derived "
                                    f"parameters, but {list(derived)} were requested")
-        if not single:
+        if not single and not functions_only:
             raise UnsupportedModel(f"likelihood '{lname}' (device_function) must be the only "
                                    "likelihood: it cannot be combined with others")
         if not isinstance(inputs, (list, tuple)):
             inputs = [p for p in sampled if p.startswith(in_prefix)]  # model.py:1169-1172
+        if functions_only:
+            foreign = [p for p in inputs if p not in sampled]
+            if foreign or not inputs or len(set(inputs)) != len(inputs):
+                raise UnsupportedModel(
+                    f"likelihood '{lname}' takes {list(inputs)}: its inputs must be one or more of the "
+                    f"sampled parameters {list(sampled)}, each listed once")
+            return {"name": lname, "kind": "device_function", "idx": [sampled.index(p) for p in inputs],
+                    "means": None, "covs": None, "weights": None, "normalized": True,
+                    "has_derived": False, "speed": float(speed if speed is not None else -1),
+                    "function": fn}
         if list(inputs) != list(sampled):
             raise UnsupportedModel(
                 f"likelihood '{lname}' takes {list(inputs)} but all sampled parameters "
@@ -697,6 +735,9 @@ class ProblemSpec:
             if c["kind"] == "one":
                 continue
             xs = x[:, c["idx"]]
+            if c["kind"] == "device_function":   # the function itself, on the stored rows
+                out[:, ic] = self._call_function(c["function"], xs)
+                continue
             K, n = c["means"].shape
             w = c["weights"]
             w = np.full(K, 1.0 / K) if w is None else w / w.sum()
@@ -709,6 +750,33 @@ class ProblemSpec:
             amax = a.max(axis=1, keepdims=True)
             out[:, ic] = np.log(np.sum(w * np.exp(a - amax), axis=1)) + amax[:, 0]
         return out
+
+    @staticmethod
+    def _call_function(fn, xs):
+        """A batched device function on host points xs[n][d_c] -> loglike[n] (through the device
+        where there is one: the function may hold device tensors)."""
+        import torch
+        dev = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
+        if len(xs) == 0:
+            return np.zeros(0)
+        out = fn(torch.as_tensor(np.ascontiguousarray(xs), dtype=torch.float64, device=dev))
+        return out.detach().cpu().numpy().astype(np.float64)
+
+    @property
+    def functions(self):
+        """[(name, function, inputs as sampler indices)] of several device_function likelihoods
+        (empty for a single one, which takes all sampled parameters in sampled order)."""
+        if self.like_kind != "device_function" or len(self.components) < 2:
+            return []
+        return [(c["name"], c["function"], list(c["idx"])) for c in self.components]
+
+    def function_due(self, blocks):
+        """Which functions a step calls: due[b] = names of the device_function likelihoods with an
+        input in sorted block b or a faster one (`blocks`: lists of names, slow -> fast).  A slot
+        of block b moves block b and every faster one; the others keep their carried value."""
+        block_of = {p: b for b, blk in enumerate(blocks) for p in blk}
+        last = {name: max(block_of[self.sampled[i]] for i in idx) for name, _, idx in self.functions}
+        return [[name for name, _, _ in self.functions if last[name] >= b] for b in range(len(blocks))]
 
     def param_blocking(self, oversample_power=0.0, split_fast_slow=False):
         """Model.get_param_blocking_for_sampler (model.py:1340-1467) with
@@ -723,6 +791,12 @@ class ProblemSpec:
         if len(comps) == 1 or all(not c["idx"] for c in comps[1:]):
             blocks = [list(self.sampled)]
             footprints = [tuple([1] + [0] * (len(comps) - 1))]
+        elif self.functions:
+            # overlapping inputs: parameters grouped by footprint, the set of likelihoods each feeds
+            # (model.py:1371-1389; the reference lists the footprints in the order of a set of them)
+            rows = [tuple(int(i in c["idx"]) for c in comps) for i in range(self.d)]
+            footprints = list({row for row in rows})
+            blocks = [[p for p, row in zip(self.sampled, rows) if row == fp] for fp in footprints]
         else:
             blocks = [[self.sampled[i] for i in c["idx"]] for c in comps if c["idx"]]
             footprints = [tuple(int(j == ic) for j in range(len(comps)))
@@ -811,6 +885,9 @@ class ProblemSpec:
             engine.set_target_one()
         elif self.like_kind == "planck_pliklite":
             engine.set_target_binned_gaussian(self.binned, self.emulator, self.calib_index)
+        elif self.like_kind == "device_function" and self.functions:
+            engine.set_target_functions([f for _, f, _ in self.functions],
+                                        [idx for _, _, idx in self.functions])
         elif self.like_kind == "device_function":
             engine.set_target_function(self.function)
         elif self.like_kind == "gaussian":

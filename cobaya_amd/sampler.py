@@ -641,13 +641,16 @@ class EnsembleMCMC:
     def _check_function(self, spec, d):
         """A `device_function` likelihood is sampled from scratch with Metropolis steps of one
         parameter block, the shared basis, non-periodic priors and emit: snapshots, up to d = 128.
+        Several of them (`spec.functions`) are sampled with parameter blocks and oversampling as
+        well: a slot calls only the functions its block or a faster one feeds.
         Everything else is refused here, by the option to change, before the engine is created."""
         why = None
+        several = bool(spec.functions)
         if d > self.MAX_DIM:
             why = "d = %d > %d parameters are not served" % (d, self.MAX_DIM)
         elif self.drag:
             why = "drag: True is not served"
-        elif len(self.blocks) > 1 or any(int(f) != 1 for f in self.oversampling_factors):
+        elif not several and (len(self.blocks) > 1 or any(int(f) != 1 for f in self.oversampling_factors)):
             why = "parameter blocks / oversample_power / blocking are not served (one block only)"
         elif np.any(spec.periodic):
             why = "periodic parameters are not served (periodic: True of %s)" % (
@@ -658,9 +661,16 @@ class EnsembleMCMC:
             why = "shared_basis: False is not served"
         elif self.evaluation == "incremental":
             why = "evaluation: incremental is not served (use evaluation: full or auto)"
+        if why and several:
+            self._fail("mcmc_hip samples device_function likelihoods from scratch with Metropolis "
+                       "steps: %s", why)
         if why:
             self._fail("mcmc_hip samples a device_function likelihood from scratch with Metropolis "
                        "steps of one parameter block only: %s", why)
+        if several:
+            due = spec.function_due(self.blocks)
+            self.log.info("Functions called per slot of each block (slow -> fast): %s",
+                          "; ".join("%s: %s" % (b, ", ".join(c)) for b, c in zip(self.blocks, due)))
 
     def _init_device_checkpoint(self):
         """`device_checkpoint`: which part of the checkpoint runs on the device -- nothing (False),
@@ -1166,7 +1176,7 @@ class EnsembleMCMC:
         self.engine.set_full_state({k: z[k] for k in ("x", "logpost", "logprior", "loglike",
                                                       "weight", "prior_rej", "burn_left",
                                                       "n_accept", "step", "y", "amode",
-                                                      "thin_carry") if k in z})
+                                                      "thin_carry", "ll_c") if k in z})
         self._shift = z["shift"]
         self.engine.set_moment_shift(self._shift)
         if "acc_n" in z:   # snapshots accumulated on the device since the last read-out

@@ -182,6 +182,26 @@ MCMC_HIP_API int mcmc_hip_set_target_one(mcmc_hip_ctx* h);
 typedef int (*mcmc_hip_loglike_fn)(void* user, int32_t n, int32_t d, const double* points,
                                    double* loglike, void* stream);
 MCMC_HIP_API int mcmc_hip_set_target_function(mcmc_hip_ctx* h, mcmc_hip_loglike_fn fn, void* user);
+/* Target kind `function` with SEVERAL functions over parameter blocks ("Function
+ * targets with parameter blocks"): the log-likelihood is the sum of n = 1..8 batched device functions.
+ * Function c reads n_inputs[c] of the sampled parameters -- their sampler indices are the next
+ * n_inputs[c] entries of `inputs`, function after function; the subsets may overlap, every sampled
+ * parameter must feed at least one -- as a point-major (n_points, n_inputs[c]) tensor in that order:
+ * the `d` argument of its callback is n_inputs[c].  Unlike mcmc_hip_set_target_function this target
+ * accepts parameter blocks and oversampling (mcmc_hip_set_blocking, before or after; no dragging).
+ * The slot schedule of a cycle is then shared by the whole ensemble (the shuffle of global group 0),
+ * and at a slot of sorted block b only the functions with an input in a block >= b are called, once,
+ * with the trials of all walkers; the others keep the value carried per walker.  mcmc_hip_set_state
+ * and mcmc_hip_evaluate call every function.  Otherwise the limits of mcmc_hip_set_target_function. */
+MCMC_HIP_API int mcmc_hip_set_target_functions(mcmc_hip_ctx* h, int32_t n, const mcmc_hip_loglike_fn* fns,
+                                               void* const* users, const int32_t* n_inputs,
+                                               const int32_t* inputs);
+/* The carried per-function log-likelihoods of the state, ll[n * n_walkers] (function c of walker w at
+ * c * n_walkers + w): part of the full state of such a target.  mcmc_hip_set_full_state without a
+ * following mcmc_hip_set_component_loglikes has every function called on the state at the next
+ * mcmc_hip_step.  MCMC_HIP_ERR_STATE unless mcmc_hip_set_target_functions is in force. */
+MCMC_HIP_API int mcmc_hip_get_component_loglikes(mcmc_hip_ctx* h, double* ll);
+MCMC_HIP_API int mcmc_hip_set_component_loglikes(mcmc_hip_ctx* h, const double* ll);
 
 /* PlanckPlikLite.init_params (cobaya/likelihoods/base_classes/planck_pliklite.py:32-141) for the
  * used bins, + the Cl provider of `logp` (planck_pliklite.py:170-178) as a LINEAR emulator:
