@@ -124,9 +124,11 @@ def translation_units(dims, big=True):
             for lo, hi in DUO_DQ_RANGES]
     tus += [("huge_kernels.hip", "huge", []),        # 128 < d <= 256 (run-time d)
             ("function_kernels.hip", "function", []),   # function targets (the user's batched device function)
+            ("stretch_kernels.hip", "stretch", []),     # the stretch move on a function target
             ("host_linalg.cpp", "host_linalg", []),  # the host side: the C ABI, split by job
             ("capi.hip", "capi", []),
             ("capi_targets.hip", "capi_targets", []),
+            ("capi_stretch.hip", "capi_stretch", []),
             ("capi_incremental.hip", "capi_incremental", []),
             ("capi_rows.hip", "capi_rows", []),
             ("capi_checkpoint.hip", "capi_checkpoint", []),

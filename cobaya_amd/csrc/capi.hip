@@ -437,6 +437,7 @@ void mcmc_hip_destroy(mcmc_hip_ctx* h)
     }
     h->fnt.points.release(); h->fnt.lp_t.release(); h->fnt.Ea.release(); h->fnt.ll_t.release();
     h->fnt.bad.release();
+    h->mv.q.release();
     h->fnt.dinputs.release(); h->fnt.ll_new.release(); h->fnt.ll_c.release();
     h->fnt.epts.release(); h->fnt.ell.release();
     for (auto& b : h->fnt.pts) b.release();
@@ -815,6 +816,7 @@ int mcmc_hip_set_state(mcmc_hip_ctx* h, const double* x, int32_t* n_bad)
     HIP_TRY(h, hipStreamSynchronize(s));
     h->step = 0;
     h->have_state = true;
+    h->mv.checked = false; h->mv.broken = false;
     h->y_valid = false; h->amode_valid = false;   // incremental mode: y = L^-1 (x - mu) is formed before the next step
     return MCMC_HIP_OK;
 }
@@ -899,6 +901,7 @@ int mcmc_hip_set_full_state(mcmc_hip_ctx* h, const double* x, const double* logp
     }
     h->step = step;
     h->have_state = true;
+    h->mv.checked = false; h->mv.broken = false;
     h->y_valid = false; h->amode_valid = false;   // incremental mode: mcmc_hip_set_whitened must follow (bit-exact resume)
     return MCMC_HIP_OK;
 }
@@ -906,10 +909,12 @@ int mcmc_hip_set_full_state(mcmc_hip_ctx* h, const double* x, const double* logp
 int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
-    if (!h->have_state || !h->have_cov)
+    const bool stretch = h->mv.kind == MCMC_HIP_MOVE_STRETCH;   // (needs no proposal covariance)
+    if (!h->have_state || (!h->have_cov && !stretch))
         return fail(h, MCMC_HIP_ERR_STATE, "set_state and set_proposal_cov must precede step");
     if (n_steps <= 0) return fail(h, MCMC_HIP_ERR_ARG, "n_steps must be > 0");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (stretch) return step_stretch(h, n_steps);
     if (h->bg.on) return step_binned(h, n_steps);
     if (h->fnt.on) return h->fnt.n_fn > 0 ? step_functions(h, n_steps) : step_function(h, n_steps);
     if (h->incremental && h->huge) return step_huge(h, n_steps);

@@ -20,6 +20,7 @@
 #include "huge_args.h"
 #include "pliklite_args.h"
 #include "function_args.h"
+#include "stretch_args.h"
 #include "checkpoint_args.h"
 #include "marginal_args.h"
 #include "autocorr_args.h"
@@ -441,6 +442,16 @@ struct mcmc_hip_ctx {
         unsigned long long sched_cycle = ~0ull, sched_epoch = ~0ull;
         std::vector<short> sched;                // block of every slot of cycle sched_cycle
     } fnt;
+    // the move of mcmc_hip_step (mcmc_hip_set_move): Metropolis along Haar directions, or the stretch
+    // move of stretch_kernels.hip on the single-function target.  With the default nothing below is
+    // allocated or read
+    struct Stretch {
+        int kind = MCMC_HIP_MOVE_METROPOLIS;
+        double a = 2.0;
+        DevBuf<double> q;          // [W / 2] (d - 1) log z of the pending trials
+        bool checked = false;      // the state in force has no half-group flat in a parameter
+        bool broken = false;       // a callback failed between the half-updates: a state must be set again
+    } mv;
 };
 
 // the end of a device product (mcmc_hip_destroy): what it holds, then the event of its read-out
@@ -558,6 +569,8 @@ int functions_evaluate(mcmc_hip_ctx* h, int n, const double* x, double* comps);
 int evaluate_binned_points(mcmc_hip_ctx* h, int n, const double* x, double* logprior, double* loglike);
 int function_call(mcmc_hip_ctx* h, int n, const double* points, double* loglike);
 int function_target_error(mcmc_hip_ctx* h, int bad);
+// capi_stretch.hip: the stretch move on the single-function target
+int step_stretch(mcmc_hip_ctx* h, int n_steps);
 // capi_incremental.hip: incremental evaluation (d <= 128: step_incremental; above: step_huge)
 int blocked_basis(mcmc_hip_ctx* h, int which, unsigned long long c0, int ncyc, int L, size_t slab,
                   DevBuf<double>& V, DevBuf<int>& flag, bool& any_1d, hipStream_t st = nullptr,

@@ -76,6 +76,8 @@ class IncChoice(C.Structure):
 (INC_NOT_SERVED, INC_STEP, INC_STEP_EMIT, INC_MIX, INC_ANY, INC_DRAG, INC_DUO_MIX,
  INC_DUO_ONE) = range(8)
 
+MOVE_METROPOLIS, MOVE_STRETCH = 0, 1   # mcmc_hip_set_move
+
 # every symbol include/mcmc_hip.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = [
@@ -136,6 +138,7 @@ SYMBOLS = [
                                           c_int32_p, c_int32_p, c_int32_p, c_int64_p,
                                           C.c_uint64]),
     ("mcmc_hip_step", C.c_int, [_H, C.c_int32]),
+    ("mcmc_hip_set_move", C.c_int, [_H, C.c_int32, C.c_double]),
     ("mcmc_hip_sync", C.c_int, [_H]),
     ("mcmc_hip_get_counters", C.c_int, [_H, c_int64_p]),
     ("mcmc_hip_drain_samples", C.c_int, [_H, c_double_p, C.c_int64, c_int64_p]),
@@ -803,6 +806,18 @@ class Engine:
     # -- sampling
     def step(self, n_steps):
         self._check(self._lib.mcmc_hip_step(self._h, int(n_steps)))
+
+    def set_move(self, move, stretch_a=2.0):
+        """The move `step` makes (mcmc_hip_set_move): "metropolis" (the default: the Gaussian
+        proposal along Haar directions) or "stretch", the affine-invariant stretch move with scale
+        `stretch_a` on the target of `set_target_function`.  A stretch step is two half-updates:
+        the function is called twice per step, each time with the n_walkers / 2 trial rows of the
+        active half of every group, in ascending walker order.  No proposal covariance is needed.
+        What the move does not serve is refused by name at the first `step`."""
+        kinds = {None: MOVE_METROPOLIS, "metropolis": MOVE_METROPOLIS, "stretch": MOVE_STRETCH}
+        if move not in kinds:
+            raise EngineError(ERR_ARG, f"move must be 'metropolis' or 'stretch', got {move!r}")
+        self._check(self._lib.mcmc_hip_set_move(self._h, kinds[move], float(stretch_a)))
 
     def sync(self):
         self._check(self._lib.mcmc_hip_sync(self._h))

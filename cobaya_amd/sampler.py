@@ -200,6 +200,16 @@ HIP_DEFAULTS = {
                               # `cobaya_amd.importance.Importance`.  With `marginals` on, "marginals": True
                               # in an alternative keeps a weighted copy of those histograms
                               # (`Importance.marginals(name)`).  None: off.  Needs temperature: 1
+    "move": None,             # how a walker moves.  None / "metropolis": the reference's Gaussian proposal
+                              # along Haar directions, scaled by the learned covariance.  "stretch": the
+                              # affine-invariant stretch move (Goodman & Weare 2010) for ONE
+                              # device_function likelihood: a walker moves along the line through a
+                              # partner drawn from the other half of its own group, so the ensemble
+                              # itself is the proposal -- no covariance, nothing learned, nothing to
+                              # tune; for curved posteriors.  One step is two half-updates: the
+                              # function is called twice, with half of the walkers each.  Needs
+                              # group_size >= 4 d and `ref` pdfs (not fixed points)
+    "stretch_a": 2.0,         # move: stretch -- the scale a > 1 of the stretch factor z in [1/a, a]
     "shared_basis": True,     # True: the walkers of a group share one Haar basis per cycle;
                               # False: every walker draws its own (proposal.py:59-69 to the
                               # letter: the reference-faithful control, much slower)
@@ -275,6 +285,8 @@ class EnsembleMCMC:
     file_base_name = "mcmc_hip"
     sampler_type = "mcmc"
     supports_periodic_params = True
+    move, stretch_a = None, 2.0     # (the options' default)
+    stretch = False     # move: stretch is in force (`_check_move`)
     fallback_covmat_scale = 4.0  # sampler.py:474
     _LoggedError = LoggedError   # the hosted class raises cobaya.log.LoggedError instead
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
@@ -458,6 +470,7 @@ class EnsembleMCMC:
             # (function_kernels.hip: propose -> function -> accept)
             can_inc = False
             self._check_function(spec, d)
+        self._check_move(spec, d)
         if not self.shared_basis and (len(self.blocks) > 1 or self.oversampling_factors[0] != 1):
             self._fail("shared_basis: False serves a single parameter block without "
                        "oversampling or dragging")
@@ -527,6 +540,8 @@ class EnsembleMCMC:
                                  incremental=self.incremental,
                                  basis_group_size=int(self.basis_group_size))
             spec.configure(self.engine)
+            if self.stretch:
+                self.engine.set_move("stretch", self.stretch_a)
             self._size_drain_ring(d, W)
             if len(self.blocks) > 1 or self.oversampling_factors[0] != 1:
                 self.engine.set_blocking(
@@ -637,6 +652,55 @@ class EnsembleMCMC:
         if why:
             self._fail("mcmc_hip samples d = %d > %d parameters with incremental evaluation of one "
                        "parameter block only: %s", d, self.MAX_DIM, why)
+
+    def _check_move(self, spec, d):
+        """`move: stretch` (stretch_kernels.hip) serves ONE device_function likelihood, all parameters
+        in one block, non-periodic priors, emit: snapshots, evaluation from scratch, group_size >= 4 d
+        and an initial ensemble that spans every parameter.  Everything else is refused here, by the
+        option to change, before the engine is created."""
+        if self.move not in (None, "metropolis", "stretch"):
+            self._fail("move must be None, 'metropolis' or 'stretch', got %r", self.move)
+        self.stretch = self.move == "stretch"
+        if not self.stretch:
+            return
+        try:
+            self.stretch_a = float(self.stretch_a)
+        except (TypeError, ValueError):
+            self._fail("stretch_a must be a number > 1, got %r", self.stretch_a)
+        why = None
+        if not (np.isfinite(self.stretch_a) and self.stretch_a > 1):
+            why = "stretch_a must be finite and > 1, got %r" % (self.stretch_a,)
+        elif spec.like_kind != "device_function":
+            why = ("likelihood %r is not served: the move is for one device_function likelihood (analytic "
+                   "targets have the learned Gaussian proposal)" % (spec.like_kind,))
+        elif spec.functions:
+            why = "several device_function likelihoods are not served (one function only)"
+        elif self.drag:
+            why = "drag: True is not served"
+        elif len(self.blocks) > 1 or any(int(f) != 1 for f in self.oversampling_factors):
+            why = "parameter blocks / oversample_power / blocking are not served (all parameters move at once)"
+        elif np.any(spec.periodic):
+            why = "periodic parameters are not served (periodic: True of %s)" % (
+                [p for p, per in zip(spec.sampled, spec.periodic) if per],)
+        elif self.emit != "snapshots":
+            why = "emit: %s is not served (use emit: snapshots)" % self.emit
+        elif self.evaluation == "incremental":
+            why = "evaluation: incremental is not served (use evaluation: full or auto)"
+        elif int(self.group_size) < 4 * d:
+            why = ("group_size: %d < 4 d = %d: a half-group of %d walkers spans too little of %d dimensions; "
+                   "use a larger group_size (256 serves d <= 64)" % (
+                       int(self.group_size), 4 * d, int(self.group_size) // 2, d))
+        else:
+            fixed = [p for p, r in zip(spec.sampled, spec.refs) if r.kind == "point"]
+            if fixed:
+                why = ("`ref` of %s is a fixed point: every walker would start with the same value there, and "
+                       "the move can never leave that hyperplane; give `ref` as a pdf (e.g. {dist: norm, "
+                       "loc: ..., scale: ...}) or leave it out (the prior is used)" % (fixed,))
+        if why:
+            self._fail("move: stretch: %s", why)
+        if self.learn_proposal:
+            self.log.info("move: stretch -- the ensemble is the proposal: no proposal covariance is learned.")
+        self.learn_proposal = False
 
     def _check_function(self, spec, d):
         """A `device_function` likelihood is sampled from scratch with Metropolis steps of one
@@ -1129,6 +1193,8 @@ class EnsembleMCMC:
             if self.emit == "chains" and self.row_thin > 1 and not self._device_thin:
                 st["thin_carry"] = self._thin_carry.astype(np.int32)   # (host-thinned rows)
             st["geometry"] = np.array([int(self.group_size), int(self.basis_group_size)], dtype=np.int64)
+            if self.stretch:   # (absent: metropolis -- the file of the default move keeps its key set)
+                st["move"] = np.array([1.0, float(self.stretch_a)])
             acc_n, acc_gs, acc_S = self.engine.read_moments(reset=False)
             st.update(acc_n=np.int64(acc_n), acc_gs=acc_gs, acc_S=acc_S)
             ivs = self._intervals
@@ -1170,6 +1236,13 @@ class EnsembleMCMC:
                        "and now has %d / %d (the walkers' variate streams and the R-1 groups "
                        "depend on them).", int(z["geometry"][0]), int(z["geometry"][1]),
                        int(self.group_size), int(self.basis_group_size))
+        was = z["move"] if "move" in z else np.zeros(2)   # (absent: metropolis)
+        now = np.array([1.0 if self.stretch else 0.0, float(self.stretch_a) if self.stretch else 0.0])
+        if not np.array_equal(was, now):
+            def name(m):
+                return "stretch (stretch_a: %g)" % m[1] if m[0] else "metropolis"
+            self._fail("cannot resume -- the run was written with move: %s and now has move: %s (the "
+                       "walkers' trials depend on it).", name(was), name(now))
         if "thin_carry" in z and not self._device_thin:
             self._thin_carry = z["thin_carry"].astype(np.int64)
         self.engine.set_proposal_cov(z["proposal_cov"])

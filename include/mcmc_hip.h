@@ -288,6 +288,28 @@ MCMC_HIP_API int mcmc_hip_set_full_state(mcmc_hip_ctx* h, const double* x, const
 /* n_steps iterations of MCMC.get_new_sample_metropolis (mcmc.py:545-562) for every walker,
  * asynchronously on the engine's stream; generates the Haar bases the steps need. */
 MCMC_HIP_API int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps);
+/* The move mcmc_hip_step makes.  MCMC_HIP_MOVE_METROPOLIS (the default): the Gaussian proposal along
+ * Haar directions of everything above; `a` is ignored.  MCMC_HIP_MOVE_STRETCH: the affine-invariant
+ * stretch move (Goodman & Weare 2010; DESIGN.md section 2, "Stretch move"; stretch_kernels.hip) with
+ * scale a (finite, > 1; 2 is the usual choice) on the target of mcmc_hip_set_target_function.  A
+ * group of group_size walkers is two halves; one step is two half-updates, in each of which the
+ * walkers of one half move to t = p + z (x - p), p the current state of a partner drawn from the
+ * OTHER half of the same group, z in [1 / a, a] with density ~ 1 / sqrt(z), accepted with probability
+ * min(1, z^(d - 1) (post(t) / post(x))^(1 / temperature)).  The function is called once per half-update
+ * with the n_walkers / 2 trial rows of the active half, in ascending walker order.  mcmc_hip_step(n)
+ * is 2 n half-updates and ends with the state complete; step counter, weights, max_tries, burn-in and
+ * the accept counters mean what they mean for Metropolis steps (one trial per walker and step).
+ * No proposal covariance is needed (mcmc_hip_set_proposal_cov is accepted and unused), no basis is
+ * formed.  If the callback fails (MCMC_HIP_ERR_CALLBACK) the step counter is that of the last
+ * completed step, but half 0 of the interrupted step may already be committed: mcmc_hip_step then
+ * answers MCMC_HIP_ERR_STATE until a state is set again (mcmc_hip_set_state / _set_full_state).
+ * Refused by mcmc_hip_step with MCMC_HIP_ERR_ARG, each by name: any target but one function (analytic
+ * targets, mcmc_hip_set_target_functions), parameter blocks / oversampling / dragging, periodic
+ * parameters, emit_capacity > 0, MCMC_HIP_FLAG_INCREMENTAL, group_size < 4 d, and a state in which some
+ * parameter has one value in every walker of a half-group (the move never leaves that hyperplane).
+ * mcmc_hip_set_move itself refuses an unknown kind and an `a` that is not finite or <= 1. */
+enum { MCMC_HIP_MOVE_METROPOLIS = 0, MCMC_HIP_MOVE_STRETCH = 1 };
+MCMC_HIP_API int mcmc_hip_set_move(mcmc_hip_ctx* h, int32_t kind, double a);
 /* wait for queued work; returns MCMC_HIP_ERR_STUCK if a walker tripped max_tries, and
  * MCMC_HIP_ERR_TARGET if a function target returned NaN or +inf inside the prior support */
 MCMC_HIP_API int mcmc_hip_sync(mcmc_hip_ctx* h);

@@ -62,6 +62,8 @@ else:
         evidence: bool | dict | None = HIP_DEFAULTS["evidence"]
         derived_stats: bool | dict | None = HIP_DEFAULTS["derived_stats"]
         importance: dict | None = HIP_DEFAULTS["importance"]
+        move: str | None = HIP_DEFAULTS["move"]
+        stretch_a: float = HIP_DEFAULTS["stretch_a"]
 
         def _export_collection(self, coll):
             """Our table -> `cobaya.collection.SampleCollection` (same columns,
