@@ -44,6 +44,13 @@
 // parent's spread was 0.59 %); 3.2 % fewer vector instructions per launch.  With the certain path laid over two
 // taken branches the same instructions gained 0.4 %.  step_duo_mix_kernel keeps the exact staging: at K = 2 the
 // lazy form measured 1.881 -> 1.850 ms per 1 200 steps, inside three times the parent's spread (1.2 %).
+// The commit of the one-mode kernel runs under the accept mask (round 20): an accepting lane takes the step's trial as its
+// x (15 v_mov_b64 at d = 30, not 15 FMAs with a selected r) and moves y on with r, a rejecting lane is not touched; the
+// test of the limit of tries leaves the step of a wave whose chains cannot pass it within the chunk.  v_mov_b64 issues in
+// one pass at the rate of v_add_f64 (4.6 clocks at two waves per SIMD, v_fma_f64 5.6; tools/probes/valu_op_cost.hip).  Measured
+// (profiles/r20_masked_commit.txt, same box, parent / new alternated four times): step kernel 0.7416 -> 0.7033 ms (-5.2 %;
+// the masked commit alone -1.8 %, the stuck test a further -3.5 %), bench.py 9.845e10 -> 1.0337e11 (+5.0 %; the parent's
+// spread was 0.73 %); 6.9 fewer vector instructions per wave-step.
 //
 // Served: Metropolis steps, no periodic parameter, no emitted rows, no block of one parameter, whole
 // workgroups of 128 walkers inside one basis group -- for ensembles that fill the chip with it
@@ -710,14 +717,18 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
     // eight steps the octet has inside the chunk -- a chunk is a multiple of four columns and a launch starts
     // anywhere, so an octet may begin in one chunk and end in the next.  The common path of a step is straight-line
     // code whose one taken branch is the back-edge (tools/check_step_path.py): the octet test and the 64-bit step
-    // index stand in front of the octet, the exact support test, the exact accept, the burn-in bookkeeping and the
-    // report of a stuck chain behind the loop.
+    // index stand in front of the octet, the exact support test, the exact accept, the burn-in bookkeeping, the test
+    // of the limit of tries and the report of a stuck chain behind the loop.  The commit's block, under the accept
+    // mask, lies in front of the latch: its guard (s_cbranch_execz) is taken by a wave without an accepting lane only.
     for (int base = 0, k = 0; base < ncols; base += C, ++k) {
         const double2* __restrict__ cur = smem2 + (k & 1) * CHUNK;
         stage(k + 1);
         const int cols = __builtin_amdgcn_readfirstlane(ncols - base < C ? ncols - base : C);
         unsigned coff = lds_offset(cur + (SPLIT ? h : 2 * h));
         unsigned uoff = lds_offset(sUU + (k & 1) * C);   // (the same address in every lane: a broadcast read)
+        // wt - prej grows by at most one per step: where no chain of the wave can pass lim1 within the chunk's columns,
+        // its steps do not look (the burning wave keeps its bookkeeping, and its higher limit, at every step)
+        bool watch = burning || lanes(wt - prej > lim1 - cols) != 0ull;   // wave-uniform
 #pragma unroll 1
         for (int sl0 = 0; sl0 < cols;) {
             const unsigned long long S0 = s.step0 + (unsigned long long)(base + sl0);
@@ -754,6 +765,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
                 // the step's pairs stay in registers from the trial to the commit (requesting the next
                 // step's behind the commit, over the bookkeeping, was measured slower: 1.24 against 1.02 ms)
                 pair_t pk[NE];
+                double tx[NE];   // the trial coordinates: the support test reads them, an accepting lane commits them
                 const lds_pairs col = (lds_pairs)(unsigned long long)coff;
 #pragma unroll
                 for (int e = 0; e < NE; ++e) pk[e] = col[duo1_off<SPLIT>(e)];
@@ -776,7 +788,8 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
 #pragma unroll
                         for (int q = 0; q < e1 - e0; ++q) {
                             const int e = q == 0 ? e1 - 1 : e0 + q - 1;
-                            const unsigned hw = (unsigned)__double2hiint(fma(r, pk[e].x, x[e]));
+                            tx[e] = fma(r, pk[e].x, x[e]);
+                            const unsigned hw = (unsigned)__double2hiint(tx[e]);
                             hmx = hmx > hw ? hmx : hw;
                         }
 #pragma unroll
@@ -814,10 +827,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
                     if (__builtin_expect((lanes(pmx == bhi_word) | lanes(pmx == 0x80000000u)) != 0ull, 0)) {   // (rare) in doubt
                         unsigned long long inb = ~0ull;
 #pragma unroll
-                        for (int e = 0; e < NE; ++e) {
-                            const double t = fma(r, pk[e].x, x[e]);
-                            inb &= lanes(t <= bhi) & lanes(t >= blo);
-                        }
+                        for (int e = 0; e < NE; ++e) inb &= lanes(tx[e] <= bhi) & lanes(tx[e] >= blo);
                         inside_m = pair_all_mask(inb);
                     }
                 }
@@ -835,30 +845,38 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
                     inside_m & (up_m | accept_lanes(Ea, delta, a.accept_slack, s.key0, s.key1, gid,
                                                     S0 + (unsigned long long)so_here, slog));   // (the index: formed where it is used)
                 const bool accept = __builtin_amdgcn_inverse_ballot_w64(acc_m);
-                llik = accept ? ll : llik;
-                {
-                    const bool inside = __builtin_amdgcn_inverse_ballot_w64(inside_m);
-                    prej = accept ? 0 : (prej + (inside ? 0 : 1));
-                    wt = accept ? 1 : wt + 1;
-                    nacc += accept ? 1 : 0;
-                }
-                // (the limit of tries of a wave past its burn-in is a scalar; the burning wave's bookkeeping, with its
-                // own compare, lies behind the loop.  `burning` goes from true to false once per run)
-                unsigned long long over_m = lanes(wt - prej > lim1);
-                if (__builtin_expect(burning, 0)) {   // wave-uniform (see step_inc_kernel)
-                    const int lim = burn > 0 ? lim10 : lim1;
-                    burn -= (accept & (burn > 0)) ? 1 : 0;
-                    burning = lanes(burn > 0) != 0ull;
-                    over_m = lanes(wt - prej > lim);
-                }
-                stuck_m |= over_m;
-                const double ra = accept ? r : 0.0;
+                // The commit runs on the accepting lanes alone (round 20; step_core_inc -> commit assigns x = t, y = yt
+                // on an accept and touches nothing on a reject): x takes the trial -- on such a lane fma(r, v, x) IS the
+                // new coordinate, nothing is formed again --, y moves on with r itself, the carried values and the
+                // bookkeeping are written under the same mask.  A wave of 32 walkers has an accepting lane at nearly
+                // every step: the block lies on the common path and falls through into the loop's latch.
+                wt += 1;
+                prej += __builtin_amdgcn_inverse_ballot_w64(inside_m) ? 0 : 1;
+                if (accept) {
 #pragma unroll
-                for (int e = 0; e < NE; ++e) {
-                    x[e] = fma(ra, pk[e].x, x[e]);
-                    y[e] = fma(ra, pk[e].y, y[e]);
+                    for (int e = 0; e < NE; ++e) {
+                        x[e] = tx[e];
+                        y[e] = fma(r, pk[e].y, y[e]);
+                    }
+                    llik = ll;
+                    lpost = lt;
+                    wt = 1;
+                    prej = 0;
+                    nacc += 1;
                 }
-                lpost = accept ? lt : lpost;
+                // (the test of the limit of tries and the burning wave's bookkeeping lie behind the loop: a wave past its
+                // burn-in whose chains cannot pass the limit inside this chunk -- `watch`, at the head of the chunk -- skips both)
+                if (__builtin_expect(watch, 0)) {   // wave-uniform
+                    unsigned long long over_m = lanes(wt - prej > lim1);
+                    if (burning) {   // wave-uniform (see step_inc_kernel); goes from true to false once per run
+                        // (wt and prej are the committed ones, the limit is that of the burn-in left BEFORE this step)
+                        const int lim = burn > 0 ? lim10 : lim1;
+                        burn -= (accept & (burn > 0)) ? 1 : 0;
+                        burning = lanes(burn > 0) != 0ull;
+                        over_m = lanes(wt - prej > lim);
+                    }
+                    stuck_m |= over_m;
+                }
             }
             sl0 += n_oct;
         }

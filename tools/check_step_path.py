@@ -9,6 +9,11 @@ of dq = 1 .. 8 to assembly with the build's flags and reports, per instantiation
     s_branch   unconditional branches
     taken      conditional branches that are not the back-edge and target a block laid out at or in front of it
                (a branch to a block BEHIND the back-edge leaves the common path: a rare case, which jumps back)
+    guards     s_cbranch_execz over ONE straight-line block to the label right behind it (round 20: the commit runs on
+               the accepting lanes alone, exec narrowed around it).  Such a branch is taken only by a wave NONE of whose
+               lanes enters the block -- of 32 walkers at an acceptance of 0.3 one wave-step in 10^5 --: the common
+               step falls through it, it is reported apart and is not `taken`.  A guard is no licence: the instructions
+               of its block count as the common path's (tests/test_commit_path_compile.py says what the block may hold)
     python tools/check_step_path.py        exit code 1 if the headline instantiation <8, 15, true, true> has any of them,
                                            or its step loop has no run of 16 reads with a back-edge behind it"""
 import os
@@ -26,7 +31,7 @@ BRANCH = re.compile(r"^(s_branch|s_cbranch_\w+)\s+(\.LBB\d+_\d+)")
 def step_path(kernel_text, reads):
     """The instructions between the first run of exactly `reads` ds_read_b128 inside a loop of depth >= 2 and the first
     backward branch behind it whose target lies at or in front of the run (the back-edge), as
-    {run_at, back_edge, instructions, s_load, s_branch, taken}; None if there is no such run or no such branch."""
+    {run_at, back_edge, instructions, s_load, s_branch, taken, guards}; None if there is no such run or no such branch."""
     lines = [(i, ln.strip()) for i, ln in enumerate(kernel_text.split("\n"))]
     at = {}   # label -> line
     for i, text in lines:
@@ -55,7 +60,9 @@ def step_path(kernel_text, reads):
     if found is None:
         return None
     run_start, behind = found
-    out = {"run_at": run_start, "back_edge": None, "instructions": 0, "s_load": [], "s_branch": [], "taken": []}
+    out = {"run_at": run_start, "back_edge": None, "instructions": 0, "s_load": [], "s_branch": [], "taken": [],
+           "guards": []}
+    labels = sorted(at.values())
     path = []
     for i, text in lines:
         if i < behind or not text or text.startswith(";") or LABEL.match(text):
@@ -75,19 +82,43 @@ def step_path(kernel_text, reads):
         elif b and b.group(1) == "s_branch":
             out["s_branch"].append(text)
         elif b and i != out["back_edge"] and at.get(b.group(2), -1) <= out["back_edge"]:
-            out["taken"].append(text)
+            target = at.get(b.group(2), -1)
+            # (a guard: the target is the first label behind the branch and no branch stands in the block it skips)
+            if (b.group(1) == "s_cbranch_execz" and target > i and not any(i < ln < target for ln in labels)
+                    and not any(BRANCH.match(t) for j, t in path if i < j < target)):
+                out["guards"].append(text)
+            else:
+                out["taken"].append(text)
     return out
+
+
+KERNEL = re.compile(r"^(_ZN4mcmc\S*step_inc_duo_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E\S*):\s.*?^\s*s_endpgm", re.S | re.M)
 
 
 def report(asm_text):
     """[{dq, ne, split, unit_t, path}] for every step_inc_duo_kernel in the text (path: step_path for NE + 1 reads)"""
     out = []
-    for m in re.finditer(r"^(_ZN4mcmc\S*step_inc_duo_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E\S*):\s.*?^\s*s_endpgm",
-                         asm_text, re.S | re.M):
+    for m in KERNEL.finditer(asm_text):
         ne = int(m.group(3))
         out.append({"dq": int(m.group(2)), "ne": ne, "split": m.group(4) == "1", "unit_t": m.group(5) == "1",
                     "path": step_path(m.group(0), ne + 1)})
     return out
+
+
+def step_lines(asm_text, dq, ne, unit_t):
+    """(path, [(line, instruction)] from the first instruction behind the run of reads to the back-edge, labels as
+    `.LBBn_m:`) of the instantiation <dq, ne, true, unit_t>; (None, []) where step_path finds none"""
+    for m in KERNEL.finditer(asm_text):
+        if (int(m.group(2)), int(m.group(3)), m.group(4), m.group(5)) != (dq, ne, "1", "1" if unit_t else "0"):
+            continue
+        p = step_path(m.group(0), ne + 1)
+        if p is None:
+            break
+        rows = [(i, ln.strip()) for i, ln in enumerate(m.group(0).split("\n"))]
+        first = next(i for i, t in rows if i > p["run_at"] and t and not t.startswith(("ds_read_b128", ";")))
+        return p, [(i, t.split(";")[0].strip()) for i, t in rows
+                   if first <= i <= p["back_edge"] and t and not t.startswith(";")]
+    return None, []
 
 
 def is_headline(r):
@@ -107,6 +138,6 @@ if __name__ == "__main__":
         print({k: v for k, v in r.items() if k != "path"},
               "no run of reads with a back-edge behind it" if p is None else
               f"{p['instructions']} instructions to the back-edge; s_load {p['s_load']}, s_branch {p['s_branch']}, "
-              f"taken {p['taken']}")
+              f"taken {p['taken']}, guards {p['guards']}")
     head = [r for r in rows if is_headline(r)]
     sys.exit(0 if head and all(straight(r) for r in head) else 1)

@@ -1,13 +1,15 @@
 // Probe: issue cost of single VALU instructions on gfx950, in SIMD clocks per wave64 instruction,
-// with 4 (and 1) waves per SIMD.  Every op runs as 8 independent chains inside an unrolled loop of
+// with 1, 2 and 4 waves per SIMD.  Every op runs as 8 independent chains inside an unrolled loop of
 // inline asm, so that neither dependences nor the compiler get in the way.
+// The rows "@30%" run with 20 of the 64 lanes in exec (ten lane pairs: the accept mask of a two-lane step kernel at
+// an acceptance of 0.3), narrowed once per 32 instructions by two scalar moves.
 //   hipcc --offload-arch=gfx950 -O2 -o valu_op_cost valu_op_cost.hip && ./valu_op_cost
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
 #define REP8(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
 
-template <int OP>
+template <int OP, bool MASKED = false>
 __global__ void __launch_bounds__(256) k(double* out, int iters)
 {
     double a[8];
@@ -19,7 +21,9 @@ __global__ void __launch_bounds__(256) k(double* out, int iters)
     const double c = 1.0000001, e = 1e-12;
     const unsigned m = 0xD2511F53u;
     if (OP == 12) asm volatile("v_cmp_lt_u32 vcc, %0, %1" : : "v"(u[0]), "v"(m) : "vcc");
+    const unsigned long long some = 0x0C30C30C30C30C30ull;   // 20 lanes
     for (int it = 0; it < iters; ++it) {
+        if (MASKED) asm volatile("s_mov_b64 exec, %0" : : "s"(some));
 #pragma unroll
         for (int rep = 0; rep < 4; ++rep) {
 #define FMA(i) asm volatile("v_fma_f64 %0, %0, %1, %2" : "+v"(a[i]) : "v"(c), "v"(e));
@@ -47,6 +51,9 @@ __global__ void __launch_bounds__(256) k(double* out, int iters)
 #define MULF64(i) asm volatile("v_mul_f64 %0, %0, %1" : "+v"(a[i]) : "v"(c));
 #define LSHL64(i) asm volatile("v_lshlrev_b64 %0, 1, %0" : "+v"(a[i]));
 #define ADD3(i) asm volatile("v_add3_u32 %0, %0, %1, %1" : "+v"(u[i]) : "v"(m));
+#define MOV64(i) asm volatile("v_mov_b64 %0, %1" : "+v"(a[i]) : "v"(c));
+#define FMAC(i) asm volatile("v_fmac_f64 %0, %1, %2" : "+v"(a[i]) : "v"(c), "v"(e));
+#define MOV32(i) asm volatile("v_mov_b32 %0, %1" : "+v"(u[i]) : "v"(m));
             if (OP == 0) { REP8(FMA) }
             if (OP == 1) { REP8(ADD) }
             if (OP == 2) { REP8(MULLO) }
@@ -70,25 +77,29 @@ __global__ void __launch_bounds__(256) k(double* out, int iters)
             if (OP == 20) { REP8(MULF64) }
             if (OP == 21) { REP8(LSHL64) }
             if (OP == 22) { REP8(ADD3) }
+            if (OP == 23) { REP8(MOV64) }
+            if (OP == 24) { REP8(FMAC) }
+            if (OP == 25) { REP8(MOV32) }
         }
+        if (MASKED) asm volatile("s_mov_b64 exec, -1");   // (whole waves: 256 threads per block)
     }
     double s = 0;
     for (int i = 0; i < 8; ++i) s += a[i] + (double)u[i];
     if (s == 12345.678) out[0] = s;
 }
 
-template <int OP>
+template <int OP, bool MASKED = false>
 void run(const char* name, double* d)
 {
     const int iters = 20000;
-    for (int blocks : {256, 1024}) {   // 1 and 4 waves per SIMD
+    for (int blocks : {256, 512, 1024}) {   // 1, 2 and 4 waves per SIMD
         hipEvent_t e0, e1;
         hipEventCreate(&e0);
         hipEventCreate(&e1);
-        hipLaunchKernelGGL(k<OP>, dim3(blocks), dim3(256), 0, 0, d, 10);
+        hipLaunchKernelGGL((k<OP, MASKED>), dim3(blocks), dim3(256), 0, 0, d, 10);
         hipDeviceSynchronize();
         hipEventRecord(e0);
-        hipLaunchKernelGGL(k<OP>, dim3(blocks), dim3(256), 0, 0, d, iters);
+        hipLaunchKernelGGL((k<OP, MASKED>), dim3(blocks), dim3(256), 0, 0, d, iters);
         hipEventRecord(e1);
         hipEventSynchronize(e1);
         float ms = 0;
@@ -126,5 +137,11 @@ int main()
     run<16>("v_mul_f32", d);
     run<17>("v_fma_f32", d);
     run<18>("v_log_f32", d);
+    run<25>("v_mov_b32", d);
+    run<23>("v_mov_b64", d);
+    run<23, true>("v_mov_b64 @30%", d);
+    run<24>("v_fmac_f64", d);
+    run<24, true>("v_fmac_f64 @30%", d);
+    run<0, true>("v_fma_f64 @30%", d);
     return 0;
 }
