@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(256) step_inc_any_kernel(const IncStepArgs a, 
     // would be merged with it into a flat load)
     typedef const double __attribute__((address_space(3))) * lds_cdoubles;
     const lds_cdoubles pLc = (lds_cdoubles)(unsigned long long)(unsigned)(unsigned long long)sLc;
-    auto stage = [&](int k) {
+    auto stage = [&](int k) {   // (written out in every kernel: incremental_common.h, "around the step loop")
         const int first = k * C;
         if (first >= ncols) return;
         const int cols = ncols - first < C ? ncols - first : C;
@@ -202,9 +202,7 @@ __global__ void __launch_bounds__(256) step_inc_any_kernel(const IncStepArgs a, 
     int tacc = thinning ? s.thin_acc[w] : 0;
     const double inv_thin = thinning ? 1.0 / (double)s.thin : 1.0;
     const uint32_t gid = s.walker0 + (uint32_t)w;
-    const double mt10 = s.max_tries * 10.0;
-    const int lim1 = s.max_tries < 2.0e9 ? (int)floor(s.max_tries) : 0x7fffffff;
-    const int lim10 = mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff;
+    const TryLimits tl = try_limits(s.max_tries);
     const short_log_tab slog = short_log_load(short_log_lds);
     __shared__ double exp64_lds[64];   // 2^(j / 64): the log-sum-exp's table-driven exponential
     const exp_tab etab = exp_tab_load(exp64_lds);
@@ -353,16 +351,10 @@ __global__ void __launch_bounds__(256) step_inc_any_kernel(const IncStepArgs a, 
                     bool em = __builtin_amdgcn_inverse_ballot_w64(em_m);
                     int ew = wt;   // the weight the row is written with
                     if (thinning) {
-                        const int tot = tacc + wt;
-                        int q = (int)((double)tot * inv_thin);
-                        int rem = tot - q * s.thin;
-                        q += rem >= s.thin ? 1 : 0;
-                        rem -= rem >= s.thin ? s.thin : 0;
-                        q -= rem < 0 ? 1 : 0;
-                        rem += rem < 0 ? s.thin : 0;
-                        tacc = em ? rem : tacc;
-                        ew = q;
-                        em = em & (q > 0);
+                        const Thinned th = thinned(tacc + wt, s.thin, inv_thin);
+                        tacc = em ? th.rem : tacc;
+                        ew = th.q;
+                        em = em & (th.q > 0);
                     }
                     if (em & (nrow < s.row_cap)) {
                         double* __restrict__ row = s.rows + ((size_t)w * s.row_cap + nrow) * (size_t)(d + 4);
@@ -374,7 +366,7 @@ __global__ void __launch_bounds__(256) step_inc_any_kernel(const IncStepArgs a, 
                     nrow += em ? 1 : 0;   // rows beyond the capacity are counted as dropped
                 }
             }
-            const int lim = sel(lanes(burn > 0), lim10, lim1);
+            const int lim = sel(lanes(burn > 0), tl.lim10, tl.lim1);
             burn -= sel(acc_m & lanes(burn > 0), 1, 0);
             // ---- commit: recomputed from the column
             const double ra = sel(acc_m, r, 0.0);
@@ -415,7 +407,7 @@ __global__ void __launch_bounds__(256) step_inc_any_kernel(const IncStepArgs a, 
             prej = sel(acc_m, 0, prej + sel(inside_m, 0, 1));
             wt = sel(acc_m, 1, wt + 1);
             nacc += sel(acc_m, 1, 0);
-            if (wt - prej > lim && c == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
+            if (wt - prej > lim && c == 0) report_stuck(s.stuck, gid);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -495,7 +487,7 @@ __global__ void __launch_bounds__(256, regs_min_waves(DQ, KM)) step_inc_regs_ker
     const int g = __builtin_amdgcn_readfirstlane(w / s.group_size);
     const int ncols = s.n_steps;
     const double* __restrict__ gVU = a.VU + (size_t)g * ncols * COL;
-    auto stage = [&](int k) {
+    auto stage = [&](int k) {   // (written out in every kernel: incremental_common.h, "around the step loop")
         const int first = k * C;
         if (first >= ncols) return;
         const int cols = ncols - first < C ? ncols - first : C;
@@ -589,9 +581,7 @@ __global__ void __launch_bounds__(256, regs_min_waves(DQ, KM)) step_inc_regs_ker
     int tacc = thinning ? s.thin_acc[w] : 0;
     const double inv_thin = thinning ? 1.0 / (double)s.thin : 1.0;
     const uint32_t gid = s.walker0 + (uint32_t)w;
-    const double mt10 = s.max_tries * 10.0;
-    const int lim1 = s.max_tries < 2.0e9 ? (int)floor(s.max_tries) : 0x7fffffff;
-    const int lim10 = mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff;
+    const TryLimits tl = try_limits(s.max_tries);
     __shared__ dpair_t short_log_lds[SHORT_LOG_TABLE_SIZE];
     const short_log_tab slog = short_log_load(short_log_lds);
     __shared__ double exp64_lds[64];   // 2^(j / 64): the log-sum-exp's table-driven exponential
@@ -761,16 +751,10 @@ __global__ void __launch_bounds__(256, regs_min_waves(DQ, KM)) step_inc_regs_ker
                 if (lanes(em) != 0ull) {   // some walker of the wave emits
                     int ew = wt;   // the weight the row is written with
                     if (thinning) {
-                        const int tot = tacc + wt;
-                        int q = (int)((double)tot * inv_thin);
-                        int rem = tot - q * s.thin;
-                        q += rem >= s.thin ? 1 : 0;
-                        rem -= rem >= s.thin ? s.thin : 0;
-                        q -= rem < 0 ? 1 : 0;
-                        rem += rem < 0 ? s.thin : 0;
-                        tacc = em ? rem : tacc;
-                        ew = q;
-                        em = em & (q > 0);
+                        const Thinned th = thinned(tacc + wt, s.thin, inv_thin);
+                        tacc = em ? th.rem : tacc;
+                        ew = th.q;
+                        em = em & (th.q > 0);
                     }
                     if (em & (nrow < s.row_cap)) {
                         double* __restrict__ row = s.rows + ((size_t)w * s.row_cap + nrow) * (size_t)(d + 4);
@@ -782,9 +766,9 @@ __global__ void __launch_bounds__(256, regs_min_waves(DQ, KM)) step_inc_regs_ker
                     nrow += em ? 1 : 0;   // rows beyond the capacity are counted as dropped
                 }
             }
-            int lim = lim1;
+            int lim = tl.lim1;
             if (burning) {   // wave-uniform (see step_inc_kernel)
-                lim = burn > 0 ? lim10 : lim1;
+                lim = tl.of(burn);
                 burn -= (accept & (burn > 0)) ? 1 : 0;
                 burning = lanes(burn > 0) != 0ull;
             }
@@ -821,7 +805,7 @@ __global__ void __launch_bounds__(256, regs_min_waves(DQ, KM)) step_inc_regs_ker
             prej = sel(acc_m, 0, prej + sel(inside_m, 0, 1));
             wt = sel(acc_m, 1, wt + 1);
             nacc += sel(acc_m, 1, 0);
-            if (wt - prej > lim && c == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
+            if (wt - prej > lim && c == 0) report_stuck(s.stuck, gid);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();

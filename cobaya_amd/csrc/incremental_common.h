@@ -1,5 +1,9 @@
-// Shared device helpers of the incremental kernels (incremental_kernels.hip, incremental_any.hip): DPP quad permutes and sums, lane-mask helpers, the priority rotation,
-// laundered LDS pointers, the size of a column chunk.  gfx950 only.
+// Shared device helpers of the incremental kernels (incremental_kernels.hip, incremental_any.hip, incremental_duo.hip):
+// DPP quad permutes and sums, lane-mask helpers, the priority rotation, laundered LDS pointers, the size of a column
+// chunk -- and what surrounds the step loop of every step kernel: the chunk staging, the in-kernel refresh of y, the
+// walker's scalars, the limits of tries with the burn-in rule, the re-anchoring sums, the emitted rows, the inward
+// single-precision bounds.  A kernel's body shows what is particular to it: its register layout, its trial loop and
+// its commit.  gfx950 only.
 #pragma once
 #include "det_math.h"
 #include "kernels.h"
@@ -169,6 +173,61 @@ __device__ __forceinline__ void stage4_dma(void* lds_dst, const void* gsrc)   //
 }
 // every DMA of this wave has landed (in front of the barrier that publishes the buffer)
 __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// ---------------------------------------------------------------- around the step loop
+// What the step kernels of the three files share beside the helpers above: the limits of tries with the burn-in rule,
+// the report of a stuck chain, the re-anchored log-density, the thinned weight of an emitted row.
+// What the helpers here may take.  A step kernel reads its arguments through `const StepArgs& s = a.s`, a reference
+// into the kernel's argument block, and keeps its state in local variables.  A helper that takes `s`, or a reference to
+// such a local, makes that object escape until the helper is inlined, which is after the first scalar-replacement
+// pass: the kernel's loops then get their loop-carried values in another order, and the register allocation of the
+// STEP loop changes with it (tried: with the walker's scalars in a struct wt and prej changed places in
+// step_duo_mix_kernel; a write-back function that took `s` changed 100 of the 121 kernels of a translation unit).  The
+// kernels are held to the machine code they were measured with (tools/compare_inc_asm.py), so the helpers take VALUES
+// -- numbers and pointers the kernel has read -- and return values.
+// Tried, and taken back because the machine code changed (profiles/r21_shared_pieces.txt); these stay written out in
+// every kernel, marked at the place:
+//   - the chunk staging (the `stage` lambdas): with the DMA loop in a function the two addresses of a DMA are formed
+//     in the other order -- one s_nop more per hidden DMA, other registers around it -- in every kernel but
+//     step_duo_mix_kernel;
+//   - the in-kernel refresh of y (step_inc_kernel, step_inc_duo_kernel): y is a register array, taken by reference;
+//   - the load and the write-back of the walker's seven scalars: they need `s`;
+//   - the inward single-precision bounds (twice in step_inc_kernel): the bounds are loaded in another order;
+//   - the store of an emitted row and the burn-in's update of `burn` and `burning`: references to the kernel's state.
+
+// stuck test (mcmc.py:717-743) on integers: (double)n > m  <=>  n > floor(m) for n integer.  lim1: the limit of
+// tries, lim10: the tenfold limit of a walker that is still burning in
+struct TryLimits {
+    int lim1, lim10;
+    // the limit of a walker with `burn` steps of burn-in left
+    __device__ __forceinline__ int of(int burn) const { return burn > 0 ? lim10 : lim1; }
+};
+__device__ __forceinline__ TryLimits try_limits(double max_tries)
+{
+    const double mt10 = max_tries * 10.0;
+    return {max_tries < 2.0e9 ? (int)floor(max_tries) : 0x7fffffff, mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff};
+}
+// a chain over its limit of tries: the flag (StepArgs::stuck) names such a walker
+__device__ __forceinline__ void report_stuck(int* stuck, uint32_t gid) { atomicCAS(stuck, 0, 1 + (int)gid); }
+
+// Re-anchoring the carried log-density on a y that has just been refreshed from x (orc_anchor_loglike,
+// orc_anchor_modes): -1/2 (c + |y|^2), |y|^2 summed (p0 + p1) + (p2 + p3) over the walker's lanes
+__device__ __forceinline__ double anchored_logpdf(double cnorm, double chi2) { return -0.5 * (cnorm + chi2); }
+
+// Thinned output (collection.py:1373-1383, OneSamplePoint.add_to_collection with output_thin): a walker's weights
+// add up, a row goes out when the sum `tot` reaches `thin`, with weight q = tot / thin -- the quotient by a
+// reciprocal (inv_thin = 1 / thin), set right by the remainder --, the remainder rem is carried
+struct Thinned { int q, rem; };
+__device__ __forceinline__ Thinned thinned(int tot, int thin, double inv_thin)
+{
+    int q = (int)((double)tot * inv_thin);
+    int rem = tot - q * thin;
+    q += rem >= thin ? 1 : 0;
+    rem -= rem >= thin ? thin : 0;
+    q -= rem < 0 ? 1 : 0;
+    rem += rem < 0 ? thin : 0;
+    return {q, rem};
+}
 
 // The (r, Ea) variates of an OCTET of steps, staged in LDS (round 4).  Lane class c of a walker draws
 // the Philox block of the step pair 4 * octet + c (PairRng) and leaves its two pairs in the wave's

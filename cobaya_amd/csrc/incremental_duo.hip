@@ -184,7 +184,7 @@ __global__ void __launch_bounds__(256, 2) step_duo_mix_kernel(const IncStepArgs 
     const int g = __builtin_amdgcn_readfirstlane(w / s.group_size);
     const int ncols = s.n_steps;
     const double* __restrict__ gVU = a.VU + (size_t)g * ncols * COL;
-    auto stage = [&](int k) {
+    auto stage = [&](int k) {   // (written out in every kernel: incremental_common.h, "around the step loop")
         const int first = k * C;
         if (first >= ncols) return;
         const int cols = ncols - first < C ? ncols - first : C;
@@ -234,9 +234,7 @@ __global__ void __launch_bounds__(256, 2) step_duo_mix_kernel(const IncStepArgs 
     const long long nacc0 = s.n_accept[w];
     int nacc = 0;
     const uint32_t gid = s.walker0 + (uint32_t)w;
-    const double mt10 = s.max_tries * 10.0;
-    const int lim1 = s.max_tries < 2.0e9 ? (int)floor(s.max_tries) : 0x7fffffff;
-    const int lim10 = mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff;
+    const TryLimits tl = try_limits(s.max_tries);
     __shared__ dpair_t short_log_lds[SHORT_LOG_TABLE_SIZE];
     const short_log_tab slog = short_log_load(short_log_lds);
     __shared__ double exp64_lds[64];   // 2^(j / 64): the log-sum-exp's table-driven exponential
@@ -273,7 +271,7 @@ __global__ void __launch_bounds__(256, 2) step_duo_mix_kernel(const IncStepArgs 
                 pa0 = fma(y[k][2 * kk], y[k][2 * kk], pa0);
                 pa1 = fma(y[k][2 * kk + 1], y[k][2 * kk + 1], pa1);
             }
-            am[k] = -0.5 * (cn[k] + duo_sum(pa0, pa1));
+            am[k] = anchored_logpdf(cn[k], duo_sum(pa0, pa1));
         }
         llik = lse(am);
         lpost = lpri + llik;
@@ -404,9 +402,9 @@ __global__ void __launch_bounds__(256, 2) step_duo_mix_kernel(const IncStepArgs 
             const double delta = UNIT_T ? (lpost - lt) : (lpost - lt) / s.temperature;
             const unsigned long long acc_m = inside_m & (lanes(lt > lpost) | lanes(Ea > delta));
             const bool accept = __builtin_amdgcn_inverse_ballot_w64(acc_m);
-            int lim = lim1;
+            int lim = tl.lim1;
             if (burning) {   // wave-uniform (see step_inc_kernel)
-                lim = burn > 0 ? lim10 : lim1;
+                lim = tl.of(burn);
                 burn -= (accept & (burn > 0)) ? 1 : 0;
                 burning = lanes(burn > 0) != 0ull;
             }
@@ -466,7 +464,7 @@ __global__ void __launch_bounds__(256, 2) step_duo_mix_kernel(const IncStepArgs 
             prej = sel(acc_m, 0, prej + sel(inside_m, 0, 1));
             wt = sel(acc_m, 1, wt + 1);
             nacc += sel(acc_m, 1, 0);
-            if (wt - prej > lim && h == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
+            if (wt - prej > lim && h == 0) report_stuck(s.stuck, gid);
         }
         dma_wait();   // the next chunk has landed
         __syncthreads();
@@ -609,7 +607,8 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
     const double2* __restrict__ gVU = (const double2*)a.VU + ((size_t)g * set_cols + (size_t)a.col0) * COLB;
     const double* __restrict__ gUUc = a.UU + ((size_t)g * set_cols + (size_t)a.col0);   // |u|^2 of the launch's columns
     double* const sUU = (double*)(smem2 + 2 * CHUNK);                                    // [2][C], behind the pairs
-    auto stage = [&](int k) {   // chunk k -> buffer k & 1, by DMA (as in step_inc_kernel)
+    // chunk k -> buffer k & 1, by DMA (as in step_inc_kernel)
+    auto stage = [&](int k) {   // (written out in every kernel: incremental_common.h, "around the step loop")
         const int first = k * C;
         if (first >= ncols) return;
         const int cols = ncols - first < C ? ncols - first : C;
@@ -683,7 +682,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
             if (e & 1) pa1 = fma(y[e], y[e], pa1);
             else pa0 = fma(y[e], y[e], pa0);
         }
-        llik = -0.5 * (s.cnorm0 + duo1_sum<SPLIT>(pa0, pa1));
+        llik = anchored_logpdf(s.cnorm0, duo1_sum<SPLIT>(pa0, pa1));
         lpost = lpri + llik;
     }
     int wt = s.weight[w], prej = s.prior_rej[w], burn = s.burn_left[w];
@@ -691,9 +690,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
     int nacc = 0;
     const cdoubles gUU = (cdoubles)(unsigned long long)(a.UU + (size_t)g * set_cols + (size_t)a.col0);
     const uint32_t gid = s.walker0 + (uint32_t)w;
-    const double mt10 = s.max_tries * 10.0;
-    const int lim1 = s.max_tries < 2.0e9 ? (int)floor(s.max_tries) : 0x7fffffff;
-    const int lim10 = mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff;
+    const TryLimits tl = try_limits(s.max_tries);
     __shared__ dpair_t short_log_lds[SHORT_LOG_TABLE_SIZE];
     const short_log_tab slog = short_log_load(short_log_lds);
     dma_wait();   // chunk 0 has landed
@@ -728,7 +725,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
         unsigned uoff = lds_offset(sUU + (k & 1) * C);   // (the same address in every lane: a broadcast read)
         // wt - prej grows by at most one per step: where no chain of the wave can pass lim1 within the chunk's columns,
         // its steps do not look (the burning wave keeps its bookkeeping, and its higher limit, at every step)
-        bool watch = burning || lanes(wt - prej > lim1 - cols) != 0ull;   // wave-uniform
+        bool watch = burning || lanes(wt - prej > tl.lim1 - cols) != 0ull;   // wave-uniform
 #pragma unroll 1
         for (int sl0 = 0; sl0 < cols;) {
             const unsigned long long S0 = s.step0 + (unsigned long long)(base + sl0);
@@ -867,10 +864,10 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
                 // (the test of the limit of tries and the burning wave's bookkeeping lie behind the loop: a wave past its
                 // burn-in whose chains cannot pass the limit inside this chunk -- `watch`, at the head of the chunk -- skips both)
                 if (__builtin_expect(watch, 0)) {   // wave-uniform
-                    unsigned long long over_m = lanes(wt - prej > lim1);
+                    unsigned long long over_m = lanes(wt - prej > tl.lim1);
                     if (burning) {   // wave-uniform (see step_inc_kernel); goes from true to false once per run
                         // (wt and prej are the committed ones, the limit is that of the burn-in left BEFORE this step)
-                        const int lim = burn > 0 ? lim10 : lim1;
+                        const int lim = tl.of(burn);
                         burn -= (accept & (burn > 0)) ? 1 : 0;
                         burning = lanes(burn > 0) != 0ull;
                         over_m = lanes(wt - prej > lim);
@@ -883,7 +880,7 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
         // a chain over its limit of tries is reported by a lane that was over it at some step of the chunk (it may
         // have accepted since): the flag says that, and names such a walker
         if (__builtin_expect(stuck_m != 0ull, 0)) {
-            if (__builtin_amdgcn_inverse_ballot_w64(stuck_m) && h == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
+            if (__builtin_amdgcn_inverse_ballot_w64(stuck_m) && h == 0) report_stuck(s.stuck, gid);
             stuck_m = 0ull;
         }
         dma_wait();   // the next chunk has landed

@@ -242,6 +242,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
 
     constexpr bool DMAH = MCMC_INC_DMA_HIDDEN(DQ, MODE);
     // chunk k of the launch -> buffer k & 1, by DMA: every wave moves every fourth KiB
+    // (written out in every kernel: incremental_common.h, "around the step loop")
     auto stage = [&](int k) {
         const int first = k * C;
         if (first >= ncols) return;
@@ -297,7 +298,8 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
             const double blo_d = a.prior[i];
             double bhi_d = a.prior[dpad + i];
             if (in && is_periodic(i)) bhi_d = pred_double(bhi_d);
-            // lo: rounded up, then one ulp further in; hi: rounded down, then one further in
+            // lo: rounded up, then one ulp further in; hi: rounded down, then one further in; written out here
+            // and below (incremental_common.h, "around the step loop")
             // (infinite bounds -- the padding, a dimension without a bound -- stay infinite)
             float fl = __double2float_ru(blo_d), fh = __double2float_rd(bhi_d);
             if (fl > -INFINITY) fl = nextafterf(fl, INFINITY);
@@ -379,6 +381,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
     double lpost = s.logpost[w], lpri = s.logprior[w], llik = s.loglike[w];
     __shared__ pair_t sRE[kStagedPairs];   // the (r, Ea) pairs of the current octet (StagedVariates)
     if (refresh_y) {
+        // (written out here and in step_inc_duo_kernel: incremental_common.h, "around the step loop")
         // y = L^-1 (x - mu) from the walker's x (round 5: whiten_state_kernel folded into the
         // launch that needs it -- one kernel and ~17 us less on the main stream between two step
         // kernels).  The deviations of the wave's 16 walkers go to LDS ([walker][dimension], in the
@@ -427,7 +430,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
         double pa = 0.0;   // is re-anchored on it (orc_anchor_loglike)
 #pragma unroll
         for (int kk = 0; kk < DQ; ++kk) pa = fma(y[kk], y[kk], pa);
-        llik = -0.5 * (s.cnorm0 + quad_sum(pa));
+        llik = anchored_logpdf(s.cnorm0, quad_sum(pa));
         if (NORMP) {
             // ... and the carried log-prior on x: the normal terms, branch-free -- a dimension
             // without one has 1/scale = 0 and mls = 0, so its term is fma(-0, 0, 0) = +0 and
@@ -458,10 +461,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
     const cdoubles gNL =
         (cdoubles)(unsigned long long)(NORMP ? a.NL + 2 * ((size_t)g * set_cols + (size_t)a.col0) : a.UU);
     const uint32_t gid = s.walker0 + (uint32_t)w;
-    // stuck test (mcmc.py:717-743) on integers: (double)n > m  <=>  n > floor(m) for n integer
-    const double mt10 = s.max_tries * 10.0;
-    const int lim1 = s.max_tries < 2.0e9 ? (int)floor(s.max_tries) : 0x7fffffff;
-    const int lim10 = mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff;
+    const TryLimits tl = try_limits(s.max_tries);
 
     __shared__ dpair_t short_log_lds[SHORT_LOG_TABLE_SIZE];
     const short_log_tab slog = short_log_load(short_log_lds);
@@ -729,7 +729,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
                             double ps = 0.0;
 #pragma unroll
                             for (int kk = 0; kk < DQ; ++kk) ps = fma(ytw[kk], ytw[kk], ps);
-                            const double ll_w = -0.5 * (s.cnorm0 + quad_sum(ps));
+                            const double ll_w = anchored_logpdf(s.cnorm0, quad_sum(ps));
                             ll = sel(wq, ll_w, ll);
                         }
                     }
@@ -747,19 +747,12 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
                         if (lanes(em) != 0ull) {   // (wave-uniform: some walker emits)
                             int ew = wt;   // the weight the row is written with
                             if (thinning) {
-                                // thinned output (collection.py:1373-1383): the weights add up; a
-                                // row goes out when the sum reaches `thin`, with weight sum / thin
-                                // (the quotient by a reciprocal, set right by the remainder)
-                                const int tot = tacc + wt;
-                                int q = (int)((double)tot * inv_thin);
-                                int rem = tot - q * s.thin;
-                                q += rem >= s.thin ? 1 : 0;
-                                rem -= rem >= s.thin ? s.thin : 0;
-                                q -= rem < 0 ? 1 : 0;
-                                rem += rem < 0 ? s.thin : 0;
-                                tacc = em ? rem : tacc;
-                                ew = q;
-                                em = em & (q > 0);
+                                // thinned output: the weights add up; a row goes out when the sum
+                                // reaches `thin`, with weight sum / thin (thinned)
+                                const Thinned th = thinned(tacc + wt, s.thin, inv_thin);
+                                tacc = em ? th.rem : tacc;
+                                ew = th.q;
+                                em = em & (th.q > 0);
                             }
                             if (em & (nrow < s.row_cap)) {
                                 double* __restrict__ row =
@@ -780,7 +773,7 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
                     int lim_b;
                     asm("" : "=v"(lim_b));   // (set and used while burning in only)
                     if (burning) {
-                        lim_b = burn > 0 ? lim10 : lim1;
+                        lim_b = tl.of(burn);
                         burn -= (accept & (burn > 0)) ? 1 : 0;
                         burning = lanes(burn > 0) != 0ull;
                     }
@@ -868,9 +861,9 @@ __global__ void __launch_bounds__(256, inc_min_waves(DQ, MODE, PER)) step_inc_ke
                     // (after the burn-in the limit is the wave-uniform lim1)
                     unsigned long long over_m;
                     if (was_burning) over_m = lanes(wt - prej > lim_b);
-                    else over_m = lanes(wt - prej > lim1);
+                    else over_m = lanes(wt - prej > tl.lim1);
                     if (__builtin_amdgcn_inverse_ballot_w64(over_m) && c == 0)
-                        atomicCAS(s.stuck, 0, 1 + (int)gid);
+                        report_stuck(s.stuck, gid);
                 }
             }
         }
@@ -934,7 +927,7 @@ drag_inc_kernel(const IncStepArgs a)
     const int CHUNK = Sc * cps * COLB;           // pairs per chunk
     const double2* __restrict__ gVU = (const double2*)a.VU + (size_t)g * nsteps * cps * COLB;
     double2* const sVU = smem2;
-    auto stage = [&](int k) {
+    auto stage = [&](int k) {   // (written out in every kernel: incremental_common.h, "around the step loop")
         const int first = k * Sc;
         if (first >= nsteps) return;
         const int n = nsteps - first < Sc ? nsteps - first : Sc;
@@ -976,9 +969,7 @@ drag_inc_kernel(const IncStepArgs a)
     long long nacc = s.n_accept[w];
     const long long nacc0 = nacc;
     const uint32_t gid = s.walker0 + (uint32_t)w;
-    const double mt10 = s.max_tries * 10.0;
-    const int lim1 = s.max_tries < 2.0e9 ? (int)floor(s.max_tries) : 0x7fffffff;
-    const int lim10 = mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff;
+    const TryLimits tl = try_limits(s.max_tries);
     const double navg = (double)cps;
     const int hw_slot = hw_wave_slot();
 
@@ -1132,7 +1123,7 @@ drag_inc_kernel(const IncStepArgs a)
             const unsigned long long accept_m =
                 ~lanes(dead) & metropolis(end_acc / navg, start_acc / navg, Ea0);
             const bool accept = __builtin_amdgcn_inverse_ballot_w64(accept_m);
-            const int lim = burn > 0 ? lim10 : lim1;
+            const int lim = tl.of(burn);
             burn -= (accept & (burn > 0)) ? 1 : 0;
             lpri = sel(accept_m, ce_lp, lpri);
             llik = sel(accept_m, ce_ll, llik);
@@ -1140,7 +1131,7 @@ drag_inc_kernel(const IncStepArgs a)
             prej = sel(accept_m, 0, prej);
             wt = sel(accept_m, 1, wt + 1);
             nacc += sel(accept_m, 1, 0);
-            if (!accept & !dead & (wt - prej > lim) && c == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
+            if (!accept & !dead & (wt - prej > lim) && c == 0) report_stuck(s.stuck, gid);
             // the walker's point: the dragged end point on accept (cs / ys were dragged along and
             // are re-seeded from it at the next step)
 #pragma unroll
@@ -1522,7 +1513,7 @@ step_inc_mix_kernel(const IncStepArgs a)
     const int g = __builtin_amdgcn_readfirstlane(w / s.group_size);
     const int ncols = s.n_steps;
     const double* __restrict__ gVU = a.VU + (size_t)g * ncols * COL;
-    auto stage = [&](int k) {
+    auto stage = [&](int k) {   // (written out in every kernel: incremental_common.h, "around the step loop")
         const int first = k * C;
         if (first >= ncols) return;
         const int cols = ncols - first < C ? ncols - first : C;
@@ -1570,9 +1561,7 @@ step_inc_mix_kernel(const IncStepArgs a)
     const long long nacc0 = s.n_accept[w];
     int nacc = 0;     // accepted steps of this launch
     const uint32_t gid = s.walker0 + (uint32_t)w;
-    const double mt10 = s.max_tries * 10.0;
-    const int lim1 = s.max_tries < 2.0e9 ? (int)floor(s.max_tries) : 0x7fffffff;
-    const int lim10 = mt10 < 2.0e9 ? (int)floor(mt10) : 0x7fffffff;
+    const TryLimits tl = try_limits(s.max_tries);
     __shared__ dpair_t short_log_lds[SHORT_LOG_TABLE_SIZE];
     const short_log_tab slog = short_log_load(short_log_lds);
     __shared__ double exp64_lds[64];   // 2^(j / 64): the log-sum-exp's table-driven exponential
@@ -1619,7 +1608,7 @@ step_inc_mix_kernel(const IncStepArgs a)
             double pa = 0.0;
 #pragma unroll
             for (int kk = 0; kk < DQ; ++kk) pa = fma(y[k][kk], y[k][kk], pa);
-            am[k] = -0.5 * (cn[k] + quad_sum(pa));
+            am[k] = anchored_logpdf(cn[k], quad_sum(pa));
         }
         llik = lse(am);
         lpost = lpri + llik;
@@ -1766,9 +1755,9 @@ step_inc_mix_kernel(const IncStepArgs a)
                 const double delta = UNIT_T ? (lpost - lt) : (lpost - lt) / s.temperature;
                 const unsigned long long acc_m = inside_m & (lanes(lt > lpost) | lanes(Ea > delta));
                 const bool accept = __builtin_amdgcn_inverse_ballot_w64(acc_m);
-                int lim = lim1;
+                int lim = tl.lim1;
                 if (burning) {   // wave-uniform (see step_inc_kernel)
-                    lim = burn > 0 ? lim10 : lim1;
+                    lim = tl.of(burn);
                     burn -= (accept & (burn > 0)) ? 1 : 0;
                     burning = lanes(burn > 0) != 0ull;
                 }
@@ -1809,7 +1798,7 @@ step_inc_mix_kernel(const IncStepArgs a)
                 prej = sel(acc_m, 0, prej + sel(inside_m, 0, 1));
                 wt = sel(acc_m, 1, wt + 1);
                 nacc += sel(acc_m, 1, 0);
-                if (wt - prej > lim && c == 0) atomicCAS(s.stuck, 0, 1 + (int)gid);
+                if (wt - prej > lim && c == 0) report_stuck(s.stuck, gid);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

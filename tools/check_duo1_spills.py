@@ -9,7 +9,7 @@ import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from check_duo_spills import compile_to_asm  # noqa: E402
+from hip_asm import duo_to_asm as compile_to_asm, kernels_matching  # noqa: E402
 
 
 def report(asm_text):
@@ -19,10 +19,9 @@ def report(asm_text):
                          r"\s+\.vgpr_spill_count:\s+(\d+)", asm_text):
         meta[m.group(1)] = (int(m.group(2)), int(m.group(3)))
     out = []
-    for m in re.finditer(r"^(_ZN4mcmc\S*step_inc_duo_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E\S*):\s.*?^\s*s_endpgm",
-                         asm_text, re.S | re.M):
+    for m, lines in kernels_matching(asm_text, r"(_ZN4mcmc\S*step_inc_duo_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E\S*)$"):
         in_loop, n, n_st = False, 0, 0
-        for line in m.group(0).split("\n"):
+        for line in lines:
             b = re.match(r"^\.LBB\d+_\d+:.*Depth=(\d+)", line)
             if b or re.match(r"^\.LBB\d+_\d+:", line):
                 in_loop = bool(b) and int(b.group(1)) >= 2

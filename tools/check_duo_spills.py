@@ -8,24 +8,10 @@ scratch instructions inside the step loop (the blocks the compiler marks `Depth=
     python tools/check_duo_spills.py [dq_lo dq_hi]        exit code 1 if a step loop stores to scratch or reloads more than once"""
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def compile_to_asm(dq_lo=6, dq_hi=8, extra=()):
-    from cobaya_amd import build as B
-    src = os.path.join(ROOT, "cobaya_amd", "csrc", "incremental_duo.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "duo.s")
-        flags = [f for f in B.FLAGS if f != "-fPIC"]
-        subprocess.run([B.hipcc(), *flags, *extra, f"-DMCMC_DUO_DQ_LO={dq_lo}", f"-DMCMC_DUO_DQ_HI={dq_hi}",
-                        "-S", "--cuda-device-only", "-o", out, src], check=True, capture_output=True)
-        with open(out) as f:
-            return f.read()
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from hip_asm import duo_to_asm as compile_to_asm, kernels_matching  # noqa: E402
 
 
 def report(asm_text):
@@ -35,10 +21,9 @@ def report(asm_text):
                          r"\s+\.vgpr_spill_count:\s+(\d+)", asm_text):
         meta[m.group(1)] = (int(m.group(2)), int(m.group(3)))
     out = []
-    for m in re.finditer(r"^(_ZN4mcmc\S*step_duo_mix_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E\S*):\s.*?^\s*s_endpgm",
-                         asm_text, re.S | re.M):
+    for m, lines in kernels_matching(asm_text, r"(_ZN4mcmc\S*step_duo_mix_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E\S*)$"):
         in_loop, n, n_st = False, 0, 0
-        for line in m.group(0).split("\n"):
+        for line in lines:
             if re.match(r"^\.LBB\d+_\d+:", line):
                 in_loop = "Depth=2" in line
             elif in_loop and line.strip().startswith("scratch_"):

@@ -14,7 +14,7 @@ import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from check_duo_spills import compile_to_asm  # noqa: E402
+from hip_asm import duo_to_asm as compile_to_asm, kernels_matching  # noqa: E402
 
 MIN_RUN = 4
 
@@ -22,10 +22,9 @@ MIN_RUN = 4
 def report(asm_text):
     """[{dq, ne, split, unit_t, ladders}], ladders = [(block label, reads in the run, [N of each lgkmcnt(N) behind it])]"""
     out = []
-    for m in re.finditer(r"^(_ZN4mcmc\S*step_inc_duo_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E\S*):\s.*?^\s*s_endpgm",
-                         asm_text, re.S | re.M):
+    for m, lines in kernels_matching(asm_text, r"_ZN4mcmc\S*step_inc_duo_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E"):
         ladders, in_loop, label, run, cur = [], False, None, 0, None
-        for line in m.group(0).split("\n"):
+        for line in lines:
             text = line.strip()
             b = re.match(r"^(\.LBB\d+_\d+):(?:.*Depth=(\d+))?", line)
             if b:
@@ -46,8 +45,8 @@ def report(asm_text):
                 if w and cur is not None:
                     cur[2].append(int(w.group(1)))
                 run = 0
-        out.append({"dq": int(m.group(2)), "ne": int(m.group(3)), "split": m.group(4) == "1",
-                    "unit_t": m.group(5) == "1", "ladders": ladders, "chunk_vmcnt": chunk_vmcnt(m.group(0))})
+        out.append({"dq": int(m.group(1)), "ne": int(m.group(2)), "split": m.group(3) == "1",
+                    "unit_t": m.group(4) == "1", "ladders": ladders, "chunk_vmcnt": chunk_vmcnt("\n".join(lines))})
     return out
 
 

@@ -8,19 +8,16 @@ instructions in it, and per producer block the scratch instructions and the
     python tools/check_pl_spills.py [extra -D flags]      exit code 1 if a loop spills"""
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import hip_asm  # noqa: E402
 
 
 def kernel_lines(asm_text, name=r"pl_fused_kernelILi5ELi4"):
-    m = re.search(r"^(_ZN4mcmc\S*" + name + r"\S*):\s.*?^\s*s_endpgm", asm_text, re.S | re.M)
-    if not m:
-        raise RuntimeError("kernel not found in the assembly")
-    return m.group(0).split("\n")
+    for _, lines in hip_asm.kernels_matching(asm_text, r"_ZN4mcmc\S*" + name):
+        return lines
+    raise RuntimeError("kernel not found in the assembly")
 
 
 def report(lines):
@@ -51,15 +48,7 @@ def report(lines):
 
 
 def compile_to_asm(extra=()):
-    from cobaya_amd import build as B
-    src = os.path.join(ROOT, "cobaya_amd", "csrc", "pliklite_kernels.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "pl.s")
-        flags = [f for f in B.FLAGS if f != "-fPIC"]
-        subprocess.run([B.hipcc(), *flags, *extra, "-S", "--cuda-device-only", "-o", out, src],
-                       check=True, capture_output=True)
-        with open(out) as f:
-            return f.read()
+    return hip_asm.compile_to_asm("pliklite_kernels.hip", extra)
 
 
 if __name__ == "__main__":

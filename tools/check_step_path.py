@@ -21,7 +21,7 @@ import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from check_duo_spills import compile_to_asm  # noqa: E402
+from hip_asm import duo_to_asm as compile_to_asm, kernels_matching  # noqa: E402
 
 LABEL = re.compile(r"^(\.LBB\d+_\d+):(?:.*Depth=(\d+))?")
 HEADER = re.compile(r"^;\s*=>\s*This (?:Inner )?Loop Header: Depth=(\d+)")
@@ -92,29 +92,30 @@ def step_path(kernel_text, reads):
     return out
 
 
-KERNEL = re.compile(r"^(_ZN4mcmc\S*step_inc_duo_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E\S*):\s.*?^\s*s_endpgm", re.S | re.M)
+def kernels(asm_text):
+    """(dq, ne, split, unit_t, text) of every step_inc_duo_kernel in the text"""
+    for m, lines in kernels_matching(asm_text, r"_ZN4mcmc\S*step_inc_duo_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E"):
+        yield int(m.group(1)), int(m.group(2)), m.group(3) == "1", m.group(4) == "1", "\n".join(lines)
 
 
 def report(asm_text):
     """[{dq, ne, split, unit_t, path}] for every step_inc_duo_kernel in the text (path: step_path for NE + 1 reads)"""
     out = []
-    for m in KERNEL.finditer(asm_text):
-        ne = int(m.group(3))
-        out.append({"dq": int(m.group(2)), "ne": ne, "split": m.group(4) == "1", "unit_t": m.group(5) == "1",
-                    "path": step_path(m.group(0), ne + 1)})
+    for dq, ne, split, unit_t, text in kernels(asm_text):
+        out.append({"dq": dq, "ne": ne, "split": split, "unit_t": unit_t, "path": step_path(text, ne + 1)})
     return out
 
 
 def step_lines(asm_text, dq, ne, unit_t):
     """(path, [(line, instruction)] from the first instruction behind the run of reads to the back-edge, labels as
     `.LBBn_m:`) of the instantiation <dq, ne, true, unit_t>; (None, []) where step_path finds none"""
-    for m in KERNEL.finditer(asm_text):
-        if (int(m.group(2)), int(m.group(3)), m.group(4), m.group(5)) != (dq, ne, "1", "1" if unit_t else "0"):
+    for k_dq, k_ne, k_split, k_unit_t, text in kernels(asm_text):
+        if (k_dq, k_ne, k_split, k_unit_t) != (dq, ne, True, bool(unit_t)):
             continue
-        p = step_path(m.group(0), ne + 1)
+        p = step_path(text, ne + 1)
         if p is None:
             break
-        rows = [(i, ln.strip()) for i, ln in enumerate(m.group(0).split("\n"))]
+        rows = [(i, ln.strip()) for i, ln in enumerate(text.split("\n"))]
         first = next(i for i, t in rows if i > p["run_at"] and t and not t.startswith(("ds_read_b128", ";")))
         return p, [(i, t.split(";")[0].strip()) for i, t in rows
                    if first <= i <= p["back_edge"] and t and not t.startswith(";")]

@@ -11,13 +11,10 @@ and the backward branch to it).  Static counts: what the loop bodies contain, no
 each executes -- the executed totals are SQ_INSTS_VALU in profiles/r02*_pmc.txt."""
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from cobaya_amd.build import FLAGS, hipcc  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from hip_asm import compile_to_asm, split_kernels  # noqa: E402
 
 CLASSES = [
     ("fp64 fma", r"^v_(fma|fmac)_f64"),
@@ -48,21 +45,11 @@ def classify(op, line):
     return "other vector" if op.startswith("v_") else "other"
 
 
-def assembly(src, defines):
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "k.s")
-        cmd = [hipcc(), *[f for f in FLAGS if f not in ("-fPIC",)], *defines, "-S",
-               "--cuda-device-only", src, "-o", out]
-        subprocess.run(cmd, check=True, capture_output=True)
-        with open(out) as f:
-            return f.read()
-
-
-def kernel_body(asm, mangled_re):
-    m = re.search(r"^(" + mangled_re + r"):[^\n]*\n(.*?)^\s*s_endpgm", asm, re.S | re.M)
-    if not m:
-        raise SystemExit(f"kernel {mangled_re} not found")
-    return m.group(1), m.group(2).splitlines()
+def kernel_body(asm, mangled):
+    lines = split_kernels(asm).get(mangled)
+    if lines is None:
+        raise SystemExit(f"kernel {mangled} not found")
+    return mangled, lines[1:-1]
 
 
 def count(lines):
@@ -117,14 +104,13 @@ def report(title, name, lines):
 
 
 def main():
-    csrc = os.path.join(ROOT, "cobaya_amd", "csrc")
-    inc = assembly(os.path.join(csrc, "incremental_kernels.hip"), ["-DMCMC_DQ_LO=1", "-DMCMC_DQ_HI=8"])
-    name, body = kernel_body(inc, r"_ZN4mcmc12_GLOBAL__N_115step_inc_kernelILi8ELi0ELb1ELb0ELb0ELb0EEEvNS_11IncStepArgsE")
+    inc = compile_to_asm("incremental_kernels.hip", ["-DMCMC_DQ_LO=1", "-DMCMC_DQ_HI=8"])
+    name, body = kernel_body(inc, "_ZN4mcmc12_GLOBAL__N_115step_inc_kernelILi8ELi0ELb1ELb0ELb0ELb0EEEvNS_11IncStepArgsE")
     report("step_inc_kernel<8, 0, true>  (d = 30, incremental evaluation; 16 walkers per wave: the "
            "step loop is the loop holding the ds_read_b128 / v_fma_f64 body; PairRng is the block "
            "with the v_mul_hi_u32 Philox rounds, entered every eighth step)", name, body)
-    wk = assembly(os.path.join(csrc, "walker_kernels.hip"), ["-DMCMC_D=30"])
-    name, body = kernel_body(wk, r"_ZN4mcmc12_GLOBAL__N_116step_pair_kernelILb1ELb0EEEvNS_8StepArgsE")
+    wk = compile_to_asm("walker_kernels.hip", ["-DMCMC_D=30"])
+    name, body = kernel_body(wk, "_ZN4mcmc12_GLOBAL__N_116step_pair_kernelILb1ELb0EEEvNS_8StepArgsE")
     report("step_pair_kernel<true, false>  (d = 30, evaluation: full; two waves per 64 walkers, "
            "both roles in one kernel body)", name, body)
 

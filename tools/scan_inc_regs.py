@@ -10,23 +10,17 @@ import os
 import re
 import subprocess
 import sys
-import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from cobaya_amd.build import FLAGS, INC_DQ_RANGES, hipcc  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from hip_asm import compile_to_asm  # noqa: E402
+from cobaya_amd.build import INC_DQ_RANGES  # noqa: E402
 
 
 def scan(rng):
     lo, hi = rng
-    out = os.path.join(tempfile.gettempdir(), f"inc_{lo}.s")
-    subprocess.run([hipcc()] + FLAGS + ["-S", "--cuda-device-only", f"-DMCMC_DQ_LO={lo}",
-                                        f"-DMCMC_DQ_HI={hi}", "-o", out,
-                                        os.path.join(ROOT, "cobaya_amd/csrc/incremental_kernels.hip")],
-                   check=True, stderr=subprocess.DEVNULL)
     rows = []
-    text = open(out).read()
+    text = compile_to_asm("incremental_kernels.hip", [f"-DMCMC_DQ_LO={lo}", f"-DMCMC_DQ_HI={hi}"])
     # (ROCm 7.2 writes these as expressions over the callees: `max(128, .L…pair_tail….num_vgpr)`,
     # `96+max(…)`: the leading number is the kernel's own)
     for m in re.finditer(r"\.set (\S+)\.num_vgpr, (?:max\()?(\d+)", text):
