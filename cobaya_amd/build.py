@@ -125,6 +125,7 @@ def translation_units(dims, big=True):
     tus += [("huge_kernels.hip", "huge", []),        # 128 < d <= 256 (run-time d)
             ("function_kernels.hip", "function", []),   # function targets (the user's batched device function)
             ("stretch_kernels.hip", "stretch", []),     # the stretch move on a function target
+            ("ensemble_move_kernels.hip", "ensemble_move", []),   # mixtures of stretch, DE and snooker moves
             ("host_linalg.cpp", "host_linalg", []),  # the host side: the C ABI, split by job
             ("capi.hip", "capi", []),
             ("capi_targets.hip", "capi_targets", []),

@@ -909,7 +909,12 @@ int mcmc_hip_set_full_state(mcmc_hip_ctx* h, const double* x, const double* logp
 int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
-    const bool stretch = h->mv.kind == MCMC_HIP_MOVE_STRETCH;   // (needs no proposal covariance)
+    // (the stretch move and the mixtures of ensemble moves need no proposal covariance)
+    const bool stretch = h->mv.kind == MCMC_HIP_MOVE_STRETCH || h->mx.n > 0;
+    if (h->mv.kind == MCMC_HIP_MOVE_STRETCH && h->mx.n > 0)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "mcmc_hip_set_moves and mcmc_hip_set_move(MCMC_HIP_MOVE_STRETCH) are both in force: a mixture "
+                    "replaces the one move (give the stretch move as a member, or switch one of them off)");
     if (!h->have_state || (!h->have_cov && !stretch))
         return fail(h, MCMC_HIP_ERR_STATE, "set_state and set_proposal_cov must precede step");
     if (n_steps <= 0) return fail(h, MCMC_HIP_ERR_ARG, "n_steps must be > 0");

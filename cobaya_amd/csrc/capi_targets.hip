@@ -291,19 +291,6 @@ int functions_refusals(mcmc_hip_ctx* h)
     return MCMC_HIP_OK;
 }
 
-// word 0 of Philox4x32-10 (det_math.h: philox4x32_10), on the host: the slot shuffle decides which
-// functions a step calls, so the host forms it too
-uint32_t philox_w0(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3)
-{
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
-
 // the block of every slot of `cycle` in the schedule all groups share: the Fisher-Yates shuffle of
 // basis_blocked_kernel (sequence 0) with GLOBAL group 0 in its counter
 void shared_schedule(mcmc_hip_ctx* h, unsigned long long cycle, int L)

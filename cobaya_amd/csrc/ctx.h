@@ -21,6 +21,7 @@
 #include "pliklite_args.h"
 #include "function_args.h"
 #include "stretch_args.h"
+#include "ensemble_move_args.h"
 #include "checkpoint_args.h"
 #include "marginal_args.h"
 #include "autocorr_args.h"
@@ -452,6 +453,15 @@ struct mcmc_hip_ctx {
         bool checked = false;      // the state in force has no half-group flat in a parameter
         bool broken = false;       // a callback failed between the half-updates: a state must be set again
     } mv;
+    // the mixture of ensemble moves (mcmc_hip_set_moves; DESIGN.md section 2, "Ensemble move
+    // mixtures"); n = 0: off.  It shares mv.q, mv.checked and mv.broken with the stretch move
+    struct Mixture {
+        int n = 0;
+        int kind[mcmc::kMaxEnsembleMoves];
+        double weight[mcmc::kMaxEnsembleMoves];        // normalised
+        double p0[mcmc::kMaxEnsembleMoves], p1[mcmc::kMaxEnsembleMoves];
+        unsigned long long below[mcmc::kMaxEnsembleMoves];   // member j is chosen by a word w0 < below[j] (and >= below[j - 1])
+    } mx;
 };
 
 // the end of a device product (mcmc_hip_destroy): what it holds, then the event of its read-out
@@ -569,7 +579,20 @@ int functions_evaluate(mcmc_hip_ctx* h, int n, const double* x, double* comps);
 int evaluate_binned_points(mcmc_hip_ctx* h, int n, const double* x, double* logprior, double* loglike);
 int function_call(mcmc_hip_ctx* h, int n, const double* points, double* loglike);
 int function_target_error(mcmc_hip_ctx* h, int bad);
-// capi_stretch.hip: the stretch move on the single-function target
+// word 0 of Philox4x32-10 (det_math.h: philox4x32_10), on the host: the slot shuffle decides which
+// functions a step calls and the mixture of ensemble moves the kind of a step, so the host forms it too
+inline uint32_t philox_w0(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3)
+{
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+// capi_stretch.hip: the stretch move, or a mixture of ensemble moves, on the single-function target
 int step_stretch(mcmc_hip_ctx* h, int n_steps);
 // capi_incremental.hip: incremental evaluation (d <= 128: step_incremental; above: step_huge)
 int blocked_basis(mcmc_hip_ctx* h, int which, unsigned long long c0, int ncyc, int L, size_t slab,

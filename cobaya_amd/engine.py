@@ -139,6 +139,7 @@ SYMBOLS = [
                                           C.c_uint64]),
     ("mcmc_hip_step", C.c_int, [_H, C.c_int32]),
     ("mcmc_hip_set_move", C.c_int, [_H, C.c_int32, C.c_double]),
+    ("mcmc_hip_set_moves", C.c_int, [_H, C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p]),
     ("mcmc_hip_sync", C.c_int, [_H]),
     ("mcmc_hip_get_counters", C.c_int, [_H, c_int64_p]),
     ("mcmc_hip_drain_samples", C.c_int, [_H, c_double_p, C.c_int64, c_int64_p]),
@@ -818,6 +819,23 @@ class Engine:
         if move not in kinds:
             raise EngineError(ERR_ARG, f"move must be 'metropolis' or 'stretch', got {move!r}")
         self._check(self._lib.mcmc_hip_set_move(self._h, kinds[move], float(stretch_a)))
+
+    def set_moves(self, moves):
+        """A weighted mixture of ensemble moves in place of the one move (mcmc_hip_set_moves;
+        cobaya_amd/moves.py has the format): e.g. [["de", 0.8], ["de", 0.2, {"gamma": 1.0}]].  The
+        kind of a step is drawn once per step for the whole ensemble; halves, partners and limits
+        are the stretch move's.  None or an empty list switches the mixture off."""
+        from .moves import parse
+        if not moves:
+            self._check(self._lib.mcmc_hip_set_moves(self._h, 0, None, None, None, None))
+            return
+        try:
+            members = parse(moves, self.d)
+        except ValueError as e:
+            raise EngineError(ERR_ARG, str(e)) from None
+        kinds = np.array([m[0] for m in members], np.int32)
+        w, p0, p1 = (np.array([m[i] for m in members], np.float64) for i in (1, 2, 3))
+        self._check(self._lib.mcmc_hip_set_moves(self._h, len(members), _ip(kinds), _dp(w), _dp(p0), _dp(p1)))
 
     def sync(self):
         self._check(self._lib.mcmc_hip_sync(self._h))

@@ -46,6 +46,7 @@ from .evidence import EvidenceAccumulator
 from .importance import ImportanceAccumulator
 from .marginals import MarginalsAccumulator
 from .model import ProblemSpec, UnsupportedModel
+from .moves import describe as describe_moves, normalised as normalised_moves, parse as parse_moves
 
 log = logging.getLogger("mcmc_hip")
 
@@ -210,6 +211,13 @@ HIP_DEFAULTS = {
                               # function is called twice, with half of the walkers each.  Needs
                               # group_size >= 4 d and `ref` pdfs (not fixed points)
     "stretch_a": 2.0,         # move: stretch -- the scale a > 1 of the stretch factor z in [1/a, a]
+    "moves": None,            # a weighted mixture of ensemble moves in place of `move` (which must stay
+                              # None): a list of 1 .. 8 members [kind, weight] or [kind, weight, {params}],
+                              # kinds "stretch" (a: 2.0), "de" -- differential evolution, x + gamma (p1 - p2)
+                              # (gamma: None = 2.38 / sqrt(2 d), sigma: 1e-5) -- and "snooker" (gamma: 1.7).
+                              # The kind is drawn per step, by weight, for the whole ensemble.  A "de"
+                              # member with gamma: 1 hops between the modes of a multimodal posterior:
+                              # [["de", 0.8], ["de", 0.2, {"gamma": 1.0}]].  Limits as for move: stretch
     "shared_basis": True,     # True: the walkers of a group share one Haar basis per cycle;
                               # False: every walker draws its own (proposal.py:59-69 to the
                               # letter: the reference-faithful control, much slower)
@@ -287,6 +295,8 @@ class EnsembleMCMC:
     supports_periodic_params = True
     move, stretch_a = None, 2.0     # (the options' default)
     stretch = False     # move: stretch is in force (`_check_move`)
+    moves = None
+    mixture = None      # moves: the members (kind id, normalised weight, p0, p1) in force (`_check_move`)
     fallback_covmat_scale = 4.0  # sampler.py:474
     _LoggedError = LoggedError   # the hosted class raises cobaya.log.LoggedError instead
     _engine_factory = staticmethod(Engine)  # the seam to libmcmc_hip.so (tests swap it)
@@ -542,6 +552,8 @@ class EnsembleMCMC:
             spec.configure(self.engine)
             if self.stretch:
                 self.engine.set_move("stretch", self.stretch_a)
+            if self.mixture:
+                self.engine.set_moves(self.moves)
             self._size_drain_ring(d, W)
             if len(self.blocks) > 1 or self.oversampling_factors[0] != 1:
                 self.engine.set_blocking(
@@ -661,16 +673,45 @@ class EnsembleMCMC:
         if self.move not in (None, "metropolis", "stretch"):
             self._fail("move must be None, 'metropolis' or 'stretch', got %r", self.move)
         self.stretch = self.move == "stretch"
+        self.mixture = None
+        if self.moves is not None:
+            if self.move is not None:
+                self._fail("moves and move: %r are both given: a mixture replaces the one move (leave `move` "
+                           "out; the stretch move can be a member, [\"stretch\", weight, {\"a\": ...}])", self.move)
+            try:
+                members = parse_moves(self.moves, d)
+            except ValueError as e:
+                self._fail("%s", e)
+            why = self._ensemble_limits(spec, d)
+            if why:
+                self._fail("moves: %s", why)
+            # (the snooker update draws three distinct members of a half-group)
+            assert int(self.group_size) // 2 >= 3
+            self.mixture = normalised_moves(members)
+            if self.learn_proposal:
+                self.log.info("moves -- the ensemble is the proposal: no proposal covariance is learned.")
+            self.learn_proposal = False
+            return
         if not self.stretch:
             return
         try:
             self.stretch_a = float(self.stretch_a)
         except (TypeError, ValueError):
             self._fail("stretch_a must be a number > 1, got %r", self.stretch_a)
-        why = None
         if not (np.isfinite(self.stretch_a) and self.stretch_a > 1):
             why = "stretch_a must be finite and > 1, got %r" % (self.stretch_a,)
-        elif spec.like_kind != "device_function":
+        else:
+            why = self._ensemble_limits(spec, d)
+        if why:
+            self._fail("move: stretch: %s", why)
+        if self.learn_proposal:
+            self.log.info("move: stretch -- the ensemble is the proposal: no proposal covariance is learned.")
+        self.learn_proposal = False
+
+    def _ensemble_limits(self, spec, d):
+        """What the half-ensemble moves (`move: stretch`, `moves`) do not serve: the reason, or None."""
+        why = None
+        if spec.like_kind != "device_function":
             why = ("likelihood %r is not served: the move is for one device_function likelihood (analytic "
                    "targets have the learned Gaussian proposal)" % (spec.like_kind,))
         elif spec.functions:
@@ -696,11 +737,7 @@ class EnsembleMCMC:
                 why = ("`ref` of %s is a fixed point: every walker would start with the same value there, and "
                        "the move can never leave that hyperplane; give `ref` as a pdf (e.g. {dist: norm, "
                        "loc: ..., scale: ...}) or leave it out (the prior is used)" % (fixed,))
-        if why:
-            self._fail("move: stretch: %s", why)
-        if self.learn_proposal:
-            self.log.info("move: stretch -- the ensemble is the proposal: no proposal covariance is learned.")
-        self.learn_proposal = False
+        return why
 
     def _check_function(self, spec, d):
         """A `device_function` likelihood is sampled from scratch with Metropolis steps of one
@@ -1195,6 +1232,8 @@ class EnsembleMCMC:
             st["geometry"] = np.array([int(self.group_size), int(self.basis_group_size)], dtype=np.int64)
             if self.stretch:   # (absent: metropolis -- the file of the default move keeps its key set)
                 st["move"] = np.array([1.0, float(self.stretch_a)])
+            if self.mixture:   # (absent: no mixture) rows of kind, normalised weight, p0, p1
+                st["moves"] = np.array(self.mixture, dtype=np.float64)
             acc_n, acc_gs, acc_S = self.engine.read_moments(reset=False)
             st.update(acc_n=np.int64(acc_n), acc_gs=acc_gs, acc_S=acc_S)
             ivs = self._intervals
@@ -1243,6 +1282,13 @@ class EnsembleMCMC:
                 return "stretch (stretch_a: %g)" % m[1] if m[0] else "metropolis"
             self._fail("cannot resume -- the run was written with move: %s and now has move: %s (the "
                        "walkers' trials depend on it).", name(was), name(now))
+        was = z["moves"] if "moves" in z else np.zeros((0, 4))   # (absent: no mixture)
+        now = np.array(self.mixture or [], dtype=np.float64).reshape(-1, 4)
+        if not np.array_equal(was, now):
+            def mname(m):
+                return describe_moves(m) if len(m) else "None"
+            self._fail("cannot resume -- the run was written with moves: %s and now has moves: %s (the "
+                       "walkers' trials depend on them).", mname(was), mname(now))
         if "thin_carry" in z and not self._device_thin:
             self._thin_carry = z["thin_carry"].astype(np.int64)
         self.engine.set_proposal_cov(z["proposal_cov"])

@@ -310,6 +310,27 @@ MCMC_HIP_API int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps);
  * mcmc_hip_set_move itself refuses an unknown kind and an `a` that is not finite or <= 1. */
 enum { MCMC_HIP_MOVE_METROPOLIS = 0, MCMC_HIP_MOVE_STRETCH = 1 };
 MCMC_HIP_API int mcmc_hip_set_move(mcmc_hip_ctx* h, int32_t kind, double a);
+/* A weighted mixture of ensemble moves in place of the one move above ("Ensemble
+ * move mixtures"; ensemble_move_kernels.hip): n = 1 .. 8 members, member j of kind kinds[j] with weight
+ * weights[j] (positive and finite; normalised here) and parameters p0[j], p1[j]:
+ *   MCMC_HIP_ENSEMBLE_STRETCH   p0 = a > 1: the stretch move above
+ *   MCMC_HIP_ENSEMBLE_DE        differential evolution, t = x + gamma (p1 - p2) with two distinct partners
+ *                               and gamma = p0 (1 + p1 n), n standard normal: p0 = gamma0 > 0 (the usual
+ *                               2.38 / sqrt(2 d) is the caller's to form; 1 hops between modes),
+ *                               p1 = sigma >= 0
+ *   MCMC_HIP_ENSEMBLE_SNOOKER   the snooker update, t = x + c (x - z) with c = p0 s / |x - z|^2, s the
+ *                               projection of the difference of two further partners on x - z:
+ *                               p0 = gamma_s > 0 (1.7 is usual); accepted with (|t - z| / |x - z|)^(d - 1)
+ * Halves, partners (the other half of the walker's own group, pairwise distinct), the one call of the
+ * function per half-update, the callback rule and every limit are those of MCMC_HIP_MOVE_STRETCH; the
+ * kind of a step is drawn once per step for the whole ensemble -- every rank and every walker offset
+ * draws the same -- from the seed and the step alone.  n = 0 switches the mixture off (the pointers may
+ * be NULL).  A mixture needs mcmc_hip_set_move at MCMC_HIP_MOVE_METROPOLIS (mcmc_hip_step refuses both).
+ * Refused here with MCMC_HIP_ERR_ARG, the offender named: n outside 0 .. 8, an unknown kind, a weight
+ * that is not positive and finite, a <= 1, a gamma that is not finite or <= 0, sigma < 0. */
+enum { MCMC_HIP_ENSEMBLE_STRETCH = 0, MCMC_HIP_ENSEMBLE_DE = 1, MCMC_HIP_ENSEMBLE_SNOOKER = 2 };
+MCMC_HIP_API int mcmc_hip_set_moves(mcmc_hip_ctx* h, int32_t n, const int32_t* kinds, const double* weights,
+                                    const double* p0, const double* p1);
 /* wait for queued work; returns MCMC_HIP_ERR_STUCK if a walker tripped max_tries, and
  * MCMC_HIP_ERR_TARGET if a function target returned NaN or +inf inside the prior support */
 MCMC_HIP_API int mcmc_hip_sync(mcmc_hip_ctx* h);

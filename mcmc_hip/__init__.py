@@ -64,6 +64,7 @@ else:
         importance: dict | None = HIP_DEFAULTS["importance"]
         move: str | None = HIP_DEFAULTS["move"]
         stretch_a: float = HIP_DEFAULTS["stretch_a"]
+        moves: list | None = HIP_DEFAULTS["moves"]
 
         def _export_collection(self, coll):
             """Our table -> `cobaya.collection.SampleCollection` (same columns,
