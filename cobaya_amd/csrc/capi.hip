@@ -309,6 +309,10 @@ int mcmc_hip_create(const mcmc_hip_config* cfg, mcmc_hip_ctx** out)
     h->shift.assign(h->d, 0.0);
     h->incremental = (cfg->flags & MCMC_HIP_FLAG_INCREMENTAL) != 0;
     h->own_basis = (cfg->flags & MCMC_HIP_FLAG_OWN_BASIS) != 0 && cfg->d > 1;
+    // MCMC_HIP_DIR_BUDGET_KIB (test switch): KiB of directions per span of mcmc_hip_step instead of the
+    // steppers' 256 and 64 MiB (step_span.h; 1: every span is one cycle)
+    if (const char* e = getenv("MCMC_HIP_DIR_BUDGET_KIB"))
+        if (atol(e) > 0) h->dir_budget = (size_t)atol(e) << 10;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
         delete h;
         return fail(nullptr, MCMC_HIP_ERR_DEVICE, "hipStreamCreate failed");
@@ -929,7 +933,6 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
     const bool drag = h->drag_last_slow >= 0;
     // steps (= direction columns) per cycle, doubles per (group, cycle) slab of directions
     const int Lc = block_slots(h, drag ? 1 : 0);
-    const unsigned long long d = (unsigned long long)Lc;
     // (parameter blocks and dragging at d > 32: blocked directions in the d <= 32 layout --
     // column stride d -- read by the general kernels)
     const bool big_blocked = h->kb && (h->blocked || drag);
@@ -963,60 +966,42 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
                     "a cycle of %d steps needs %zu KiB of LDS per group: use group_size 256 or "
                     "smaller oversampling factors", Lc, dd * sizeof(double) / 1024);
     // directions buffer: at most ~256 MiB of cycles per launch
-    const int max_cyc = (int)std::max<size_t>(1, (256u << 20) / (sizeof(double) * dd * (size_t)n_basis));
+    const int max_cyc = max_span_cycles(h, 256u << 20, dd, n_basis);
     // dragging: the fast blocks' directions, n_drag columns per step
     const int Lf = drag ? block_slots(h, 2) : 0;
     const size_t ddf = drag ? (size_t)mcmc::v_slab_cols(Lf, h->d) : 0;
     const unsigned long long nd = (unsigned long long)h->drag_steps;
-    const int max_cyc_f =
-        drag ? (int)std::max<size_t>(2, (256u << 20) / (sizeof(double) * ddf * (size_t)h->G)) : 0;
+    const int max_cyc_f = drag ? max_span_cycles(h, 256u << 20, ddf, h->G, 2) : 0;
+    // the arguments of the general d > 32 kernels around those of a launch
+    auto general_args = [h](const mcmc::StepArgs& a, int ld, int own_basis) {
+        mcmc::GeneralStepArgs g{};
+        g.s = a;
+        g.Lrow = h->dLrow.p; g.d = h->d; g.ld = ld; g.own_basis = own_basis;
+        put_norm_mask4(h, g.norm_mask4);
+        periodic_mask4(h, g.periodic_mask4);
+        return g;
+    };
     int left = n_steps;
     while (left > 0) {
-        const unsigned long long c0 = h->step / d;
-        const unsigned long long room = (c0 + (unsigned long long)max_cyc) * d - h->step;
-        int n = (int)std::min<unsigned long long>((unsigned long long)left, room);
-        if (drag) {  // at most max_cyc_f cycles of fast directions per launch
-            const unsigned long long fc0 = h->step * nd / (unsigned long long)Lf;
-            const unsigned long long fend = (fc0 + (unsigned long long)max_cyc_f) * (unsigned long long)Lf;
-            const unsigned long long room_f = (fend - h->step * nd) / nd;   // whole steps
-            n = (int)std::min<unsigned long long>((unsigned long long)n, std::max<unsigned long long>(1, room_f));
-        }
-        const unsigned long long c1 = (h->step + (unsigned long long)n - 1) / d;
-        const int ncyc = (int)(c1 - c0 + 1);
+        // (dragging: at most max_cyc_f cycles of fast directions per launch as well)
+        const StepSpan sp = drag ? drag_span(h->step, left, Lc, max_cyc, h->drag_steps, Lf, max_cyc_f)
+                                 : step_span(h->step, left, Lc, max_cyc);
+        const unsigned long long c0 = sp.c0;
+        const int n = sp.n, ncyc = sp.ncyc;
         bool any_1d = false;
         {
             Timed t(h, 1);
-            if (h->blocked) {
-                const int rc = blocked_basis(h, drag ? 1 : 0, c0, ncyc, Lc, dd, h->V, h->vflag, any_1d);
-                if (rc != MCMC_HIP_OK) return rc;
-            } else {
-                HIP_TRY(h, h->V.resize((size_t)n_basis * ncyc * dd));
-                mcmc::BasisArgs b{};
-                b.T = h->dT.p; b.V = h->V.p;
-                b.group0 = basis0;
-                b.cycle0 = (uint32_t)c0;
-                b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
-                b.ncyc = ncyc;
-                if (h->kb) HIP_TRY(h, h->kb->basis(b, n_basis, h->d, h->stream));
-                else HIP_TRY(h, h->k->basis(b, n_basis, h->stream));
-            }
+            const int rc = h->blocked ? blocked_basis(h, drag ? 1 : 0, c0, ncyc, Lc, dd, h->V, h->vflag, any_1d)
+                                      : shared_basis(h, h->V, n_basis, basis0, c0, ncyc, dd, h->stream);
+            if (rc != MCMC_HIP_OK) return rc;
         }
         {
             Timed t(h, 0);
-            mcmc::StepArgs a{};
-            a.x = h->x.p; a.logpost = h->logpost.p; a.logprior = h->logprior.p;
-            a.loglike = h->loglike.p; a.weight = h->weight_i.p; a.prior_rej = h->prej.p;
-            a.burn_left = h->burn.p; a.n_accept = h->nacc.p; a.stuck = h->stuck.p;
-            a.accept_total = h->acc_total.p;
+            mcmc::StepArgs a = step_args(h);
             a.rows = h->rows.p; a.n_rows = h->nrows.p; a.row_cap = h->cfg.emit_capacity;
-            a.cblock = h->cblock.p; a.V = h->V.p; a.W = h->W; a.n_modes = h->K;
-            a.group_size = h->gs;
-            a.norm_mask = h->norm_mask; a.periodic_mask = h->periodic_mask;
-            a.walker0 = h->cfg.walker_offset;
-            a.key0 = (uint32_t)h->cfg.seed; a.key1 = (uint32_t)(h->cfg.seed >> 32);
+            a.V = h->V.p; a.n_modes = h->K;
+            a.periodic_mask = h->periodic_mask;
             a.step0 = h->step; a.n_steps = n; a.ncyc = ncyc;
-            a.uniform_logp = h->uniform_logp; a.temperature = h->cfg.temperature;
-            a.max_tries = h->cfg.max_tries;
             a.cnorm0 = h->K > 0 ? h->cnorm[0] : 0.0;
             a.cps = Lc; a.slab = (int)dd;
             a.vflag = any_1d ? h->vflag.p : nullptr;
@@ -1038,11 +1023,7 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
                 g.vflag_f = any_1d_f ? h->vflag_f.p : nullptr;
                 if (h->kb) {   // 32 < d <= 128: the general dragging kernel
                     mcmc::GeneralDragArgs q{};
-                    q.g.s = a;
-                    q.g.Lrow = h->dLrow.p; q.g.d = h->d; q.g.ld = h->d; q.g.own_basis = 0;
-                    for (int m = 0; m < 4; ++m) q.g.norm_mask4[m] = h->norm_mask4[m];
-                    for (int i = 0; i < h->d; ++i)
-                        if (h->periodic[i]) q.g.periodic_mask4[i >> 5] |= 1u << (i & 31);
+                    q.g = general_args(a, h->d, 0);
                     HIP_TRY(h, h->drag_cs.resize((size_t)h->d * h->W));
                     q.Vf = g.Vf; q.vflag_f = g.vflag_f; q.cs = h->drag_cs.p;
                     q.cyc0 = g.cyc0; q.cyc0_f = g.cyc0_f; q.cps_f = g.cps_f; q.slab_f = g.slab_f;
@@ -1052,15 +1033,8 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
                     HIP_TRY(h, h->k->drag(g, h->stream));
                 }
             } else if (general_big) {
-                mcmc::GeneralStepArgs g{};
-                g.s = a;
-                g.Lrow = h->dLrow.p;
-                g.d = h->d;
-                g.ld = (h->kb && !big_blocked) ? mcmc::v_ld(h->d) : h->d;
-                g.own_basis = h->own_basis ? 1 : 0;
-                for (int q = 0; q < 4; ++q) g.norm_mask4[q] = h->norm_mask4[q];
-                for (int i = 0; i < h->d; ++i)
-                    if (h->periodic[i]) g.periodic_mask4[i >> 5] |= 1u << (i & 31);
+                const mcmc::GeneralStepArgs g = general_args(
+                    a, (h->kb && !big_blocked) ? mcmc::v_ld(h->d) : h->d, h->own_basis ? 1 : 0);
                 HIP_TRY(h, mcmc_hip_launch_general_step(&g, h->stream));
             } else if (h->kb) {
                 a.norm_mask = h->norm_mask4[0];

@@ -160,15 +160,8 @@ int make_directions(mcmc_hip_ctx* h, const IncChoice& C, const IncPlan& P, const
             if (rc != MCMC_HIP_OK) return rc;
         }
     } else {
-        HIP_TRY(h, D.V.resize((size_t)h->BG * s.ncyc * P.dd));
-        mcmc::BasisArgs b{};
-        b.T = h->dT.p; b.V = D.V.p;
-        b.group0 = h->cfg.walker_offset / (uint32_t)h->bgs;
-        b.cycle0 = (uint32_t)s.c0;
-        b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
-        b.ncyc = s.ncyc;
-        if (h->kb) HIP_TRY(h, h->kb->basis(b, h->BG, h->d, st));
-        else HIP_TRY(h, h->k->basis(b, h->BG, st));
+        const int rc = shared_basis(h, D.V, h->BG, h->cfg.walker_offset / (uint32_t)h->bgs, s.c0, s.ncyc, P.dd, st);
+        if (rc != MCMC_HIP_OK) return rc;
     }
     HIP_TRY(h, D.VU.resize((size_t)h->BG * s.n * (1 + nd) * (size_t)C.colb));
     // one-parameter blocks: the columns that draw the RandProposer1D variates, in VU order
@@ -297,23 +290,17 @@ mcmc::IncStepArgs fill_inc_args(const mcmc_hip_ctx* h, const IncChoice& C, const
 {
     const int d = P.d, K = P.K;
     mcmc::IncStepArgs a{};
-    a.s.x = h->x.p; a.s.logpost = h->logpost.p; a.s.logprior = h->logprior.p;
-    a.s.loglike = h->loglike.p; a.s.weight = h->weight_i.p; a.s.prior_rej = h->prej.p;
-    a.s.burn_left = h->burn.p; a.s.n_accept = h->nacc.p; a.s.stuck = h->stuck.p;
-    a.s.accept_total = h->acc_total.p;
+    a.s = step_args(h);
+    a.s.group_size = h->bgs;   // the walkers that share a column of VU
+    a.s.norm_mask = 0;         // (these kernels take the priors from `prior` and has_norm)
     a.s.rows = h->rows.p; a.s.n_rows = h->nrows.p; a.s.row_cap = h->cfg.emit_capacity;
     a.s.thin = h->emit_thin; a.s.thin_acc = h->thin_acc.p;
-    a.s.W = h->W; a.s.n_modes = K; a.s.group_size = h->bgs;   // the walkers that share a column of VU
-    a.s.cblock = h->cblock.p;
+    a.s.n_modes = K;
     {
         const ConstLayout cl{d, K};
         a.n_modes = K; a.cnorm_off = cl.cnorm(); a.weight_off = cl.weight();
     }
-    a.s.walker0 = h->cfg.walker_offset;
-    a.s.key0 = (uint32_t)h->cfg.seed; a.s.key1 = (uint32_t)(h->cfg.seed >> 32);
     a.s.step0 = h->step; a.s.n_steps = n;
-    a.s.uniform_logp = h->uniform_logp; a.s.temperature = h->cfg.temperature;
-    a.s.max_tries = h->cfg.max_tries;
     a.s.cnorm0 = h->cnorm[0];
     a.y = h->y.p; a.VU = D.VU.p; a.prior = h->inc_prior.p;
     a.d = d; a.dq = C.dq;
@@ -333,8 +320,7 @@ mcmc::IncStepArgs fill_inc_args(const mcmc_hip_ctx* h, const IncChoice& C, const
     a.VW = C.carry_prior ? D.VW.p : nullptr;
     a.NL = C.carry_prior ? D.NL.p : nullptr;
     a.accept_slack = h->accept_slack;
-    for (int i = 0; i < d; ++i)
-        if (h->periodic[i]) a.periodic_mask4[i >> 5] |= 1u << (i & 31);
+    periodic_mask4(h, a.periodic_mask4);
     return a;
 }
 

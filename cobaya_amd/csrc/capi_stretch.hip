@@ -114,18 +114,10 @@ int step_stretch(mcmc_hip_ctx* h, int n_steps)
     HIP_TRY(h, h->mv.q.resize(n_act));
     mcmc::EnsembleMoveArgs ma{};
     mcmc::StretchArgs& a = ma.st;
-    a.s.x = h->x.p; a.s.logpost = h->logpost.p; a.s.logprior = h->logprior.p;
-    a.s.loglike = h->loglike.p; a.s.weight = h->weight_i.p; a.s.prior_rej = h->prej.p;
-    a.s.burn_left = h->burn.p; a.s.n_accept = h->nacc.p; a.s.stuck = h->stuck.p;
-    a.s.accept_total = h->acc_total.p;
-    a.s.cblock = h->cblock.p; a.s.W = W; a.s.group_size = h->gs; a.s.n_modes = 0;
-    a.s.norm_mask = h->norm_mask; a.s.walker0 = h->cfg.walker_offset;
-    a.s.key0 = (uint32_t)h->cfg.seed; a.s.key1 = (uint32_t)(h->cfg.seed >> 32);
-    a.s.uniform_logp = h->uniform_logp; a.s.temperature = h->cfg.temperature;
-    a.s.max_tries = h->cfg.max_tries;
+    a.s = step_args(h);
     a.d = d; a.a = h->mv.a; a.dm1 = (double)(d - 1);
     a.log2_half = h->gs == 64 ? 5 : (h->gs == 128 ? 6 : 7);
-    for (int q = 0; q < 4; ++q) a.norm_mask4[q] = h->norm_mask4[q];
+    put_norm_mask4(h, a.norm_mask4);
     a.points = F.points.p; a.lp_t = F.lp_t.p; a.Ea = F.Ea.p; a.q = h->mv.q.p; a.ll_t = F.ll_t.p;
     a.bad = F.bad.p;
     // one launch: [accept of the pending half +] the proposal (propose: 0 for the last accept of a call)

@@ -5,6 +5,54 @@
 
 namespace {
 
+// ------------------------------------------------------------------ the trial pipeline
+// mcmc_hip_step on a target that is evaluated outside the walker kernel: per step one launch
+// [accept of the previous trial +] proposal, then the target on the trial points; a call ends with
+// the accept of its last trial, so the state is complete between calls.  The steps are cut into
+// spans of at most max_cyc cycles of L (step_span.h), whose directions go to h->V, and every step
+// is placed in w, the walker kernel's arguments (w.s: its StepArgs).  The stepper's own parts:
+// directions(span) forms the span's directions; launch(accept, propose) launches the walker kernel
+// on w; evaluate() evaluates the trial.  All three return a code of mcmc_hip.h.  The launch has
+// settled the previous trial, so an evaluation that fails drops THIS trial only -- state and step
+// counter stay as of the last completed step -- and ends the call with its code.
+template <class WalkerArgs, class Directions, class Launch, class Evaluate>
+int trial_pipeline(mcmc_hip_ctx* h, int n_steps, int L, int max_cyc, WalkerArgs& w, Directions directions,
+                   Launch launch, Evaluate evaluate)
+{
+    const unsigned long long Lu = (unsigned long long)L;
+    bool pending = false;   // a trial has been proposed and evaluated, not yet accepted / rejected
+    int rc = MCMC_HIP_OK;
+    for (int left = n_steps; left > 0 && rc == MCMC_HIP_OK;) {
+        const StepSpan sp = step_span(h->step, left, L, max_cyc);
+        {
+            Timed t(h, 1);
+            const int drc = directions(sp);
+            if (drc) return drc;
+        }
+        w.s.V = h->V.p; w.s.ncyc = sp.ncyc;
+        for (int s = 0; s < sp.n && rc == MCMC_HIP_OK; ++s) {
+            w.s.step0 = h->step;
+            w.cyc = (int)(h->step / Lu - sp.c0);
+            w.col = (int)(h->step % Lu);
+            const int lrc = launch(pending ? 1 : 0, 1);
+            if (lrc) return lrc;
+            h->n_step_launches += 1;
+            pending = false;
+            rc = evaluate();
+            if (rc == MCMC_HIP_OK) {
+                pending = true;
+                h->step += 1;
+            }
+        }
+        left -= sp.n;
+    }
+    if (pending) {
+        const int lrc = launch(1, 0);
+        if (lrc) return lrc;
+    }
+    return rc;
+}
+
 // ------------------------------------------------------------------ binned Gaussian target
 // chain of the chi2 sum that row tile R of NT joins (oracle: binned_class): its position in its
 // group of eight tiles, the groups counted down from the last tile.  pl_fused_kernel gives the
@@ -103,75 +151,42 @@ int step_binned(mcmc_hip_ctx* h, int n_steps)
     if (unfused)    // (fused: delta lives in LDS, 323 MB of HBM less at 65 536 walkers)
         HIP_TRY(h, B.delta.resize(((size_t)W / 64) * (size_t)B.KT * 256 + (size_t)mcmc::kPlPad * 256));
     const size_t dd = (size_t)mcmc::v_slab(d);
-    const int max_cyc = (int)std::max<size_t>(1, (64u << 20) / (sizeof(double) * dd * (size_t)h->G));
     mcmc::PlWalkerArgs a{};
-    a.s.x = h->x.p; a.s.logpost = h->logpost.p; a.s.logprior = h->logprior.p;
-    a.s.loglike = h->loglike.p; a.s.weight = h->weight_i.p; a.s.prior_rej = h->prej.p;
-    a.s.burn_left = h->burn.p; a.s.n_accept = h->nacc.p; a.s.stuck = h->stuck.p;
-    a.s.accept_total = h->acc_total.p;
-    a.s.cblock = h->cblock.p; a.s.W = W; a.s.group_size = h->gs; a.s.n_modes = 0;
-    a.s.norm_mask = h->norm_mask; a.s.walker0 = h->cfg.walker_offset;
-    a.s.key0 = (uint32_t)h->cfg.seed; a.s.key1 = (uint32_t)(h->cfg.seed >> 32);
-    a.s.uniform_logp = h->uniform_logp; a.s.temperature = h->cfg.temperature;
-    a.s.max_tries = h->cfg.max_tries; a.s.cps = d; a.s.slab = (int)dd;
+    a.s = step_args(h);
+    a.s.cps = d; a.s.slab = (int)dd;
     a.d = d; a.trial = B.trial.p; a.lp_t = B.lp_t.p; a.Ea = B.Ea.p; a.psum_t = B.psum.p;
-    int left = n_steps;
-    bool pending = false;   // a trial has been proposed and evaluated, not yet accepted / rejected
-    while (left > 0) {
-        const unsigned long long c0 = h->step / (unsigned long long)d;
-        const unsigned long long room = (c0 + (unsigned long long)max_cyc) * d - h->step;
-        const int n = (int)std::min<unsigned long long>((unsigned long long)left, room);
-        const int ncyc = (int)((h->step + (unsigned long long)n - 1) / d - c0 + 1);
-        {
-            Timed t(h, 1);
-            HIP_TRY(h, h->V.resize((size_t)h->G * ncyc * dd));
-            mcmc::BasisArgs b{};
-            b.T = h->dT.p; b.V = h->V.p;
-            b.group0 = h->cfg.walker_offset / (uint32_t)h->gs;
-            b.cycle0 = (uint32_t)c0;
-            b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
-            b.ncyc = ncyc;
-            HIP_TRY(h, h->k->basis(b, h->G, h->stream));
-        }
-        a.s.V = h->V.p; a.s.ncyc = ncyc;
-        for (int s = 0; s < n; ++s) {
-            a.s.step0 = h->step;
-            a.cyc = (int)(h->step / (unsigned long long)d - c0);
-            a.col = (int)(h->step % (unsigned long long)d);
-            {
-                Timed t(h, 3);
-                HIP_TRY(h, mcmc_hip_launch_pl_walker(&a, pending ? 1 : 0, 1, h->stream));
-            }
+    const int rc = trial_pipeline(
+        h, n_steps, d, max_span_cycles(h, 64u << 20, dd, h->G), a,
+        [&](const StepSpan& sp) {
+            return shared_basis(h, h->V, h->G, h->cfg.walker_offset / (uint32_t)h->gs, sp.c0, sp.ncyc, dd, h->stream);
+        },
+        [&](int accept, int propose) -> int {
+            Timed t(h, 3);
+            HIP_TRY(h, mcmc_hip_launch_pl_walker(&a, accept, propose, h->stream));
+            return MCMC_HIP_OK;
+        },
+        [&]() -> int {   // (no callback here: only a launch can fail, and the call returns at once)
             if (unfused) {
                 {
                     Timed t(h, 4);
-                    const int rc = binned_residual(h, B.trial.p, B.delta.p, W);
-                    if (rc) return rc;
+                    const int rrc = binned_residual(h, B.trial.p, B.delta.p, W);
+                    if (rrc) return rrc;
                 }
                 Timed t(h, 5);
-                const int rc = binned_chi2(h, B.delta.p, B.psum.p, nullptr, W);
-                if (rc) return rc;
-            } else {
-                Timed t(h, 5);
-                mcmc::PlFusedArgs f{};
-                f.trial = B.trial.p; f.theta0 = B.theta0.p; f.bjs = B.bjs.p; f.es = B.es.p;
-                f.Astream = B.Afused.p; f.psum = B.psum.p;
-                std::memcpy(f.a_off, B.f_off, sizeof f.a_off);
-                std::memcpy(f.a_pairs, B.f_pairs, sizeof f.a_pairs);
-                f.W = W; f.KT = B.KT; f.n_lin = B.n_lin; f.np = (B.n_lin + 7) / 8; f.calib = B.calib;
-                f.n_tiles = (B.KT + 3) / 4; f.shift = B.f_shift; f.ng = B.f_ng; f.n_sets = W / 64;
-                HIP_TRY(h, mcmc_hip_launch_pl_fused(&f, h->stream));
+                return binned_chi2(h, B.delta.p, B.psum.p, nullptr, W);
             }
-            h->n_step_launches += 1;
-            pending = true;
-            h->step += 1;
-        }
-        left -= n;
-    }
-    if (pending) {
-        Timed t(h, 3);
-        HIP_TRY(h, mcmc_hip_launch_pl_walker(&a, 1, 0, h->stream));
-    }
+            Timed t(h, 5);
+            mcmc::PlFusedArgs f{};
+            f.trial = B.trial.p; f.theta0 = B.theta0.p; f.bjs = B.bjs.p; f.es = B.es.p;
+            f.Astream = B.Afused.p; f.psum = B.psum.p;
+            std::memcpy(f.a_off, B.f_off, sizeof f.a_off);
+            std::memcpy(f.a_pairs, B.f_pairs, sizeof f.a_pairs);
+            f.W = W; f.KT = B.KT; f.n_lin = B.n_lin; f.np = (B.n_lin + 7) / 8; f.calib = B.calib;
+            f.n_tiles = (B.KT + 3) / 4; f.shift = B.f_shift; f.ng = B.f_ng; f.n_sets = W / 64;
+            HIP_TRY(h, mcmc_hip_launch_pl_fused(&f, h->stream));
+            return MCMC_HIP_OK;
+        });
+    if (rc) return rc;
     take_noted_kernel(h, "n_bins", B.n_bins);
     return MCMC_HIP_OK;
 }
@@ -179,6 +194,26 @@ int step_binned(mcmc_hip_ctx* h, int n_steps)
 namespace {
 
 // ------------------------------------------------------------------ function target
+// what the engine was created with: checked by mcmc_hip_set_target_function and _functions
+int function_target_refusals(mcmc_hip_ctx* h)
+{
+    if (h->d > kMaxDimBig)
+        return fail(h, MCMC_HIP_ERR_ARG, "a function target serves d <= %d, got d=%d", kMaxDimBig, h->d);
+    if (h->cfg.flags & MCMC_HIP_FLAG_INCREMENTAL)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target is evaluated from scratch (incremental evaluation, "
+                    "MCMC_HIP_FLAG_INCREMENTAL, is not served)");
+    if (h->cfg.flags & MCMC_HIP_FLAG_OWN_BASIS)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target needs the shared basis (own basis, MCMC_HIP_FLAG_OWN_BASIS / "
+                    "shared_basis: False, is not served)");
+    if (h->cfg.emit_capacity > 0)
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a function target emits no rows on the device (emit_capacity > 0 / emit: chains is "
+                    "not served; use emit: snapshots)");
+    return MCMC_HIP_OK;
+}
+
 // what may be set before or after the target: checked by mcmc_hip_set_target_function and again by
 // every mcmc_hip_step
 int function_refusals(mcmc_hip_ctx* h)
@@ -216,64 +251,23 @@ int step_function(mcmc_hip_ctx* h, int n_steps)
     HIP_TRY(h, F.Ea.resize(W));
     HIP_TRY(h, F.ll_t.resize(W));
     const size_t dd = h->kb ? (size_t)mcmc::v_slab_big(d) : (size_t)mcmc::v_slab(d);
-    const int max_cyc = (int)std::max<size_t>(1, (64u << 20) / (sizeof(double) * dd * (size_t)h->G));
     mcmc::FnWalkerArgs a{};
-    a.s.x = h->x.p; a.s.logpost = h->logpost.p; a.s.logprior = h->logprior.p;
-    a.s.loglike = h->loglike.p; a.s.weight = h->weight_i.p; a.s.prior_rej = h->prej.p;
-    a.s.burn_left = h->burn.p; a.s.n_accept = h->nacc.p; a.s.stuck = h->stuck.p;
-    a.s.accept_total = h->acc_total.p;
-    a.s.cblock = h->cblock.p; a.s.W = W; a.s.group_size = h->gs; a.s.n_modes = 0;
-    a.s.norm_mask = h->norm_mask; a.s.walker0 = h->cfg.walker_offset;
-    a.s.key0 = (uint32_t)h->cfg.seed; a.s.key1 = (uint32_t)(h->cfg.seed >> 32);
-    a.s.uniform_logp = h->uniform_logp; a.s.temperature = h->cfg.temperature;
-    a.s.max_tries = h->cfg.max_tries; a.s.cps = d; a.s.slab = (int)dd;
+    a.s = step_args(h);
+    a.s.cps = d; a.s.slab = (int)dd;
     a.d = d; a.ld = h->kb ? mcmc::v_ld(d) : d;
-    for (int q = 0; q < 4; ++q) a.norm_mask4[q] = h->norm_mask4[q];
+    put_norm_mask4(h, a.norm_mask4);
     a.points = F.points.p; a.lp_t = F.lp_t.p; a.Ea = F.Ea.p; a.ll_t = F.ll_t.p; a.bad = F.bad.p;
-    int left = n_steps;
-    bool pending = false;   // a trial has been proposed and evaluated, not yet accepted / rejected
-    rc = MCMC_HIP_OK;
-    while (left > 0 && rc == MCMC_HIP_OK) {
-        const unsigned long long c0 = h->step / (unsigned long long)d;
-        const unsigned long long room = (c0 + (unsigned long long)max_cyc) * d - h->step;
-        const int n = (int)std::min<unsigned long long>((unsigned long long)left, room);
-        const int ncyc = (int)((h->step + (unsigned long long)n - 1) / d - c0 + 1);
-        {
-            Timed t(h, 1);
-            HIP_TRY(h, h->V.resize((size_t)h->G * ncyc * dd));
-            mcmc::BasisArgs b{};
-            b.T = h->dT.p; b.V = h->V.p;
-            b.group0 = h->cfg.walker_offset / (uint32_t)h->gs;
-            b.cycle0 = (uint32_t)c0;
-            b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
-            b.ncyc = ncyc;
-            if (h->kb) HIP_TRY(h, h->kb->basis(b, h->G, d, h->stream));
-            else HIP_TRY(h, h->k->basis(b, h->G, h->stream));
-        }
-        a.s.V = h->V.p; a.s.ncyc = ncyc;
-        for (int s = 0; s < n; ++s) {
-            a.s.step0 = h->step;
-            a.cyc = (int)(h->step / (unsigned long long)d - c0);
-            a.col = (int)(h->step % (unsigned long long)d);
-            {
-                Timed t(h, 0);
-                HIP_TRY(h, mcmc_hip_launch_fn_walker(&a, pending ? 1 : 0, 1, h->stream));
-            }
-            h->n_step_launches += 1;
-            // (the launch has settled the previous trial; a callback that fails drops THIS one:
-            // state and step counter stay as of the last completed step)
-            pending = false;
-            rc = function_call(h, W, F.points.p, F.ll_t.p);
-            if (rc) break;
-            pending = true;
-            h->step += 1;
-        }
-        left -= n;
-    }
-    if (pending) {
-        Timed t(h, 0);
-        HIP_TRY(h, mcmc_hip_launch_fn_walker(&a, 1, 0, h->stream));
-    }
+    rc = trial_pipeline(
+        h, n_steps, d, max_span_cycles(h, 64u << 20, dd, h->G), a,
+        [&](const StepSpan& sp) {
+            return shared_basis(h, h->V, h->G, h->cfg.walker_offset / (uint32_t)h->gs, sp.c0, sp.ncyc, dd, h->stream);
+        },
+        [&](int accept, int propose) -> int {
+            Timed t(h, 0);
+            HIP_TRY(h, mcmc_hip_launch_fn_walker(&a, accept, propose, h->stream));
+            return MCMC_HIP_OK;
+        },
+        [&] { return function_call(h, W, F.points.p, F.ll_t.p); });
     take_noted_kernel(h);
     return rc;
 }
@@ -380,20 +374,11 @@ int step_functions(mcmc_hip_ctx* h, int n_steps)
     HIP_TRY(h, F.ll_new.resize((size_t)nf * W));
     const size_t dd = blocked ? (size_t)mcmc::v_slab_cols(L, d)
                               : (h->kb ? (size_t)mcmc::v_slab_big(d) : (size_t)mcmc::v_slab(d));
-    const int max_cyc = (int)std::max<size_t>(1, (64u << 20) / (sizeof(double) * dd * (size_t)h->G));
     mcmc::FnBlockedArgs a{};
-    mcmc::StepArgs& s = a.w.s;
-    s.x = h->x.p; s.logpost = h->logpost.p; s.logprior = h->logprior.p;
-    s.loglike = h->loglike.p; s.weight = h->weight_i.p; s.prior_rej = h->prej.p;
-    s.burn_left = h->burn.p; s.n_accept = h->nacc.p; s.stuck = h->stuck.p;
-    s.accept_total = h->acc_total.p;
-    s.cblock = h->cblock.p; s.W = W; s.group_size = h->gs; s.n_modes = 0;
-    s.norm_mask = h->norm_mask; s.walker0 = h->cfg.walker_offset;
-    s.key0 = (uint32_t)h->cfg.seed; s.key1 = (uint32_t)(h->cfg.seed >> 32);
-    s.uniform_logp = h->uniform_logp; s.temperature = h->cfg.temperature;
-    s.max_tries = h->cfg.max_tries; s.cps = L; s.slab = (int)dd;
+    a.w.s = step_args(h);
+    a.w.s.cps = L; a.w.s.slab = (int)dd;
     a.w.d = d; a.w.ld = blocked ? d : (h->kb ? mcmc::v_ld(d) : d);
-    for (int q = 0; q < 4; ++q) a.w.norm_mask4[q] = h->norm_mask4[q];
+    put_norm_mask4(h, a.w.norm_mask4);
     a.w.points = F.points.p; a.w.lp_t = F.lp_t.p; a.w.Ea = F.Ea.p; a.w.ll_t = nullptr; a.w.bad = F.bad.p;
     a.n_fn = nf; a.inputs = F.dinputs.p; a.ll_c = F.ll_c.p;
     for (int c = 0, off = 0; c < nf; ++c) {
@@ -403,73 +388,39 @@ int step_functions(mcmc_hip_ctx* h, int n_steps)
         a.ll_new[c] = F.ll_new.p + (size_t)c * W;
         off += dc;
     }
-    const unsigned long long Lu = (unsigned long long)L;
-    int left = n_steps;
-    bool pending = false;   // a trial has been proposed and evaluated, not yet accepted / rejected
-    rc = MCMC_HIP_OK;
-    while (left > 0 && rc == MCMC_HIP_OK) {
-        const unsigned long long c0 = h->step / Lu;
-        const unsigned long long room = (c0 + (unsigned long long)max_cyc) * Lu - h->step;
-        const int n = (int)std::min<unsigned long long>((unsigned long long)left, room);
-        const int ncyc = (int)((h->step + (unsigned long long)n - 1) / Lu - c0 + 1);
-        {
-            Timed t(h, 1);
-            if (blocked) {
-                bool any_1d = false;
-                const int brc = blocked_basis(h, 0, c0, ncyc, L, dd, h->V, h->vflag, any_1d, nullptr, true);
-                if (brc) return brc;
-            } else {
-                HIP_TRY(h, h->V.resize((size_t)h->G * ncyc * dd));
-                mcmc::BasisArgs b{};
-                b.T = h->dT.p; b.V = h->V.p;
-                b.group0 = h->cfg.walker_offset / (uint32_t)h->gs;
-                b.cycle0 = (uint32_t)c0;
-                b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
-                b.ncyc = ncyc;
-                if (h->kb) HIP_TRY(h, h->kb->basis(b, h->G, d, h->stream));
-                else HIP_TRY(h, h->k->basis(b, h->G, h->stream));
+    rc = trial_pipeline(
+        h, n_steps, L, max_span_cycles(h, 64u << 20, dd, h->G), a.w,
+        [&](const StepSpan& sp) {
+            bool any_1d = false;
+            return blocked ? blocked_basis(h, 0, sp.c0, sp.ncyc, L, dd, h->V, h->vflag, any_1d, nullptr, true)
+                           : shared_basis(h, h->V, h->G, h->cfg.walker_offset / (uint32_t)h->gs, sp.c0, sp.ncyc,
+                                          dd, h->stream);
+        },
+        [&](int accept, int propose) -> int {
+            if (propose) {   // the functions due at the slot of this step
+                a.due = (1u << nf) - 1u;
+                a.oned = d == 1;
+                if (blocked) {
+                    // (the cycle index is kept modulo 2^32, as the direction kernels keep it)
+                    shared_schedule(h, (h->step / (unsigned long long)L) & 0xFFFFFFFFull, L);
+                    const int b = F.sched[a.w.col];
+                    a.due = 0;
+                    for (int c = 0; c < nf; ++c)
+                        if (last_block[c] >= b) a.due |= 1u << c;
+                    a.oned = h->blk_size[b] == 1;
+                }
             }
-        }
-        s.V = h->V.p; s.ncyc = ncyc;
-        for (int q = 0; q < n; ++q) {
-            const unsigned long long cycle = h->step / Lu;
-            const int slot = (int)(h->step % Lu);
-            unsigned due = (1u << nf) - 1u;
-            a.oned = d == 1;
-            if (blocked) {
-                // (the cycle index is kept modulo 2^32, as the direction kernels keep it)
-                shared_schedule(h, cycle & 0xFFFFFFFFull, L);
-                const int b = F.sched[slot];
-                due = 0;
-                for (int c = 0; c < nf; ++c)
-                    if (last_block[c] >= b) due |= 1u << c;
-                a.oned = h->blk_size[b] == 1;
-            }
-            s.step0 = h->step;
-            a.w.cyc = (int)(cycle - c0);
-            a.w.col = slot;
-            a.due = due;
-            {
-                Timed t(h, 0);
-                HIP_TRY(h, mcmc_hip_launch_fn_blocked_walker(&a, pending ? 1 : 0, 1, h->stream));
-            }
-            h->n_step_launches += 1;
-            // (the launch has settled the previous trial; a callback that fails drops THIS one:
-            // state and step counter stay as of the last completed step)
-            pending = false;
-            for (int c = 0; c < nf && rc == MCMC_HIP_OK; ++c)
-                if ((due >> c) & 1u) rc = functions_call_one(h, c, W, F.pts[c].p, F.ll_new.p + (size_t)c * W);
-            if (rc) break;
-            pending = true;
-            a.due_prev = due;
-            h->step += 1;
-        }
-        left -= n;
-    }
-    if (pending) {
-        Timed t(h, 0);
-        HIP_TRY(h, mcmc_hip_launch_fn_blocked_walker(&a, 1, 0, h->stream));
-    }
+            Timed t(h, 0);
+            HIP_TRY(h, mcmc_hip_launch_fn_blocked_walker(&a, accept, propose, h->stream));
+            return MCMC_HIP_OK;
+        },
+        [&] {
+            int erc = MCMC_HIP_OK;
+            for (int c = 0; c < nf && erc == MCMC_HIP_OK; ++c)
+                if ((a.due >> c) & 1u) erc = functions_call_one(h, c, W, F.pts[c].p, F.ll_new.p + (size_t)c * W);
+            if (erc == MCMC_HIP_OK) a.due_prev = a.due;
+            return erc;
+        });
     take_noted_kernel(h);
     return rc;
 }
@@ -488,21 +439,8 @@ int mcmc_hip_set_target_function(mcmc_hip_ctx* h, mcmc_hip_loglike_fn fn, void* 
 {
     if (!h) return MCMC_HIP_ERR_ARG;
     if (!fn) return fail(h, MCMC_HIP_ERR_ARG, "null argument");
-    if (h->d > kMaxDimBig)
-        return fail(h, MCMC_HIP_ERR_ARG, "a function target serves d <= %d, got d=%d", kMaxDimBig, h->d);
-    if (h->cfg.flags & MCMC_HIP_FLAG_INCREMENTAL)
-        return fail(h, MCMC_HIP_ERR_ARG,
-                    "a function target is evaluated from scratch (incremental evaluation, "
-                    "MCMC_HIP_FLAG_INCREMENTAL, is not served)");
-    if (h->cfg.flags & MCMC_HIP_FLAG_OWN_BASIS)
-        return fail(h, MCMC_HIP_ERR_ARG,
-                    "a function target needs the shared basis (own basis, MCMC_HIP_FLAG_OWN_BASIS / "
-                    "shared_basis: False, is not served)");
-    if (h->cfg.emit_capacity > 0)
-        return fail(h, MCMC_HIP_ERR_ARG,
-                    "a function target emits no rows on the device (emit_capacity > 0 / emit: chains is "
-                    "not served; use emit: snapshots)");
-    const int rc = function_refusals(h);
+    int rc = function_target_refusals(h);
+    if (rc == MCMC_HIP_OK) rc = function_refusals(h);
     if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, h->fnt.bad.resize(1));
@@ -528,21 +466,8 @@ int mcmc_hip_set_target_functions(mcmc_hip_ctx* h, int32_t n, const mcmc_hip_log
     if (n < 1 || n > mcmc::kFnMaxFunctions)
         return fail(h, MCMC_HIP_ERR_ARG, "a function target takes 1..%d functions, got %d",
                     mcmc::kFnMaxFunctions, n);
-    if (h->d > kMaxDimBig)
-        return fail(h, MCMC_HIP_ERR_ARG, "a function target serves d <= %d, got d=%d", kMaxDimBig, h->d);
-    if (h->cfg.flags & MCMC_HIP_FLAG_INCREMENTAL)
-        return fail(h, MCMC_HIP_ERR_ARG,
-                    "a function target is evaluated from scratch (incremental evaluation, "
-                    "MCMC_HIP_FLAG_INCREMENTAL, is not served)");
-    if (h->cfg.flags & MCMC_HIP_FLAG_OWN_BASIS)
-        return fail(h, MCMC_HIP_ERR_ARG,
-                    "a function target needs the shared basis (own basis, MCMC_HIP_FLAG_OWN_BASIS / "
-                    "shared_basis: False, is not served)");
-    if (h->cfg.emit_capacity > 0)
-        return fail(h, MCMC_HIP_ERR_ARG,
-                    "a function target emits no rows on the device (emit_capacity > 0 / emit: chains is "
-                    "not served; use emit: snapshots)");
-    int rc = functions_refusals(h);
+    int rc = function_target_refusals(h);
+    if (rc == MCMC_HIP_OK) rc = functions_refusals(h);
     if (rc) return rc;
     std::vector<char> fed(h->d, 0);
     std::vector<int> flat;

@@ -33,6 +33,7 @@
 #include "comm.h"
 #include "inc_choice.h"
 #include "readout.h"
+#include "step_span.h"
 
 MCMC_DECLARE_DIM(1) MCMC_DECLARE_DIM(2) MCMC_DECLARE_DIM(3) MCMC_DECLARE_DIM(4)
 MCMC_DECLARE_DIM(5) MCMC_DECLARE_DIM(6) MCMC_DECLARE_DIM(7) MCMC_DECLARE_DIM(8)
@@ -206,6 +207,8 @@ struct mcmc_hip_ctx {
     bool lazy_dirs = true;
     // step_inc_kernel: calls whose directions are formed together (MCMC_HIP_LOOKAHEAD, default 4)
     int lookahead = 4;
+    // bytes of directions a span of mcmc_hip_step may hold (MCMC_HIP_DIR_BUDGET_KIB; 0: the stepper's default)
+    size_t dir_budget = 0;
     // incremental_duo.hip (two lanes per walker): -1 = where the ensemble fills the chip with it
     // (kDuoMinWalkers), 0 = never, 1 = wherever the kernel serves the model (MCMC_HIP_DUO)
     int duo = -1;
@@ -563,6 +566,64 @@ inline void resolve_timing(mcmc_hip_ctx* h)
         h->pool.push_back(e.b);
     }
     h->pending.clear();
+}
+
+// ---- what every host stepper fills the same way ----
+// The ensemble's part of a step kernel's arguments.  The directions (V, vflag, own_basis), the cycle
+// geometry (cps, slab, ncyc), the steps (step0, n_steps), the emitted rows and their thinning, the
+// modes (n_modes, cnorm0) and periodic_mask are the stepper's own: kernels test several of them
+// against null or zero.
+inline mcmc::StepArgs step_args(const mcmc_hip_ctx* h)
+{
+    mcmc::StepArgs a{};
+    a.x = h->x.p; a.logpost = h->logpost.p; a.logprior = h->logprior.p;
+    a.loglike = h->loglike.p; a.weight = h->weight_i.p; a.prior_rej = h->prej.p;
+    a.burn_left = h->burn.p; a.n_accept = h->nacc.p; a.stuck = h->stuck.p;
+    a.accept_total = h->acc_total.p;
+    a.cblock = h->cblock.p; a.W = h->W; a.group_size = h->gs;
+    a.norm_mask = h->norm_mask; a.walker0 = h->cfg.walker_offset;
+    a.key0 = (uint32_t)h->cfg.seed; a.key1 = (uint32_t)(h->cfg.seed >> 32);
+    a.uniform_logp = h->uniform_logp; a.temperature = h->cfg.temperature;
+    a.max_tries = h->cfg.max_tries;
+    return a;
+}
+
+// one bit per dimension d <= 128 with a normal prior / that is periodic, into a kernel's arguments
+// (out: still zero)
+inline void put_norm_mask4(const mcmc_hip_ctx* h, uint32_t out[4])
+{
+    std::copy(h->norm_mask4, h->norm_mask4 + 4, out);
+}
+inline void periodic_mask4(const mcmc_hip_ctx* h, uint32_t out[4])
+{
+    for (int i = 0; i < h->d; ++i)
+        if (h->periodic[i]) out[i >> 5] |= 1u << (i & 31);
+}
+
+// cycles of directions per span (step_span.h): what the byte budget -- MCMC_HIP_DIR_BUDGET_KIB, or
+// the stepper's default -- holds of slabs of `slab` doubles for n_groups bases, at least `least`
+inline int max_span_cycles(const mcmc_hip_ctx* h, size_t default_bytes, size_t slab, int n_groups,
+                           size_t least = 1)
+{
+    const size_t bytes = h->dir_budget ? h->dir_budget : default_bytes;
+    return (int)std::max<size_t>(least, bytes / (sizeof(double) * slab * (size_t)n_groups));
+}
+
+// The Haar bases of cycles [c0, c0 + ncyc) of n_groups basis groups from global group group0 on,
+// into V ([n_groups][ncyc][slab]), on stream st (blocked directions: blocked_basis)
+inline int shared_basis(mcmc_hip_ctx* h, DevBuf<double>& V, int n_groups, uint32_t group0,
+                        unsigned long long c0, int ncyc, size_t slab, hipStream_t st)
+{
+    HIP_TRY(h, V.resize((size_t)n_groups * ncyc * slab));
+    mcmc::BasisArgs b{};
+    b.T = h->dT.p; b.V = V.p;
+    b.group0 = group0;
+    b.cycle0 = (uint32_t)c0;
+    b.key0 = (uint32_t)h->cfg.seed; b.key1 = (uint32_t)(h->cfg.seed >> 32);
+    b.ncyc = ncyc;
+    if (h->kb) HIP_TRY(h, h->kb->basis(b, n_groups, h->d, st));
+    else HIP_TRY(h, h->k->basis(b, n_groups, st));
+    return MCMC_HIP_OK;
 }
 
 // ---- what one host translation unit defines for the others ----
