@@ -126,6 +126,7 @@ def translation_units(dims, big=True):
             ("function_kernels.hip", "function", []),   # function targets (the user's batched device function)
             ("stretch_kernels.hip", "stretch", []),     # the stretch move on a function target
             ("ensemble_move_kernels.hip", "ensemble_move", []),   # mixtures of stretch, DE and snooker moves
+            ("math_probe_kernels.hip", "math_probe", []),   # test entry: det_math.h function by function
             ("host_linalg.cpp", "host_linalg", []),  # the host side: the C ABI, split by job
             ("capi.hip", "capi", []),
             ("capi_targets.hip", "capi_targets", []),
@@ -138,7 +139,8 @@ def translation_units(dims, big=True):
             ("capi_bestfit.hip", "capi_bestfit", []),
             ("capi_evidence.hip", "capi_evidence", []),
             ("capi_derived.hip", "capi_derived", []),
-            ("capi_importance.hip", "capi_importance", [])]
+            ("capi_importance.hip", "capi_importance", []),
+            ("capi_math_probe.hip", "capi_math_probe", [])]
     return tus
 
 

@@ -219,6 +219,7 @@ SYMBOLS = [
     ("mcmc_hip_incremental_carries_modes", C.c_int, [_H]),
     ("mcmc_hip_incremental_carries_periodic", C.c_int, [_H]),
     ("mcmc_hip_accept_estimate_error", C.c_int, [c_double_p, C.POINTER(C.c_uint32)]),
+    ("mcmc_hip_math_probe", C.c_int, [C.c_int32, c_uint64_p, C.c_uint64, C.c_uint64, C.c_int64, c_uint64_p]),
     ("mcmc_hip_get_mode_logdensities", C.c_int, [_H, c_double_p]),
     ("mcmc_hip_set_mode_logdensities", C.c_int, [_H, c_double_p]),
     ("mcmc_hip_kernel_times", C.c_int, [_H, c_double_p, c_int64_p, C.c_int32]),

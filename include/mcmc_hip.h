@@ -788,6 +788,27 @@ MCMC_HIP_API int mcmc_hip_incremental_carries_periodic(const mcmc_hip_ctx* h);
  * over ka = 1 .. 2^28 - 1 on the current device (milliseconds): the largest |ea_f - Ea| and the ka
  * that attains it. */
 MCMC_HIP_API int mcmc_hip_accept_estimate_error(double* max_err, uint32_t* ka_at_max);
+/* test entry: one function of the device math (det_math.h) applied to n <= 2^24 elements on the
+ * current device, raw 64-bit words in and out, for the bit-for-bit comparison with the oracle on whole
+ * argument domains (tests/test_gpu_math_domains.py).  Words per element, in -> out (a double is its
+ * bit pattern, a 32-bit integer sits in the low half of its word):
+ *   PHILOX   k0 k1 c0 c1 c2 c3 -> w0 w1 w2 w3        U52        k -> u
+ *   DLOG, DEXP, DLOG_TAB, DEXP_TAB, SQRT_MIDRANGE, SQRT   x -> f(x)
+ *   SINCOS2PI  k -> sin cos                          NEG_LOG_SHORT_25 / _29   n -> -log(n 2^-b)
+ *   DIV_BY   a w R -> div_by(a, w, R)                 DIV        a w -> a / w
+ * args[n * words in] on the host, or NULL for a function of one word: element i then has the argument
+ * first + i * stride (the integer domains need no upload).  out[n * words out] on the host.
+ * MCMC_HIP_ERR_ARG for an unknown function, a null `out`, NULL args where a function takes more than
+ * one word, or n outside [0, 2^24]. */
+enum {
+    MCMC_HIP_PROBE_PHILOX = 0, MCMC_HIP_PROBE_U52 = 1, MCMC_HIP_PROBE_DLOG = 2, MCMC_HIP_PROBE_DEXP = 3,
+    MCMC_HIP_PROBE_SINCOS2PI = 4, MCMC_HIP_PROBE_NEG_LOG_SHORT_25 = 5, MCMC_HIP_PROBE_NEG_LOG_SHORT_29 = 6,
+    MCMC_HIP_PROBE_DLOG_TAB = 7, MCMC_HIP_PROBE_DEXP_TAB = 8, MCMC_HIP_PROBE_SQRT_MIDRANGE = 9,
+    MCMC_HIP_PROBE_SQRT = 10, MCMC_HIP_PROBE_DIV_BY = 11, MCMC_HIP_PROBE_DIV = 12
+};
+#define MCMC_HIP_PROBE_MAX_ELEMENTS (1 << 24)
+MCMC_HIP_API int mcmc_hip_math_probe(int32_t fn, const uint64_t* args, uint64_t first, uint64_t stride,
+                                     int64_t n, uint64_t* out);
 MCMC_HIP_API int mcmc_hip_get_mode_logdensities(mcmc_hip_ctx* h, double* a);
 MCMC_HIP_API int mcmc_hip_set_mode_logdensities(mcmc_hip_ctx* h, const double* a);
 

@@ -16,6 +16,7 @@ BUILD = os.path.join(HERE, "_build")
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
 c_int64_p = C.POINTER(C.c_int64)
+c_uint64_p = C.POINTER(C.c_uint64)
 
 
 def build():
@@ -137,6 +138,9 @@ def lib():
         L.orc_anchor_modes.argtypes = [C.POINTER(_Problem), C.POINTER(_State), C.c_int]
         L.orc_anchor_modes.restype = None
         L.orc_max_threads.restype = C.c_int
+        L.orc_math_bulk.restype = C.c_int
+        L.orc_math_bulk.argtypes = [C.c_int, c_uint64_p, C.c_uint64, C.c_uint64, C.c_int64, c_uint64_p,
+                                    C.c_int]
         L.orc_binned_chi2_of_delta.restype = C.c_double
         L.orc_binned_chi2_of_delta.argtypes = [C.POINTER(_Binned), c_double_p]
         L.orc_binned_delta.argtypes = [C.POINTER(_Binned), c_double_p, c_double_p]
@@ -204,6 +208,36 @@ def sincos2pi(k):
     s, c = C.c_double(), C.c_double()
     lib().orc_sincos2pi(int(k), C.byref(s), C.byref(c))
     return s.value, c.value
+
+
+# The math in bulk (orc_math_bulk): the ids and the words per element, in and out, are those of
+# mcmc_hip_math_probe (include/mcmc_hip.h)
+MATH_FUNCTIONS = {
+    "philox": (0, 6, 4), "u52": (1, 1, 1), "dlog": (2, 1, 1), "dexp": (3, 1, 1), "sincos2pi": (4, 1, 2),
+    "neg_log_short_25": (5, 1, 1), "neg_log_short_29": (6, 1, 1), "dlog_tab": (7, 1, 1),
+    "dexp_tab": (8, 1, 1), "sqrt_midrange": (9, 1, 1), "sqrt": (10, 1, 1), "div_by": (11, 3, 1),
+    "div": (12, 2, 1),
+    "tail_of_k": (13, 2, 1),   # the oracle alone: (k, b) -> fma(b, ln 2, -dlog(u52(k))), pair_tail's value
+}
+
+
+def math_bulk(name, args=None, first=0, stride=1, n=None, n_threads=1):
+    """The oracle's `name` on an array: args[n, words in] as uint64 words (a double is its bit
+    pattern), or generated arguments first + i * stride, i < n.  Returns uint64 [n, words out]
+    (1-D for one word out)."""
+    fn, wi, wo = MATH_FUNCTIONS[name]
+    if args is not None:
+        args = np.ascontiguousarray(args, dtype=np.uint64).reshape(-1, wi)
+        n = len(args)
+    elif wi != 1 or n is None:
+        raise ValueError(f"{name}: generated arguments need one word per element and a count")
+    out = np.empty((n, wo), dtype=np.uint64)
+    rc = lib().orc_math_bulk(fn, None if args is None else args.ctypes.data_as(c_uint64_p),
+                             int(first), int(stride), int(n), out.ctypes.data_as(c_uint64_p),
+                             int(n_threads))
+    if rc != 0:
+        raise ValueError(f"orc_math_bulk({name}) refused its arguments")
+    return out[:, 0] if wo == 1 else out
 
 
 def haar_from_normals(d, z):

@@ -98,7 +98,10 @@ double orc_dlog(double x)
  * table step is exact.  n = m 2^e, m in [1/2, 1); j = top seven fraction bits of m;
  * f = fma(m, RC_j, -1) is EXACT (29 + 24 bits) with |f| <= 2^-8; log1p(f) by its Taylor
  * polynomial to f^6 (next term < 2^-58); result = (b - e) ln 2 + log(RC_j) - log1p(f).
- * Table: oracle/short_log_table.h (tools/make_short_log_table.py).  Absolute error < 3e-16. */
+ * Table: oracle/short_log_table.h (tools/make_short_log_table.py).  Error <= 4e-16 max(1, t) of the
+ * result t -- a RELATIVE bound: the absolute error reaches 3.1e-15 near t = 17 (n = 1, b = 25) --,
+ * measured against an 80-bit logarithm over every argument of b = 25 and every 16th of b = 29: at most
+ * 0.64 of it (tests/test_math_domains_host.py). */
 #include "short_log_table.h"
 static const double short_log_table[SHORT_LOG_TABLE_SIZE][2] = SHORT_LOG_TABLE;
 double orc_neg_log_short(uint32_t n, int32_t b)
@@ -120,7 +123,10 @@ double orc_neg_log_short(uint32_t n, int32_t b)
  *   log x, x > 0 normal: x = m 2^e, m in [1/2, 1); j = top seven fraction bits of m;
  *     f = fma(m, RC_j, -1), |f| <= 2^-8 (one rounding: 2^-61 absolute); log x =
  *     log1p(f) - fma(-e, ln 2, LRC_j), log1p by its Taylor polynomial to f^6 (as orc_neg_log_short).
- *     Absolute error < 3e-16 + 1 ulp: what a log-sum-exp of terms in [w_max, 1] needs.
+ *     Absolute error < 3e-16 + 1 ulp for 2^-16 <= x < 2^16: what a log-sum-exp of terms in [w_max, 1]
+ *     needs.  Further out the two roundings at the size of the result (the fma and the difference) add
+ *     to the table's error: over the whole normal range < 3e-16 + 1.5 ulp, worst measured 1.41 ulp at
+ *     x = 0x1.97fffffffffffp-370 (tests/test_math_domains_host.py).
  *   exp x, x >= -708 (else 0): k = rint(x 64 / ln 2), r = x - k ln 2 / 64 (two fmas, |r| <= 0.0055),
  *     exp r - 1 = r (1 + r (1/2 + r (1/6 + r (1/24 + r / 120)))) (next term 3e-17), T_j = 2^(j / 64)
  *     with j = k mod 64 from the table, result fma(T_j, p, T_j) 2^(k div 64).  Within 2 ulp. */
@@ -1484,6 +1490,76 @@ void orc_moments(int d, int W, int gs, const double* x, const double* shift,
             }
     }
     free(Sg);
+}
+
+/* ------------------------------------------------------------------ the math in bulk */
+/* Array forms of the scalar functions above, raw 64-bit words in and out, for the bit-for-bit
+ * comparison with the device's probe (mcmc_hip_math_probe, same ids and word layout) on whole
+ * argument domains: out[i * words out ..] = fn(in[i * words in ..]) for i < n; in == NULL (functions
+ * of one word): the argument of element i is first + i * stride.  SQRT_MIDRANGE and SQRT are sqrt(),
+ * DIV_BY and DIV are `/` (the specification of both).  Returns 0, or -1 for an unknown fn / null. */
+enum { BULK_PHILOX, BULK_U52, BULK_DLOG, BULK_DEXP, BULK_SINCOS2PI, BULK_NEG_LOG_SHORT_25,
+       BULK_NEG_LOG_SHORT_29, BULK_DLOG_TAB, BULK_DEXP_TAB, BULK_SQRT_MIDRANGE, BULK_SQRT, BULK_DIV_BY,
+       BULK_DIV,
+       /* the oracle alone (it builds a grid): (k, b) -> b ln 2 - log u52(k), the redrawn tail of
+        * pair_tail below without its Philox block */
+       BULK_TAIL_OF_K, BULK_N };
+static const int bulk_words_in[BULK_N] = {6, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 3, 2, 2};
+static const int bulk_words_out[BULK_N] = {4, 1, 1, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+
+static inline void bulk_one(int fn, const uint64_t* a, uint64_t* r)
+{
+    switch (fn) {
+    case BULK_PHILOX: {
+        uint32_t w[4];
+        philox4x32_10((uint32_t)a[0], (uint32_t)a[1], (uint32_t)a[2], (uint32_t)a[3], (uint32_t)a[4],
+                      (uint32_t)a[5], w);
+        for (int j = 0; j < 4; ++j) r[j] = w[j];
+        break;
+    }
+    case BULK_U52: r[0] = d2bits(u52(a[0])); break;
+    case BULK_DLOG: r[0] = d2bits(orc_dlog(bits2d(a[0]))); break;
+    case BULK_DEXP: r[0] = d2bits(orc_dexp(bits2d(a[0]))); break;
+    case BULK_SINCOS2PI: {
+        double s, c;
+        orc_sincos2pi(a[0], &s, &c);
+        r[0] = d2bits(s); r[1] = d2bits(c);
+        break;
+    }
+    case BULK_NEG_LOG_SHORT_25: r[0] = d2bits(orc_neg_log_short((uint32_t)a[0], 25)); break;
+    case BULK_NEG_LOG_SHORT_29: r[0] = d2bits(orc_neg_log_short((uint32_t)a[0], 29)); break;
+    case BULK_DLOG_TAB: r[0] = d2bits(orc_dlog_tab(bits2d(a[0]))); break;
+    case BULK_DEXP_TAB: r[0] = d2bits(orc_dexp_tab(bits2d(a[0]))); break;
+    case BULK_SQRT_MIDRANGE:
+    case BULK_SQRT: r[0] = d2bits(sqrt(bits2d(a[0]))); break;
+    case BULK_DIV_BY:
+    case BULK_DIV: r[0] = d2bits(bits2d(a[0]) / bits2d(a[1])); break;
+    case BULK_TAIL_OF_K:
+        r[0] = d2bits(fma((double)a[1], 6.93147180559945286227e-01, -orc_dlog(u52(a[0]))));
+        break;
+    default: break;
+    }
+}
+
+int orc_math_bulk(int fn, const uint64_t* in, uint64_t first, uint64_t stride, int64_t n, uint64_t* out,
+                  int n_threads)
+{
+    if (fn < 0 || fn >= BULK_N || !out || n < 0) return -1;
+    const int wi = bulk_words_in[fn], wo = bulk_words_out[fn];
+    if (!in && wi != 1) return -1;
+#ifdef _OPENMP
+    if (n_threads > 0) omp_set_num_threads(n_threads);
+#pragma omp parallel for schedule(static)
+#else
+    (void)n_threads;
+#endif
+    for (int64_t i = 0; i < n; ++i) {
+        uint64_t a[6];
+        if (in) for (int j = 0; j < wi; ++j) a[j] = in[i * wi + j];
+        else a[0] = first + (uint64_t)i * stride;
+        bulk_one(fn, a, out + i * wo);
+    }
+    return 0;
 }
 
 int orc_max_threads(void)
