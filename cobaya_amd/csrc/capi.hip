@@ -112,14 +112,12 @@ int upload_constants(mcmc_hip_ctx* h)
 
 namespace {
 
+// (at set-target time: step_kernel's LDS at the widest workgroup, one parameter block)
 int lds_check(mcmc_hip_ctx* h)
 {
-    const ConstLayout cl{h->d, h->K};
-    (void)cl;
     if (h->kb || h->huge) return MCMC_HIP_OK;  // the big / huge step kernels' LDS does not depend on K
-    const size_t lds = sizeof(double) * ((h->K > 1 ? (size_t)h->K * 256 : 0) +
-                                         2 * (size_t)(256 / h->gs) * mcmc::v_slab(h->d));
-    if (lds > 160 * 1024)
+    const size_t lds = mcmc::step_lds_bytes(h->K, 256, h->gs, mcmc::v_slab(h->d));
+    if (lds > mcmc::kLdsMax)
         return fail(h, MCMC_HIP_ERR_ARG,
                     "the step kernel needs %zu bytes of LDS per workgroup (> 160 KiB): fewer "
                     "mixture modes or a smaller group_size are required", lds);
@@ -910,6 +908,57 @@ int mcmc_hip_set_full_state(mcmc_hip_ctx* h, const double* x, const double* logp
     return MCMC_HIP_OK;
 }
 
+namespace {
+// the model, ensemble and build of an engine, as scratch_choose is asked about them (no launch's
+// one-parameter column yet)
+mcmc::ScratchShape scratch_shape_of(mcmc_hip_ctx* h)
+{
+    mcmc::ScratchShape s;
+    const bool drag = h->drag_last_slow >= 0;
+    s.d = h->d; s.K = h->K; s.W = h->W; s.group_size = h->gs;
+    s.any_normal = h->norm_mask4[0] || h->norm_mask4[1] || h->norm_mask4[2] || h->norm_mask4[3];
+    s.any_periodic = h->any_periodic;
+    s.emit = h->cfg.emit_capacity > 0; s.emit_thin = h->emit_thin > 1;
+    s.unit_t = h->cfg.temperature == 1.0;
+    s.own_basis = h->own_basis; s.blocked = h->blocked;
+    s.n_drag = drag ? h->drag_steps : 0;
+    // steps (= direction columns) per cycle
+    s.cps = block_slots(h, drag ? 1 : 0);
+    s.cps_f = drag ? block_slots(h, 2) : 0;
+    s.lane_compiled = h->k != nullptr; s.big_dp = h->kb ? h->kb->dp : 0; s.pair_compiled = h->kp != nullptr;
+    return s;
+}
+}  // namespace
+
+int mcmc_hip_scratch_choice(const mcmc_hip_scratch_shape* shape, mcmc_hip_scratch_answer* out)
+{
+    if (!shape || !out) return MCMC_HIP_ERR_ARG;
+    mcmc::ScratchShape s;
+    s.d = shape->d; s.K = shape->n_modes; s.W = shape->n_walkers; s.group_size = shape->group_size;
+    s.any_normal = shape->any_normal != 0; s.any_periodic = shape->any_periodic != 0;
+    s.emit = shape->emit != 0; s.emit_thin = shape->emit_thin != 0; s.unit_t = shape->unit_t != 0;
+    s.own_basis = shape->own_basis != 0; s.blocked = shape->blocked != 0; s.n_drag = shape->n_drag;
+    s.cps = shape->cps > 0 ? shape->cps : shape->d; s.cps_f = shape->cps_f;
+    s.has_1d_column = shape->has_1d_column != 0;
+    // what this library was built with, as mcmc_hip_create finds it
+    s.lane_compiled = kernels_for_dim(s.d) != nullptr;
+    const BigKernels* kb = s.lane_compiled ? nullptr : big_for_dim(s.d);
+    s.big_dp = kb ? kb->dp : 0;
+    s.pair_compiled = kb && !getenv("MCMC_HIP_NO_PAIR_BIG") && pair_for_dim(s.d) != nullptr;
+    const mcmc::ScratchChoice c = mcmc::scratch_choose(s);
+    static_assert(mcmc::kScratchStep == MCMC_HIP_SCRATCH_STEP && mcmc::kScratchStepOwn == MCMC_HIP_SCRATCH_STEP_OWN &&
+                  mcmc::kScratchPair == MCMC_HIP_SCRATCH_PAIR && mcmc::kScratchMfma == MCMC_HIP_SCRATCH_MFMA &&
+                  mcmc::kScratchBigReg == MCMC_HIP_SCRATCH_BIG_REG && mcmc::kScratchGeneral == MCMC_HIP_SCRATCH_GENERAL &&
+                  mcmc::kScratchDrag == MCMC_HIP_SCRATCH_DRAG && mcmc::kScratchGeneralDrag == MCMC_HIP_SCRATCH_GENERAL_DRAG,
+                  "mcmc_hip.h names the families of scratch_choice.h");
+    out->family = c.family; out->reason = c.reason;
+    out->multi = c.multi; out->general = c.general; out->unit_t = c.unit_t; out->normp = c.normp;
+    out->unit = c.unit; out->walkers_per_wg = c.walkers_per_wg; out->threads = c.threads; out->grid = c.grid;
+    out->lds_bytes = (int32_t)c.lds_bytes; out->lds_attr = (int32_t)c.lds_attr;
+    out->v_ld = c.v_ld; out->slab = c.slab; out->slab_f = c.slab_f;
+    return MCMC_HIP_OK;
+}
+
 int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
 {
     if (!h) return MCMC_HIP_ERR_ARG;
@@ -928,55 +977,44 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
     if (h->fnt.on) return h->fnt.n_fn > 0 ? step_functions(h, n_steps) : step_function(h, n_steps);
     if (h->incremental && h->huge) return step_huge(h, n_steps);
     if (h->incremental) return step_incremental(h, n_steps);
-    if (h->emit_thin > 1)
+    // every trial from scratch: which kernel serves the shape and how it is launched is
+    // scratch_choose's (scratch_choice.h); only a one-parameter column can differ from span to span
+    mcmc::ScratchShape shape = scratch_shape_of(h);
+    const mcmc::ScratchChoice whole = mcmc::scratch_choose(shape);
+    switch (whole.reason) {
+    case mcmc::kScratchServed: break;
+    case mcmc::kScratchEmitThin:
         return fail(h, MCMC_HIP_ERR_ARG, "emit_thin needs incremental evaluation; thin on the host");
-    const bool drag = h->drag_last_slow >= 0;
-    // steps (= direction columns) per cycle, doubles per (group, cycle) slab of directions
-    const int Lc = block_slots(h, drag ? 1 : 0);
-    // (parameter blocks and dragging at d > 32: blocked directions in the d <= 32 layout --
-    // column stride d -- read by the general kernels)
-    const bool big_blocked = h->kb && (h->blocked || drag);
-    const size_t dd = (h->kb && !big_blocked) ? (size_t)mcmc::v_slab_big(h->d)
-                                              : (size_t)mcmc::v_slab_cols(Lc, h->d);
-    const bool big_norm = h->norm_mask4[0] || h->norm_mask4[1] || h->norm_mask4[2] || h->norm_mask4[3];
-    // d > 32: what the matrix-core / two-wave / column-sweep kernels leave out (mixtures, `one`,
-    // periodic parameters, emitted rows; odd ensemble sizes with normal priors or d > 112) runs
-    // on the general kernel
-    if (h->own_basis && (h->blocked || drag))
+    case mcmc::kScratchOwnBlocks:
         return fail(h, MCMC_HIP_ERR_ARG,
                     "shared_basis: False serves a single parameter block without dragging");
-    // (round 6: own bases at d <= 32 run on the tuned step kernel, step_kernel<.., OWN>)
-    const bool general_big =
-        (h->own_basis && h->kb) || big_blocked ||
-        (h->kb && (h->K != 1 || h->any_periodic || h->cfg.emit_capacity > 0 ||
-                   (h->W % 256 != 0 && (big_norm || h->d > 112))));
+    case mcmc::kScratchGeneralLds:
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "d=%d with %d modes does not fit the general d > 32 kernel (LDS)", h->d, h->K);
+    case mcmc::kScratchCycleLds:
+        return fail(h, MCMC_HIP_ERR_ARG,
+                    "a cycle of %d steps needs %zu KiB of LDS per group: use group_size 256 or "
+                    "smaller oversampling factors", shape.cps, (size_t)whole.slab * sizeof(double) / 1024);
+    default:   // (kScratchBadShape, kScratchSweepSize, kScratchSweepNormal: what the launchers answered)
+        HIP_TRY(h, hipErrorInvalidValue);
+    }
+    const bool drag = shape.n_drag > 0;
+    const int Lc = shape.cps, Lf = shape.cps_f;
+    const size_t dd = (size_t)whole.slab, ddf = (size_t)whole.slab_f;
     // basis "groups": the walker groups, or every walker on its own
     const int n_basis = h->own_basis ? h->W : h->G;
     const uint32_t basis0 = h->own_basis ? h->cfg.walker_offset
                                          : h->cfg.walker_offset / (uint32_t)h->gs;
-    if (general_big && sizeof(double) * 64 * (size_t)(2 * h->d + std::max(1, h->K)) > (160u << 10))
-        return fail(h, MCMC_HIP_ERR_ARG,
-                    "d=%d with %d modes does not fit the general d > 32 kernel (LDS)", h->d, h->K);
-    // two slabs per group of a workgroup (workgroups are 256, 128 or 64 walkers wide)
-    const int wg = (h->W % 256 == 0) ? 256 : (h->W % 128 == 0) ? 128 : 64;
-    if (!h->kb && !drag && !h->own_basis &&
-        (2 * (size_t)std::max(1, wg / h->gs) * dd + (h->K > 1 ? (size_t)h->K * wg : 0)) * sizeof(double) >
-            (160u << 10))
-        return fail(h, MCMC_HIP_ERR_ARG,
-                    "a cycle of %d steps needs %zu KiB of LDS per group: use group_size 256 or "
-                    "smaller oversampling factors", Lc, dd * sizeof(double) / 1024);
     // directions buffer: at most ~256 MiB of cycles per launch
     const int max_cyc = max_span_cycles(h, 256u << 20, dd, n_basis);
     // dragging: the fast blocks' directions, n_drag columns per step
-    const int Lf = drag ? block_slots(h, 2) : 0;
-    const size_t ddf = drag ? (size_t)mcmc::v_slab_cols(Lf, h->d) : 0;
     const unsigned long long nd = (unsigned long long)h->drag_steps;
     const int max_cyc_f = drag ? max_span_cycles(h, 256u << 20, ddf, h->G, 2) : 0;
     // the arguments of the general d > 32 kernels around those of a launch
-    auto general_args = [h](const mcmc::StepArgs& a, int ld, int own_basis) {
+    auto general_args = [h, &whole](const mcmc::StepArgs& a) {
         mcmc::GeneralStepArgs g{};
         g.s = a;
-        g.Lrow = h->dLrow.p; g.d = h->d; g.ld = ld; g.own_basis = own_basis;
+        g.Lrow = h->dLrow.p; g.d = h->d; g.ld = whole.v_ld; g.own_basis = h->own_basis ? 1 : 0;
         put_norm_mask4(h, g.norm_mask4);
         periodic_mask4(h, g.periodic_mask4);
         return g;
@@ -1006,7 +1044,9 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
             a.cps = Lc; a.slab = (int)dd;
             a.vflag = any_1d ? h->vflag.p : nullptr;
             a.own_basis = (h->own_basis && !h->kb) ? 1 : 0;
-            if (drag) {
+            shape.has_1d_column = any_1d;
+            const mcmc::ScratchChoice c = mcmc::scratch_choose(shape);
+            if (c.family == mcmc::kScratchDrag || c.family == mcmc::kScratchGeneralDrag) {
                 mcmc::DragArgs g{};
                 g.s = a;
                 const unsigned long long f0 = h->step * nd;
@@ -1021,28 +1061,27 @@ int mcmc_hip_step(mcmc_hip_ctx* h, int32_t n_steps)
                 if (rc != MCMC_HIP_OK) return rc;
                 g.Vf = h->Vf.p;
                 g.vflag_f = any_1d_f ? h->vflag_f.p : nullptr;
-                if (h->kb) {   // 32 < d <= 128: the general dragging kernel
+                if (c.family == mcmc::kScratchGeneralDrag) {   // 32 < d <= 128
                     mcmc::GeneralDragArgs q{};
-                    q.g = general_args(a, h->d, 0);
+                    q.g = general_args(a);
                     HIP_TRY(h, h->drag_cs.resize((size_t)h->d * h->W));
                     q.Vf = g.Vf; q.vflag_f = g.vflag_f; q.cs = h->drag_cs.p;
                     q.cyc0 = g.cyc0; q.cyc0_f = g.cyc0_f; q.cps_f = g.cps_f; q.slab_f = g.slab_f;
                     q.ncyc_f = g.ncyc_f; q.n_drag = g.n_drag;
-                    HIP_TRY(h, mcmc_hip_launch_general_drag(&q, h->stream));
+                    HIP_TRY(h, mcmc_hip_launch_general_drag(&q, &c, h->stream));
                 } else {
-                    HIP_TRY(h, h->k->drag(g, h->stream));
+                    HIP_TRY(h, h->k->drag(g, c, h->stream));
                 }
-            } else if (general_big) {
-                const mcmc::GeneralStepArgs g = general_args(
-                    a, (h->kb && !big_blocked) ? mcmc::v_ld(h->d) : h->d, h->own_basis ? 1 : 0);
-                HIP_TRY(h, mcmc_hip_launch_general_step(&g, h->stream));
+            } else if (c.family == mcmc::kScratchGeneral) {
+                const mcmc::GeneralStepArgs g = general_args(a);
+                HIP_TRY(h, mcmc_hip_launch_general_step(&g, &c, h->stream));
             } else if (h->kb) {
                 a.norm_mask = h->norm_mask4[0];
                 a.norm_mask_hi = h->norm_mask4[1];
-                if (h->kp && h->kp->fits(a)) HIP_TRY(h, h->kp->step(a, h->stream));
-                else HIP_TRY(h, h->kb->step(a, h->dLcol.p, h->d, h->norm_mask4, h->stream));
+                if (c.family == mcmc::kScratchPair) HIP_TRY(h, h->kp(&a, &c, h->stream));
+                else HIP_TRY(h, h->kb->step(a, h->dLcol.p, h->d, h->norm_mask4, c, h->stream));
             }
-            else HIP_TRY(h, h->k->step(a, h->gs, h->stream));
+            else HIP_TRY(h, h->k->step(a, c, h->stream));
             h->n_step_launches += 1;
             take_noted_kernel(h);
         }

@@ -69,17 +69,17 @@ inline const BigKernels* big_for_dim(int d)
                                    mcmc_hip_big_72,  mcmc_hip_big_80,  mcmc_hip_big_88,
                                    mcmc_hip_big_96,  mcmc_hip_big_100, mcmc_hip_big_112,
                                    mcmc_hip_big_120, mcmc_hip_big_128};
+    static_assert(sizeof(table) / sizeof(table[0]) == sizeof(mcmc::kBigDps) / sizeof(mcmc::kBigDps[0]), "");
     if (d <= mcmc::kMaxDimLane || d > kMaxDimBig) return nullptr;
     for (getter g : table)
         if (g != nullptr && g()->dp >= d) return g();
     return nullptr;
 }
 
-// the two-wave step kernel of a dimension 32 < d <= kMaxDimPair, if compiled
-inline const mcmc::PairKernels* pair_for_dim(int d)
+// the launcher of the two-wave step kernel of a dimension 32 < d <= kMaxDimPair, if compiled
+inline mcmc::PairStep pair_for_dim(int d)
 {
-    typedef const mcmc::PairKernels* (*getter)();
-    static const getter table[] = {mcmc_hip_pair_33, mcmc_hip_pair_34, mcmc_hip_pair_35,
+    static const mcmc::PairStep table[] = {mcmc_hip_pair_33, mcmc_hip_pair_34, mcmc_hip_pair_35,
                                    mcmc_hip_pair_36, mcmc_hip_pair_37, mcmc_hip_pair_38,
                                    mcmc_hip_pair_39, mcmc_hip_pair_40, mcmc_hip_pair_41,
                                    mcmc_hip_pair_42, mcmc_hip_pair_43, mcmc_hip_pair_44,
@@ -89,8 +89,7 @@ inline const mcmc::PairKernels* pair_for_dim(int d)
                                    mcmc_hip_pair_54, mcmc_hip_pair_55, mcmc_hip_pair_56};
     static_assert(sizeof(table) / sizeof(table[0]) == mcmc::kMaxDimPair - mcmc::kMaxDimLane, "");
     if (d <= mcmc::kMaxDimLane || d > mcmc::kMaxDimPair) return nullptr;
-    const getter g = table[d - mcmc::kMaxDimLane - 1];
-    return g != nullptr ? g() : nullptr;
+    return table[d - mcmc::kMaxDimLane - 1];
 }
 
 inline const DimKernels* kernels_for_dim(int d)
@@ -136,7 +135,7 @@ struct mcmc_hip_ctx {
     mcmc_hip_config cfg{};
     const DimKernels* k = nullptr;    // d <= 32: lane-per-walker kernels of that dimension
     const BigKernels* kb = nullptr;   // 32 < d <= 128: column-sweep / matrix-core kernels
-    const mcmc::PairKernels* kp = nullptr;   // 32 < d <= 56: the two-wave step kernel, if it fits
+    mcmc::PairStep kp = nullptr;   // 32 < d <= 56: the two-wave step kernel, if compiled
     bool huge = false;                // 128 < d <= 256: huge_kernels.hip (incremental, one block, K <= 4)
     // huge: the Haar columns of one cycle of every basis group ([BG][d][d]), the basis scratch, and
     // the per-step direction columns of a launch ([BG][n][huge_col_stride])

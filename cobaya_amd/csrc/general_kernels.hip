@@ -416,33 +416,31 @@ extern "C" hipError_t mcmc_hip_launch_pack_rows(const double* rows, const int* n
     return hipGetLastError();
 }
 
-extern "C" hipError_t mcmc_hip_launch_general_step(const mcmc::GeneralStepArgs* b, hipStream_t st)
+// (grid, block and LDS: scratch_choice.h, scratch_choose)
+extern "C" hipError_t mcmc_hip_launch_general_step(const mcmc::GeneralStepArgs* b, const mcmc::ScratchChoice* c,
+                                                   hipStream_t st)
 {
     using namespace mcmc;
-    const size_t lds = sizeof(double) * 64 * (size_t)(2 * b->d + (b->s.n_modes > 0 ? b->s.n_modes : 1));
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
+    if (c->lds_attr) {
         hipError_t e = hipFuncSetAttribute((const void*)step_general_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_attr);
         if (e != hipSuccess) return e;
     }
     mcmc_hip_note_step_kernel("mcmc::step_general_kernel");
-    hipLaunchKernelGGL(step_general_kernel, dim3(b->s.W / 64), dim3(64), lds, st, *b);
+    hipLaunchKernelGGL(step_general_kernel, dim3(c->grid), dim3(c->threads), c->lds_bytes, st, *b);
     return hipGetLastError();
 }
 
-extern "C" hipError_t mcmc_hip_launch_general_drag(const mcmc::GeneralDragArgs* g, hipStream_t st)
+extern "C" hipError_t mcmc_hip_launch_general_drag(const mcmc::GeneralDragArgs* g, const mcmc::ScratchChoice* c,
+                                                   hipStream_t st)
 {
     using namespace mcmc;
-    const GeneralStepArgs* b = &g->g;
-    const size_t lds = sizeof(double) * 64 * (size_t)(2 * b->d + (b->s.n_modes > 0 ? b->s.n_modes : 1));
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
+    if (c->lds_attr) {
         hipError_t e = hipFuncSetAttribute((const void*)drag_general_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_attr);
         if (e != hipSuccess) return e;
     }
     mcmc_hip_note_step_kernel("mcmc::drag_general_kernel");
-    hipLaunchKernelGGL(drag_general_kernel, dim3(b->s.W / 64), dim3(64), lds, st, *g);
+    hipLaunchKernelGGL(drag_general_kernel, dim3(c->grid), dim3(c->threads), c->lds_bytes, st, *g);
     return hipGetLastError();
 }

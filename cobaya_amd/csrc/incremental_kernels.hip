@@ -2014,7 +2014,7 @@ hipError_t launch_drag_dq(const IncStepArgs& a, hipStream_t st)
         "mcmc::drag_inc_kernel<" + std::to_string(DQ) + ", 2, false, 1-D blocks>",
         "mcmc::drag_inc_kernel<" + std::to_string(DQ) + ", 2, true, 1-D blocks>"};
     const int v = 2 * mode + (unit_t ? 1 : 0) + (a.colflag ? 6 : 0);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > kLdsMax) return hipErrorInvalidValue;
     if (lds > 40 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kerns[v],
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

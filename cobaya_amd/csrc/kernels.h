@@ -4,18 +4,16 @@
 #include <stdint.h>
 
 #include "inc_choice.h"   // kMaxModes, inc_mix_serves, duo_serves, kIncMaxPeriodic: what the choice of kernel and the kernels share
+#include "scratch_choice.h"   // kMaxDimLane, kMaxDimPair, kRowBlock, v_slab*, v_ld, pair_split, ...: the same for the from-scratch kernels
 
 namespace mcmc {
-
-constexpr int kMaxDimLane = 32;   // lane-per-walker kernels: d <= 32 (state in VGPRs)
-constexpr int kMaxDimPair = 56;   // ... and the two-wave step kernel alone up to here
 
 // Whitening factor L_k^-1 (lower triangular) packed in the order the kernels consume it, so
 // that the wave-uniform operand stream is read front to back with wide scalar loads:
 //   for jb = 0, RB, 2RB, ... (row blocks of RB rows)
 //     for i = 0 .. min(jb + RB, d) - 1
 //       for r = 0 .. RB-1 with jb + r < d and i <= jb + r:   L[jb + r][i]
-constexpr int kRowBlock = 4;
+// (RB = kRowBlock, scratch_choice.h)
 __host__ __device__ constexpr int tri_size(int d) { return d * (d + 1) / 2; }
 
 template <typename F>
@@ -26,23 +24,6 @@ __host__ __device__ inline void tri_stream_for_each(int d, F&& f)
         for (int i = 0; i < jb + kRowBlock && i < d; ++i)
             for (int r = 0; r < kRowBlock; ++r)
                 if (jb + r < d && i <= jb + r) f(idx++, jb + r, i);
-}
-
-// Doubles per (group, cycle) slab of proposal directions V[col][i]: d*d rounded up to whole
-// KiB so that the step kernel can move a slab into LDS with 1 KiB global->LDS DMA pieces.
-// With parameter blocks a cycle has `ncols` = sum_b oversample_b * n_b columns instead of d.
-__host__ __device__ constexpr int v_slab_cols(int ncols, int d)
-{
-    return ((ncols * d * 8 + 1023) / 1024) * 128;
-}
-__host__ __device__ constexpr int v_slab(int d) { return v_slab_cols(d, d); }
-
-// d > 32 ("big" kernels): columns of V are padded to an even number of doubles (16-byte aligned
-// for the per-step 1 KiB global->LDS DMA), and a slab keeps >= 1 KiB behind its last column.
-__host__ __device__ constexpr int v_ld(int d) { return (d + 1) & ~1; }
-__host__ __device__ constexpr int v_slab_big(int d)
-{
-    return ((d * v_ld(d) * 8 + 1024 + 1023) / 1024) * 128;
 }
 
 // Constant block (doubles) in HBM, read through the scalar data cache:
@@ -181,22 +162,19 @@ struct DragArgs {
     int n_drag;            // interpolation steps per dragging step
 };
 
-// Per-dimension launchers (one translation unit per d, see walker_kernels.hip).
+// Per-dimension launchers (one translation unit per d, see walker_kernels.hip).  The step launchers
+// take the choice of scratch_choose (scratch_choice.h): the instantiation's flags, grid, block, LDS.
 struct DimKernels {
-    hipError_t (*step)(const StepArgs&, int group_size, hipStream_t);
+    hipError_t (*step)(const StepArgs&, const ScratchChoice&, hipStream_t);   // kScratchStep, StepOwn, Pair
     hipError_t (*basis)(const BasisArgs&, int n_groups, hipStream_t);
     hipError_t (*evaluate)(const EvalArgs&, hipStream_t);
     hipError_t (*moments)(const MomentArgs&, int group_size, hipStream_t);
-    hipError_t (*drag)(const DragArgs&, hipStream_t);
+    hipError_t (*drag)(const DragArgs&, const ScratchChoice&, hipStream_t);
 };
 
 // The two-wave step kernel of one dimension 32 < d <= kMaxDimPair (walker_kernels.hip compiled
-// for that d; it reads the d > 32 layout of V).  `fits`: the launch geometry of `a` is one the
-// kernel serves (whole 256-walker workgroups, LDS) -- otherwise the caller uses BigKernels.step.
-struct PairKernels {
-    bool (*fits)(const StepArgs&);
-    hipError_t (*step)(const StepArgs&, hipStream_t);
-};
+// for that d; it reads the d > 32 layout of V): its launcher, mcmc_hip_pair_<d>.
+typedef hipError_t (*PairStep)(const StepArgs*, const ScratchChoice*, hipStream_t);
 
 // The general step of 32 < d <= 128 (general_kernels.hip): mixtures, `one`, periodic parameters,
 // emitted rows, and ensembles the specialised kernels do not take.
@@ -315,7 +293,7 @@ struct IncDirArgs {
 struct BigKernels {
     int dp;  // largest dimension this instantiation serves
     hipError_t (*step)(const StepArgs&, const double* Lcol, int d, const uint32_t* norm_mask4,
-                       hipStream_t);
+                       const ScratchChoice&, hipStream_t);   // kScratchMfma, kScratchBigReg
     hipError_t (*basis)(const BasisArgs&, int n_groups, int d, hipStream_t);
     hipError_t (*evaluate)(const EvalArgs&, const double* Lrow, int d, double* scratch, hipStream_t);
     hipError_t (*moments)(const MomentArgs&, int group_size, int d, hipStream_t);
@@ -341,8 +319,10 @@ extern "C" void mcmc_hip_note_step_kernel(const char* name);
 #define MCMC_HIP_OPTIONAL
 #endif
 // general_kernels.hip, blocked_kernels.hip
-extern "C" hipError_t mcmc_hip_launch_general_step(const mcmc::GeneralStepArgs* b, hipStream_t st);
-extern "C" hipError_t mcmc_hip_launch_general_drag(const mcmc::GeneralDragArgs* g, hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_general_step(const mcmc::GeneralStepArgs* b, const mcmc::ScratchChoice* c,
+                                                   hipStream_t st);
+extern "C" hipError_t mcmc_hip_launch_general_drag(const mcmc::GeneralDragArgs* g, const mcmc::ScratchChoice* c,
+                                                   hipStream_t st);
 extern "C" hipError_t mcmc_hip_launch_pack_rows(const double* rows, const int* n_rows,
                                                 const long long* offset, double* out, int W,
                                                 int cap, int d, uint32_t walker0, hipStream_t st);
@@ -380,5 +360,7 @@ extern "C" hipError_t mcmc_hip_launch_accept_estimate_error(double* err, uint32_
                                                             hipStream_t) MCMC_HIP_OPTIONAL;
 
 #define MCMC_DECLARE_BIG(DP) extern "C" const mcmc::BigKernels* mcmc_hip_big_##DP() __attribute__((weak));
-#define MCMC_DECLARE_PAIR(D) extern "C" const mcmc::PairKernels* mcmc_hip_pair_##D() __attribute__((weak));
+#define MCMC_DECLARE_PAIR(D)                                                                        \
+    extern "C" hipError_t mcmc_hip_pair_##D(const mcmc::StepArgs*, const mcmc::ScratchChoice*, hipStream_t) \
+        __attribute__((weak));
 #define MCMC_DECLARE_DIM(D) extern "C" const mcmc::DimKernels* mcmc_hip_dim_##D() __attribute__((weak));

@@ -656,45 +656,15 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a)
 // chi2 = fma(y_j, y_j, chi2) for j = kSplit .. D-1 -- the SAME ascending chain as the one-wave
 // kernel and the oracle, so the result is bit-identical -- take the same accept decision and
 // commit their own copy of the state.
-// The split pays from d ~ 14: per 40d steps of 65 536 walkers, two waves vs one wave per walker
-// set run 0.387 / 0.385 ms at d = 8, 0.698 / 0.655 at 12, 1.09 / 1.25 at 16, 1.61 / 1.93 at 20,
-// 2.22 / 2.84 at 24.
-#ifndef MCMC_PAIR_MIN
-#define MCMC_PAIR_MIN 14
-#endif
+// The split pays from d ~ 14 (MCMC_PAIR_MIN) and where it falls (pair_split): scratch_choice.h.
 constexpr bool kPair = D >= MCMC_PAIR_MIN;
-// Measured at d = 30 (W = 65 536): splits 16 / 20 / 24 run 3.47 / 3.32 / 3.46 ms per 1200 steps,
-// 12 runs 4.1 ms -- role 0 (which also generates the variates) takes about two thirds of the rows.
-// With normal priors role 1 also forms the prior terms (a division each), and one more row
-// block moves to role 0: at the config-5 shape (d = 27, 21 normal priors) splits 16 / 20 / 24
-// run 4.42 / 4.25 / 4.03 ms per 1080 steps.
-constexpr int pair_split(bool normp)
-{
-    if (!kPair) return D;
-    int h = kRowBlock * ((2 * D + 6) / 12);  // multiple of the row block nearest 2D/3
-    // 32 < d <= 48, measured (10^10 evals/s at W = 65 536; the matrix-core kernel runs 1.15 at
-    // every one of these d): d = 33: split 24 / 28 give 2.01 / 1.85; d = 36: 24 / 28 / 32 give
-    // 1.85 / 1.76 / 1.78; d = 40: 24 / 28 / 32 / 36 give 1.60 / 1.63 / 1.68 / 1.51; d = 44:
-    // 28 / 32 / 36 give 1.46 / 1.52 / 1.48; d = 48: 28 / 32 / 36 / 40 give 1.31 / 1.31 / 1.38 / 1.26
-    // (d = 38 with split 24 dips to 1.56)
-    // d = 50: 32 / 36 / 40 give 1.16 / 1.18 / 1.20; d = 52: 32 / 36 / 40 give 0.89 / 1.00 / 1.15;
-    // d = 54: 40 / 44 give 1.02 / 1.07; d = 56: 40 / 44 / 48 give 0.85 / 0.97 / 0.84 (matrix
-    // cores, padded to 56: 0.93) -- past d = 48 role 1 runs out of registers first
-    if (kBigD) h = D < 37 ? 24 : (D < 47 ? 32 : (D < 49 ? 36 : (D < 53 ? 40 : 44)));
-    if (normp) h += kRowBlock;
-    const int hmax = D - 1 - (D - 1) % kRowBlock;   // largest whole number of row blocks below D
-    return h < kRowBlock ? kRowBlock : (h > hmax ? hmax : h);
-}
 // the split and what follows from it, per instantiation
 template <bool NORMP>
 struct PairGeom {
-    static constexpr int split = pair_split(NORMP);
+    static constexpr int split = pair_split(D, NORMP);
     static constexpr int nta = split * (split + 1) / 2;   // operands of rows [0, split)
     static constexpr int db = D - split;
-    // exchanged doubles per walker and step: chi2 of role 0, r, Ea, the y_j of role 1; with
-    // normal priors also role 1's prior sum
-    // (d > 32: the three other chi2 chains of role 0 at the end)
-    static constexpr int xf = db + (NORMP ? 4 : 3) + (kBigD ? 3 : 0);
+    static constexpr int xf = pair_xf(D, NORMP);   // exchanged doubles per walker and step
 };
 
 // `ok` collects the support test as a wave mask on the scalar ALU (one bit per walker):
@@ -1487,109 +1457,44 @@ __global__ void __launch_bounds__(64) pool_moments_kernel(const MomentArgs a)
 
 #endif  // MCMC_D <= 32
 // ---------------------------------------------------------------- launchers
-constexpr size_t kLdsMax = 160 * 1024;
-size_t pair_lds(const StepArgs& a)
+// (which kernel, its flags, grid, block and LDS: scratch_choice.h, scratch_choose)
+hipError_t launch_pair(const StepArgs& a, const ScratchChoice& c, hipStream_t st)
 {
-    return sizeof(double) * (size_t)(2 * (256 / a.group_size) * a.slab +
-        2 * ((a.norm_mask | a.norm_mask_hi) != 0u ? PairGeom<true>::xf : PairGeom<false>::xf) * 256);
-}
-// the two-wave kernel serves: one mode, non-periodic priors (normal ones have their own
-// instantiation), no emitted rows, no one-parameter blocks, whole 256-walker workgroups
-bool pair_fits(const StepArgs& a)
-{
-    // (with normal priors the matrix-core kernel is ahead again from d = 55: 7.3 against 7.0)
-    if (D >= 55 && (a.norm_mask | a.norm_mask_hi) != 0u) return false;
-    return kPair && a.periodic_mask == 0u && a.n_modes == 1 && a.rows == nullptr &&
-           a.vflag == nullptr && a.W % 256 == 0 && 256 % a.group_size == 0 &&
-           pair_lds(a) <= kLdsMax;
-}
-hipError_t launch_pair(const StepArgs& a, hipStream_t st)
-{
-    // two waves per 64 walkers: 512-thread workgroups of 256 walkers
-    const bool normp = (a.norm_mask | a.norm_mask_hi) != 0u;
-    size_t plds = pair_lds(a);
-    const int nwg = a.W / 256;
-    const int per_cu = (nwg + 255) / 256;      // even placement, see launch_step
-    size_t want = ((size_t)(160 * 1024) / (size_t)per_cu / 1024) * 1024;
-    if (per_cu == 1) want = 96 * 1024;         // > half of the LDS: one workgroup per CU
-    if (want > plds) plds = want;
-    const bool unit_t = a.temperature == 1.0;
     typedef void (*kern_t)(const StepArgs);
-    const kern_t kern = normp ? (unit_t ? step_pair_kernel<true, true> : step_pair_kernel<false, true>)
-                              : (unit_t ? step_pair_kernel<true, false> : step_pair_kernel<false, false>);
-    hipError_t e = hipFuncSetAttribute((const void*)kern,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds);
+    const kern_t kern = c.normp ? (c.unit_t ? step_pair_kernel<true, true> : step_pair_kernel<false, true>)
+                                : (c.unit_t ? step_pair_kernel<true, false> : step_pair_kernel<false, false>);
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)c.lds_attr);
     if (e != hipSuccess) return e;
-    mcmc_hip_note_step_kernel(normp ? (unit_t ? "mcmc::step_pair_kernel<true, true>"
-                                              : "mcmc::step_pair_kernel<false, true>")
-                                    : (unit_t ? "mcmc::step_pair_kernel<true, false>"
-                                              : "mcmc::step_pair_kernel<false, false>"));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), plds, st, a);
+    mcmc_hip_note_step_kernel(c.normp ? (c.unit_t ? "mcmc::step_pair_kernel<true, true>"
+                                                  : "mcmc::step_pair_kernel<false, true>")
+                                      : (c.unit_t ? "mcmc::step_pair_kernel<true, false>"
+                                                  : "mcmc::step_pair_kernel<false, false>"));
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.threads), c.lds_bytes, st, a);
     return hipGetLastError();
 }
 
 #if MCMC_D <= 32
-hipError_t launch_step(const StepArgs& a, int group_size, hipStream_t st)
+hipError_t launch_step(const StepArgs& a, const ScratchChoice& c, hipStream_t st)
 {
-    const bool multi = a.n_modes > 1;
-    size_t lds = 0;
-    const int bs = (a.W % 256 == 0) ? 256 : (a.W % 128 == 0) ? 128 : 64;
-    const dim3 grid(a.W / bs), block(bs);
-    lds = sizeof(double) * (size_t)(2 * (bs / a.group_size) * a.slab + (multi ? a.n_modes * bs : 0));
-    // Placement: the waves of this kernel run for the whole launch, and at W = 65 536 there
-    // are exactly as many waves as SIMDs.  Requesting (otherwise unused) LDS so that only
-    // ceil(#workgroups / 256 CUs) workgroups fit on a CU makes the dispatcher spread them
-    // evenly instead of doubling up waves on some SIMDs while others idle.
-    {
-        const int per_cu = (int)((grid.x + 255) / 256);
-        size_t want = (size_t)(160 * 1024) / (size_t)per_cu;
-        want = (want / 1024) * 1024;
-        if (want > 64 * 1024) want = 64 * 1024;
-        if (want > lds) lds = want;
-    }
-    const bool general = (a.norm_mask | a.periodic_mask) != 0u || a.n_modes == 0 ||
-                         a.rows != nullptr || D == 1 || a.vflag != nullptr;
-    if (a.own_basis) {
-        // `shared_basis: False`: no directions in LDS (the mode log-densities of a mixture and the
-        // placement request only); the GENERAL step with every walker's own columns from HBM
-        size_t own_lds = sizeof(double) * (size_t)(multi ? a.n_modes * bs : 0);
-        const int per_cu = (int)((grid.x + 255) / 256);
-        size_t want = (((size_t)(160 * 1024) / (size_t)per_cu) / 1024) * 1024;
-        if (want > 64 * 1024) want = 64 * 1024;
-        if (want > own_lds) own_lds = want;
-        if (own_lds > kLdsMax) return hipErrorInvalidValue;
-        const void* ofn = multi ? (const void*)step_kernel<true, true, true> : (const void*)step_kernel<false, true, true>;
-        if (own_lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(ofn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)own_lds);
-            if (e != hipSuccess) return e;
-        }
-        mcmc_hip_note_step_kernel(multi ? "mcmc::step_kernel<true, true, own basis>"
-                                        : "mcmc::step_kernel<false, true, own basis>");
-        if (multi) hipLaunchKernelGGL((step_kernel<true, true, true>), grid, block, own_lds, st, a);
-        else hipLaunchKernelGGL((step_kernel<false, true, true>), grid, block, own_lds, st, a);
-        return hipGetLastError();
-    }
-    if (lds > kLdsMax) return hipErrorInvalidValue;   // the cycle's directions do not fit LDS
-    if (pair_fits(a)) return launch_pair(a, st);
-    const void* fn = multi ? (general ? (const void*)step_kernel<true, true>
-                                      : (const void*)step_kernel<true, false>)
-                           : (general ? (const void*)step_kernel<false, true>
-                                      : (const void*)step_kernel<false, false>);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (c.family == kScratchPair) return launch_pair(a, c, st);
+    typedef void (*kern_t)(const StepArgs);
+    const bool own = c.family == kScratchStepOwn;
+    const kern_t kern = own ? (c.multi ? step_kernel<true, true, true> : step_kernel<false, true, true>)
+                            : c.multi ? (c.general ? step_kernel<true, true> : step_kernel<true, false>)
+                                      : (c.general ? step_kernel<false, true> : step_kernel<false, false>);
+    if (c.lds_attr) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)c.lds_attr);
         if (e != hipSuccess) return e;
     }
-    mcmc_hip_note_step_kernel(multi ? (general ? "mcmc::step_kernel<true, true>"
-                                               : "mcmc::step_kernel<true, false>")
-                                    : (general ? "mcmc::step_kernel<false, true>"
-                                               : "mcmc::step_kernel<false, false>"));
-    if (multi) {
-        if (general) hipLaunchKernelGGL((step_kernel<true, true>), grid, block, lds, st, a);
-        else hipLaunchKernelGGL((step_kernel<true, false>), grid, block, lds, st, a);
-    } else {
-        if (general) hipLaunchKernelGGL((step_kernel<false, true>), grid, block, lds, st, a);
-        else hipLaunchKernelGGL((step_kernel<false, false>), grid, block, lds, st, a);
-    }
+    mcmc_hip_note_step_kernel(own ? (c.multi ? "mcmc::step_kernel<true, true, own basis>"
+                                             : "mcmc::step_kernel<false, true, own basis>")
+                                  : c.multi ? (c.general ? "mcmc::step_kernel<true, true>"
+                                                         : "mcmc::step_kernel<true, false>")
+                                            : (c.general ? "mcmc::step_kernel<false, true>"
+                                                         : "mcmc::step_kernel<false, false>"));
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.threads), c.lds_bytes, st, a);
     return hipGetLastError();
 }
 
@@ -1625,27 +1530,22 @@ hipError_t launch_moments(const MomentArgs& a, int group_size, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t launch_drag(const DragArgs& a, hipStream_t st)
+hipError_t launch_drag(const DragArgs& a, const ScratchChoice& c, hipStream_t st)
 {
-    const bool multi = a.s.n_modes > 1;
-    const int bs = (a.s.W % 256 == 0) ? 256 : 64;
-    const size_t lds = sizeof(double) * bs * (size_t)(2 * D + (multi ? a.s.n_modes : 0));
-    const dim3 grid(a.s.W / bs), block(bs);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(multi ? (const void*)drag_kernel<true> : (const void*)drag_kernel<false>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    typedef void (*kern_t)(const DragArgs);
+    const kern_t kern = c.multi ? drag_kernel<true> : drag_kernel<false>;
+    if (c.lds_attr) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)c.lds_attr);
         if (e != hipSuccess) return e;
     }
-    mcmc_hip_note_step_kernel(multi ? "mcmc::drag_kernel<true>" : "mcmc::drag_kernel<false>");
-    if (multi) hipLaunchKernelGGL(drag_kernel<true>, grid, block, lds, st, a);
-    else hipLaunchKernelGGL(drag_kernel<false>, grid, block, lds, st, a);
+    mcmc_hip_note_step_kernel(c.multi ? "mcmc::drag_kernel<true>" : "mcmc::drag_kernel<false>");
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.threads), c.lds_bytes, st, a);
     return hipGetLastError();
 }
 
 const DimKernels kKernels = {launch_step, launch_basis, launch_evaluate, launch_moments,
                              launch_drag};
-#else
-const PairKernels kPairKernels = {pair_fits, launch_pair};
 #endif
 
 }  // namespace
@@ -1657,5 +1557,9 @@ const PairKernels kPairKernels = {pair_fits, launch_pair};
 extern "C" const mcmc::DimKernels* MCMC_CAT(mcmc_hip_dim_, MCMC_D)() { return &mcmc::kKernels; }
 #else
 static_assert(MCMC_D <= mcmc::kMaxDimPair, "two-wave kernel: d <= kMaxDimPair");
-extern "C" const mcmc::PairKernels* MCMC_CAT(mcmc_hip_pair_, MCMC_D)() { return &mcmc::kPairKernels; }
+extern "C" hipError_t MCMC_CAT(mcmc_hip_pair_, MCMC_D)(const mcmc::StepArgs* a, const mcmc::ScratchChoice* c,
+                                                      hipStream_t st)
+{
+    return mcmc::launch_pair(*a, *c, st);
+}
 #endif

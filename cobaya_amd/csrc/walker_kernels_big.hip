@@ -465,13 +465,11 @@ __global__ void __launch_bounds__(256) step_big_reg_kernel(const BigStepArgs b)
 // LDS all measured SLOWER (5.1-5.8 ms vs 4.07 ms per 200 steps at d = 100) -- the unpinned
 // schedule pairs adjacent tiles into ds_read2st64_b64.
 typedef double d4 __attribute__((ext_vector_type(4)));
-// Row tile R holds the rows 16 R - kRowShift .. + 15: when DP is not a multiple of 16 the PARTIAL
-// row tile is the FIRST one (rows < 0 are zero padding), where it costs 4 - kRowShift/4 tiles,
-// instead of the last one, where it would cost KT (DP = 100: 91 tiles instead of 109).  The
-// shift is a multiple of 4, so lane class c still holds the rows j = c (mod 4).
-constexpr int kRowShift = (16 - (DP + 3) / 4 * 4 % 16) % 16;
-constexpr int RT = (DP + kRowShift + 15) / 16;     // row tiles
-constexpr int KT = (DP + 3) / 4;       // k-steps
+// Row tile R holds the rows 16 R - kRowShift .. + 15 (why the partial row tile is the first one:
+// scratch_choice.h, mfma_row_shift)
+constexpr int kRowShift = mfma_row_shift(DP);
+constexpr int RT = mfma_row_tiles(DP);     // row tiles
+constexpr int KT = mfma_k_steps(DP);       // k-steps
 constexpr int RH = (RT + 1) / 2;       // row tiles of the first pass (RT / 2 -- fewer repeated trial
                                        // deviations -- measured 14.95 against 14.0 ms at d = 100)
 // tile (R, kk) exists for kk <= kk_max(R) (its last row is 16 R - kRowShift + 15); R-major
@@ -484,6 +482,7 @@ constexpr int tile_offset(int R)
     return n;
 }
 constexpr int kTiles = tile_offset(RT);
+static_assert(kTiles == mfma_tiles(DP), "scratch_choice.h sizes the LDS of step_mfma_kernel by its tiles");
 
 struct MfmaStepArgs {
     StepArgs s;
@@ -523,19 +522,10 @@ __device__ __forceinline__ void mfma_pass(d4 (&acc)[R1 - R0], const double (&x)[
     }
 }
 
-// kMfmaWaves waves of 16 walkers per workgroup.  16 (256 walkers, one workgroup per CU, 128
-// registers per lane, two passes with 73 spilled registers) measured 4.04 ms per 200 steps at
-// d = 100; 8 (128 walkers, two workgroups per CU, 256 registers: one pass, no spills, no second
-// evaluation of the trial) 4.33 ms -- four waves per SIMD hide more than the spills cost.
-#ifndef MCMC_MFMA_WAVES
-#define MCMC_MFMA_WAVES 16
-#endif
+// (kMfmaWaves waves of 16 walkers per workgroup: scratch_choice.h)
 #ifndef MCMC_MFMA_RNG4
 #define MCMC_MFMA_RNG4 (MCMC_DP <= 80)
 #endif
-constexpr int kMfmaWaves = MCMC_MFMA_WAVES;
-constexpr int kMfmaWalkers = 16 * kMfmaWaves;
-constexpr int kMfmaThreads = 64 * kMfmaWaves;
 constexpr int kMfmaFirstPass = kMfmaWaves <= 8 ? RT : RH;
 
 // NORMP: some priors are normal (its own instantiation: the uniform-only kernel keeps its
@@ -893,49 +883,31 @@ __global__ void __launch_bounds__(64) pool_moments_big_kernel(const MomentArgs a
 }
 
 // ---------------------------------------------------------------- launchers
+// (matrix cores or column sweep, grid, block and LDS: scratch_choice.h, scratch_choose)
 hipError_t launch_step(const StepArgs& a, const double* Lcol, int d, const uint32_t* norm_mask4,
-                       hipStream_t st)
+                       const ScratchChoice& c, hipStream_t st)
 {
-    const bool has_norm = (norm_mask4[0] | norm_mask4[1] | norm_mask4[2] | norm_mask4[3]) != 0u;
-    if (a.W % kMfmaWalkers == 0 && (kMfmaWalkers % a.group_size == 0 || a.group_size % kMfmaWalkers == 0)) {
-        // matrix-core kernel: its tiles follow the column-sweep copy of L^-1 in `Lcol`
-        MfmaStepArgs m{a, Lcol + (size_t)DP * DP, d, {norm_mask4[0], norm_mask4[1], norm_mask4[2], norm_mask4[3]}};
-        const int gpb = (kMfmaWalkers + a.group_size - 1) / a.group_size;
-        const size_t lds = sizeof(double) * (size_t)(kTiles * 64 + 24 * KT + 2 * gpb * 128);
-        // placement: 256 walkers per CU at W = 65 536 -- ask for just under 1/n of the LDS so
-        // that exactly n = 256 / walkers-per-workgroup workgroups share a CU
-        const size_t share = ((size_t)(160 << 10) / (size_t)(256 / kMfmaWalkers)) - 2048;
-        const size_t want = lds > share ? lds : share;
-        hipError_t e = hipFuncSetAttribute(
-            has_norm ? (const void*)step_mfma_kernel<true> : (const void*)step_mfma_kernel<false>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
+#if MCMC_DP <= 112   // (kSweepMaxDim: no column sweep above)
+    if (c.family == kScratchBigReg) {
+        BigStepArgs b{a, Lcol, d};
+        hipError_t e = hipFuncSetAttribute((const void*)step_big_reg_kernel,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_attr);
         if (e != hipSuccess) return e;
-        mcmc_hip_note_step_kernel(has_norm ? "mcmc::step_mfma_kernel<true>"
-                                           : "mcmc::step_mfma_kernel<false>");
-        if (has_norm)
-            hipLaunchKernelGGL(step_mfma_kernel<true>, dim3(a.W / kMfmaWalkers), dim3(kMfmaThreads),
-                               want, st, m);
-        else
-            hipLaunchKernelGGL(step_mfma_kernel<false>, dim3(a.W / kMfmaWalkers), dim3(kMfmaThreads),
-                               want, st, m);
+        mcmc_hip_note_step_kernel("mcmc::step_big_reg_kernel");
+        hipLaunchKernelGGL(step_big_reg_kernel, dim3(c.grid), dim3(c.threads), c.lds_bytes, st, b);
         return hipGetLastError();
     }
-#if MCMC_DP > 112
-    return hipErrorInvalidValue;                 // no column-sweep fallback at this size
-#else
-    if (has_norm) return hipErrorInvalidValue;   // the column-sweep fallback has uniform priors only
-    BigStepArgs b{a, Lcol, d};
-    const int bs = (a.W % 256 == 0) ? 256 : (a.W % 128 == 0) ? 128 : 64;
-    const size_t lds = sizeof(double) * (size_t)(DP * DP + 4 * DP + 2 * (bs / a.group_size) * 128);
-    {
-        hipError_t e = hipFuncSetAttribute((const void*)step_big_reg_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    mcmc_hip_note_step_kernel("mcmc::step_big_reg_kernel");
-    hipLaunchKernelGGL(step_big_reg_kernel, dim3(a.W / bs), dim3(bs), lds, st, b);
-    return hipGetLastError();
 #endif
+    // kScratchMfma: the tiles of the matrix-core kernel follow the column-sweep copy of L^-1 in `Lcol`
+    MfmaStepArgs m{a, Lcol + (size_t)DP * DP, d, {norm_mask4[0], norm_mask4[1], norm_mask4[2], norm_mask4[3]}};
+    typedef void (*kern_t)(const MfmaStepArgs);
+    const kern_t kern = c.normp ? step_mfma_kernel<true> : step_mfma_kernel<false>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)c.lds_attr);
+    if (e != hipSuccess) return e;
+    mcmc_hip_note_step_kernel(c.normp ? "mcmc::step_mfma_kernel<true>" : "mcmc::step_mfma_kernel<false>");
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.threads), c.lds_bytes, st, m);
+    return hipGetLastError();
 }
 
 hipError_t launch_basis(const BasisArgs& a, int n_groups, int d, hipStream_t st)
@@ -965,7 +937,7 @@ hipError_t launch_evaluate(const EvalArgs& a, const double* Lrow, int d, double*
 hipError_t launch_moments(const MomentArgs& a, int group_size, int d, hipStream_t st)
 {
     int slice = group_size;   // walkers per pass through LDS
-    while (sizeof(double) * (size_t)slice * (d | 1) > 160 * 1024) slice /= 2;
+    while (sizeof(double) * (size_t)slice * (d | 1) > kLdsMax) slice /= 2;
     const size_t lds = sizeof(double) * (size_t)slice * (d | 1);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)group_moments_big_kernel,

@@ -76,6 +76,25 @@ class IncChoice(C.Structure):
 (INC_NOT_SERVED, INC_STEP, INC_STEP_EMIT, INC_MIX, INC_ANY, INC_DRAG, INC_DUO_MIX,
  INC_DUO_ONE) = range(8)
 
+
+class ScratchShape(C.Structure):
+    """mcmc_hip_scratch_shape: the model and ensemble as far as the choice of the from-scratch step
+    kernel depends on them (flags are 0 / 1)."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "d", "n_modes", "n_walkers", "group_size", "any_normal", "any_periodic", "emit", "emit_thin",
+        "unit_t", "own_basis", "blocked", "n_drag", "cps", "cps_f", "has_1d_column")]
+
+
+class ScratchChoice(C.Structure):
+    """mcmc_hip_scratch_answer: the kernel family (SCRATCH_*), its template flags and its launch."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "family", "reason", "multi", "general", "unit_t", "normp", "unit", "walkers_per_wg", "threads",
+        "grid", "lds_bytes", "lds_attr", "v_ld", "slab", "slab_f")]
+
+
+(SCRATCH_NOT_SERVED, SCRATCH_STEP, SCRATCH_STEP_OWN, SCRATCH_PAIR, SCRATCH_MFMA, SCRATCH_BIG_REG,
+ SCRATCH_GENERAL, SCRATCH_DRAG, SCRATCH_GENERAL_DRAG) = range(9)
+
 MOVE_METROPOLIS, MOVE_STRETCH = 0, 1   # mcmc_hip_set_move
 
 # every symbol include/mcmc_hip.h declares: (name, restype, argtypes)
@@ -87,6 +106,7 @@ SYMBOLS = [
     ("mcmc_hip_max_dim", C.c_int32, []),
     ("mcmc_hip_incremental_supported", C.c_int, [C.c_int32] * 6),
     ("mcmc_hip_incremental_choice", C.c_int, [C.POINTER(IncShape), C.POINTER(IncChoice)]),
+    ("mcmc_hip_scratch_choice", C.c_int, [C.POINTER(ScratchShape), C.POINTER(ScratchChoice)]),
     ("mcmc_hip_create", C.c_int, [C.POINTER(Config), C.POINTER(_H)]),
     ("mcmc_hip_destroy", None, [_H]),
     ("mcmc_hip_set_prior", C.c_int, [_H, c_int32_p, c_double_p, c_double_p, c_int32_p]),
@@ -320,6 +340,22 @@ def incremental_choice(d, n_modes, n_periodic=0, n_drag=0, n_walkers=65536, basi
     if rc != OK:
         raise EngineError(rc, "mcmc_hip_incremental_choice is not served by this library")
     return {n: int(getattr(out, n)) for n, _ in IncChoice._fields_}
+
+
+def scratch_choice(d, n_modes=1, n_walkers=65536, group_size=256, any_normal=False, any_periodic=False,
+                   emit=False, emit_thin=False, unit_t=True, own_basis=False, blocked=False, n_drag=0,
+                   cps=0, cps_f=0, has_1d_column=False):
+    """Which from-scratch step kernel serves this shape and how it is launched, as a dict of the
+    fields of mcmc_hip_scratch_answer (mcmc_hip_scratch_choice: the library's one rule, a pure
+    function -- no device).  family == SCRATCH_NOT_SERVED: `reason` says why."""
+    shape = ScratchShape(int(d), int(n_modes), int(n_walkers), int(group_size), int(any_normal),
+                         int(any_periodic), int(emit), int(emit_thin), int(unit_t), int(own_basis),
+                         int(blocked), int(n_drag), int(cps), int(cps_f), int(has_1d_column))
+    out = ScratchChoice()
+    rc = load_library().mcmc_hip_scratch_choice(C.byref(shape), C.byref(out))
+    if rc != OK:
+        raise EngineError(rc, "mcmc_hip_scratch_choice is not served by this library")
+    return {n: int(getattr(out, n)) for n, _ in ScratchChoice._fields_}
 
 
 def gelman_rubin(n_chains, sum_N, sum_Ncov, sum_mean, sum_mm):

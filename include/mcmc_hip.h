@@ -134,6 +134,46 @@ typedef struct mcmc_hip_inc_choice {
 } mcmc_hip_inc_choice;
 MCMC_HIP_API int mcmc_hip_incremental_choice(const mcmc_hip_inc_shape* shape, mcmc_hip_inc_choice* out);
 
+/* The same for the kernels that evaluate every trial from scratch (no MCMC_HIP_FLAG_INCREMENTAL): which
+ * kernel mcmc_hip_step launches for a shape and with what geometry (csrc/scratch_choice.h).  A pure
+ * function (no context, no device); what this library was built with is read from its own tables. */
+typedef struct mcmc_hip_scratch_shape {
+    int32_t d, n_modes;         /* n_modes 0: the `one` likelihood */
+    int32_t n_walkers, group_size;
+    int32_t any_normal, any_periodic;
+    int32_t emit;               /* emit_capacity > 0 */
+    int32_t emit_thin;          /* mcmc_hip_set_emit_thin > 1 */
+    int32_t unit_t;             /* temperature == 1 */
+    int32_t own_basis;          /* MCMC_HIP_FLAG_OWN_BASIS */
+    int32_t blocked;            /* parameter blocks */
+    int32_t n_drag;             /* interpolation steps per dragging step; 0: Metropolis steps */
+    int32_t cps, cps_f;         /* direction columns per cycle (0: d); of the fast blocks (dragging) */
+    int32_t has_1d_column;      /* the launch's columns include one of a one-parameter block */
+} mcmc_hip_scratch_shape;
+#define MCMC_HIP_SCRATCH_NOT_SERVED 0
+#define MCMC_HIP_SCRATCH_STEP 1          /* step_kernel<MULTI, GENERAL> */
+#define MCMC_HIP_SCRATCH_STEP_OWN 2      /* step_kernel<MULTI, true, own basis> */
+#define MCMC_HIP_SCRATCH_PAIR 3          /* step_pair_kernel<UNIT_T, NORMP> */
+#define MCMC_HIP_SCRATCH_MFMA 4          /* step_mfma_kernel<NORMP> */
+#define MCMC_HIP_SCRATCH_BIG_REG 5       /* step_big_reg_kernel */
+#define MCMC_HIP_SCRATCH_GENERAL 6       /* step_general_kernel */
+#define MCMC_HIP_SCRATCH_DRAG 7          /* drag_kernel<MULTI> */
+#define MCMC_HIP_SCRATCH_GENERAL_DRAG 8  /* drag_general_kernel */
+typedef struct mcmc_hip_scratch_answer {
+    int32_t family;             /* MCMC_HIP_SCRATCH_* */
+    int32_t reason;             /* not served: 1 a shape mcmc_hip_create refuses, 2 emit_thin, 3 own bases with blocks
+                                 * or dragging, 4 the general d > 32 kernels' LDS, 5 a cycle's directions against
+                                 * the LDS, 6 / 7 no column sweep at this size / with normal priors; served: 0 */
+    int32_t multi, general, unit_t, normp;   /* the template arguments of the instantiation */
+    int32_t unit;               /* the compiled MCMC_D or MCMC_DP of its translation unit; 0: one symbol */
+    int32_t walkers_per_wg, threads, grid;
+    int32_t lds_bytes;          /* dynamic LDS of the launch, placement request included */
+    int32_t lds_attr;           /* hipFuncAttributeMaxDynamicSharedMemorySize set before it; 0: not set */
+    int32_t v_ld;               /* doubles between two direction columns */
+    int32_t slab, slab_f;       /* doubles per (group, cycle) slab of directions; of the fast blocks' */
+} mcmc_hip_scratch_answer;
+MCMC_HIP_API int mcmc_hip_scratch_choice(const mcmc_hip_scratch_shape* shape, mcmc_hip_scratch_answer* out);
+
 /* Sampler.__init__ + MCMC.initialize (cobaya/sampler.py:257-322, mcmc.py:111-271) */
 MCMC_HIP_API int mcmc_hip_create(const mcmc_hip_config* cfg, mcmc_hip_ctx** out);
 MCMC_HIP_API void mcmc_hip_destroy(mcmc_hip_ctx* h);

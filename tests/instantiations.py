@@ -463,20 +463,30 @@ def one_parameter_column(prob, c, group, step):
 
 
 # ================================================================== every trial from scratch
-# walker_kernels.hip (launch_step, launch_pair, launch_drag; D = 1 .. 32 all of them, D = 33 .. 56
-# step_pair_kernel alone) and walker_kernels_big.hip (launch_step; one translation unit per DP).
-# The names carry no d: the unit is (name, D), D the compiled MCMC_D or MCMC_DP.  Which launcher a
-# shape reaches is mcmc_hip_step's (capi.hip: `general_big`, `h->kp->fits`), restated in
-# predict_scratch with the launchers' own tests.
-BIG_DPS = (48, 56, 64, 72, 80, 88, 96, 100, 112, 120, 128)     # cobaya_amd/build.py
-PAIR_MIN, PAIR_MAX, LANE_MAX = 14, 56, 32                      # MCMC_PAIR_MIN, kMaxDimPair, kMaxDimLane
-WALKER, WALKER_BIG = "cobaya_amd/csrc/walker_kernels.hip", "cobaya_amd/csrc/walker_kernels_big.hip"
+# walker_kernels.hip (D = 1 .. 32 all of its kernels, D = 33 .. 56 step_pair_kernel alone),
+# walker_kernels_big.hip (one translation unit per DP) and general_kernels.hip (one symbol each).
+# The names carry no d: the unit is (name, D), D the compiled MCMC_D or MCMC_DP (0: one symbol).
+# Which kernel serves a shape is scratch_choose's (cobaya_amd/csrc/scratch_choice.h), asked without
+# a device through cobaya_amd.engine.scratch_choice; predict_scratch is its INDEPENDENT restatement
+# -- the one the device sweep has verified -- and tests/test_host_logic.py holds one against the other.
+BIG_DPS = (48, 56, 64, 72, 80, 88, 96, 100, 112, 120, 128)     # scratch_choice.h: kBigDps
+# MCMC_PAIR_MIN, kMaxDimPair, kMaxDimPairNormal, kMaxDimLane, kSweepMaxDim, kLdsMax
+PAIR_MIN, PAIR_MAX, PAIR_MAX_NORMAL, LANE_MAX, SWEEP_MAX, LDS_MAX = 14, 56, 54, 32, 112, 160 * 1024
+SCRATCH_CHOICE = "scratch_choice.h"      # (the rules that make a name unreachable)
 S_STEP, S_OWN, S_DRAG, S_PAIR, S_MFMA, S_BIG = ("scratch_step", "scratch_own", "scratch_drag",
                                                 "scratch_pair", "scratch_mfma", "scratch_big_reg")
 S_FAMILIES = (S_STEP, S_OWN, S_DRAG, S_PAIR, S_MFMA, S_BIG)
+GENERAL_STEP, GENERAL_DRAG = "mcmc::step_general_kernel", "mcmc::drag_general_kernel"
+# the refusals of scratch_choose (mcmc_hip_scratch_answer.reason)
+(R_BAD_SHAPE, R_EMIT_THIN, R_OWN_BLOCKS, R_GENERAL_LDS, R_CYCLE_LDS, R_SWEEP_SIZE,
+ R_SWEEP_NORMAL) = range(1, 8)
 # D: the compiled MCMC_D (MCMC_DP for the last two families); flags: the template arguments
 SName = namedtuple("SName", "name family D flags kernel why")
-SCase = namedtuple("SCase", "name family D d W gs K prior T own drag seed")
+# prior: 0 the unit box, 2 normal priors on the odd parameters; periodic: the periodic indices;
+# blocks: None, "two" (two blocks of two parameters or more), "one" (the last block is one
+# parameter), "over" (two blocks, the second five times per cycle); thin: emit_thin > 1
+SCase = namedtuple("SCase", "name family D d W gs K prior T own drag seed periodic emit blocks thin",
+                   defaults=((), False, None, False))
 
 
 def dp_of(d):
@@ -489,9 +499,15 @@ def dims_of_dp(dp):
     return sorted({(below[-1] if below else LANE_MAX) + 1, dp})
 
 
-def pair_lds(d, gs, normp):
-    """walker_kernels.hip: pair_lds, with pair_split and PairGeom::xf (kRowBlock = 4) and the slab
-    of kernels.h (v_slab, v_slab_big)."""
+def v_slab(cols, d, big):
+    """scratch_choice.h: v_slab_cols, v_slab_big (doubles)."""
+    ld = (d + 1) & ~1
+    return ((d * ld * 8 + 1024 + 1023) // 1024) * 128 if big else ((cols * d * 8 + 1023) // 1024) * 128
+
+
+def pair_lds(d, gs, normp, cols=None):
+    """scratch_choose's pair_lds, with pair_split and pair_xf (kRowBlock = 4) and the slab of the
+    directions (cols: columns per cycle at d <= 32, d without blocks)."""
     big = d > LANE_MAX
     h = 4 * ((2 * d + 6) // 12)
     if big:
@@ -501,46 +517,46 @@ def pair_lds(d, gs, normp):
     hmax = d - 1 - (d - 1) % 4
     split = 4 if h < 4 else min(h, hmax)
     xf = d - split + (4 if normp else 3) + (3 if big else 0)
-    ld = (d + 1) & ~1
-    slab = ((d * ld * 8 + 1024 + 1023) // 1024) * 128 if big else ((d * d * 8 + 1023) // 1024) * 128
-    return 8 * (2 * (256 // gs) * slab + 2 * xf * 256)
+    return 8 * (2 * (256 // gs) * v_slab(d if cols is None else cols, d, big) + 2 * xf * 256)
 
 
-def pair_fits(d, W, gs, multi, normp):      # walker_kernels.hip: pair_fits (no periodic, rows, 1-D)
+def pair_fits(d, W, gs, multi, normp, cols=None):      # scratch_choose: `pair` (no periodic, rows, 1-D column)
     return (PAIR_MIN <= d <= PAIR_MAX and not multi and W % 256 == 0 and 256 % gs == 0
-            and not (d >= 55 and normp) and pair_lds(d, gs, normp) <= 160 * 1024)
+            and not (d > PAIR_MAX_NORMAL and normp) and pair_lds(d, gs, normp, cols) <= LDS_MAX)
 
 
 def enumerate_scratch():
     out = []
     for D in range(1, LANE_MAX + 1):
         for multi in (False, True):
-            for general in (False, True):      # launch_step
+            for general in (False, True):      # kScratchStep
                 why = ""
                 if D == 1 and not general:
-                    why = f"{WALKER}:1551 launch_step: D == 1 always takes the general step"
+                    why = f"{SCRATCH_CHOICE} scratch_choose, kScratchStep: d == 1 always takes the general step"
                 out.append(SName(f"mcmc::step_kernel<{_b(multi)}, {_b(general)}>", S_STEP, D, (multi, general),
                                  f"step_kernel<{_b(multi)}, {_b(general)}, false>", why))
             out.append(SName(f"mcmc::step_kernel<{_b(multi)}, true, own basis>", S_OWN, D, (multi,),
                              f"step_kernel<{_b(multi)}, true, true>",
-                             "cobaya_amd/csrc/capi.hip:311 mcmc_hip_create: a basis per walker needs d > 1" if D == 1 else ""))
+                             f"{SCRATCH_CHOICE} scratch_choose, `own`: a basis per walker needs d > 1" if D == 1 else ""))
             out.append(SName(f"mcmc::drag_kernel<{_b(multi)}>", S_DRAG, D, (multi,), f"drag_kernel<{_b(multi)}>",
-                             f"{WALKER}:1628 launch_drag: dragging needs a slow and a fast parameter" if D == 1 else ""))
-    for D in range(1, PAIR_MAX + 1):           # launch_pair: compiled at every D, served from MCMC_PAIR_MIN on
+                             f"{SCRATCH_CHOICE} ScratchShape::n_drag: dragging needs a slow and a fast parameter"
+                             if D == 1 else ""))
+    for D in range(1, PAIR_MAX + 1):           # kScratchPair: compiled at every D, served from MCMC_PAIR_MIN on
         for unit_t in (False, True):
             for normp in (False, True):
                 why = ""
                 if D < PAIR_MIN:
-                    why = f"{WALKER}:1502 pair_fits: kPair is D >= MCMC_PAIR_MIN = 14"
-                elif D >= 55 and normp:
-                    why = f"{WALKER}:1501 pair_fits: with normal priors step_mfma_kernel serves d >= 55"
+                    why = f"{SCRATCH_CHOICE} scratch_choose, `pair`: d >= MCMC_PAIR_MIN = 14"
+                elif D > PAIR_MAX_NORMAL and normp:
+                    why = (f"{SCRATCH_CHOICE} scratch_choose, `pair`: with normal priors step_mfma_kernel serves "
+                           "d > kMaxDimPairNormal = 54")
                 out.append(SName(f"mcmc::step_pair_kernel<{_b(unit_t)}, {_b(normp)}>", S_PAIR, D, (unit_t, normp),
                                  f"step_pair_kernel<{_b(unit_t)}, {_b(normp)}>", why))
-    for dp in BIG_DPS:                         # walker_kernels_big.hip: launch_step
+    for dp in BIG_DPS:                         # kScratchMfma, kScratchBigReg
         for normp in (False, True):
             out.append(SName(f"mcmc::step_mfma_kernel<{_b(normp)}>", S_MFMA, dp, (normp,),
                              f"step_mfma_kernel<{_b(normp)}>", ""))
-        if dp <= 112:                          # (#if MCMC_DP > 112: no column-sweep fallback)
+        if dp <= SWEEP_MAX:                    # (kSweepMaxDim: no column sweep above)
             out.append(SName("mcmc::step_big_reg_kernel", S_BIG, dp, (), "step_big_reg_kernel", ""))
     return out
 
@@ -578,35 +594,68 @@ def scratch_cases_of(n):
     if n.family not in (S_MFMA, S_BIG):
         return [_scratch_case(n, n.D)]
     # (DP = 48: step_mfma_kernel begins where step_pair_kernel's LDS ends, d = 36 at four groups
-    # of 64 walkers per workgroup -- d = 33 with normal priors)
+    # of 64 walkers per workgroup -- d = 41 with normal priors)
     lo, hi = dims_of_dp(n.D)[0], n.D
     ds = [d for d in range(lo, hi + 1) if predict_scratch(_scratch_case(n, d)) == (n.name, n.D)]
     return [_scratch_case(n, d) for d in sorted({ds[0], ds[-1]})]
 
 
 def scratch_blocks(c):
-    if not c.drag:
-        return None
-    cut = max(1, c.d // 2)
-    return ([list(range(cut)), list(range(cut, c.d))], [1, 1], 0, DRAG_STEPS)
-
-
-def scratch_prior(c):
+    """(blocks, oversampling, drag_last_slow, drag_steps) of a case, or None."""
     d = c.d
+    if c.drag:
+        cut = max(1, d // 2)
+        return ([list(range(cut)), list(range(cut, d))], [1, 1], 0, DRAG_STEPS)
+    if c.blocks == "one":     # the last block has one parameter, four times per cycle
+        return ([list(range(d - 1)), [d - 1]], [1, 4], -1, 0)
+    if c.blocks in ("two", "over"):
+        cut = max(1, d // 2)
+        return ([list(range(cut)), list(range(cut, d))], [1, 5 if c.blocks == "over" else 1], -1, 0)
+    return None
+
+
+def scratch_columns(c):
+    """Direction columns per cycle (dragging: of the slow blocks), of the fast blocks: capi.hip, block_slots."""
+    bl = scratch_blocks(c)
+    if bl is None:
+        return c.d, 0
+    blocks, over, last_slow, _ = bl
+    if last_slow >= 0:
+        return sum(len(b) for b in blocks[:last_slow + 1]), sum(len(b) for b in blocks[last_slow + 1:])
+    return sum(o * len(b) for o, b in zip(over, blocks)), 0
+
+
+def scratch_prior(c, means=None, covs=None):
+    """kinds, a, b (and the periodic flags where the case has periodic parameters)."""
+    d = c.d
+    kinds, a, b = [0] * d, [0.0] * d, [1.0] * d
     if c.prior == 2:     # normal priors on the odd parameters (d = 1: a general step for D == 1 alone)
         kinds = [i % 2 for i in range(d)]
-        return kinds, [NORMAL_PRIOR[0] if k else 0.0 for k in kinds], [NORMAL_PRIOR[1] if k else 1.0 for k in kinds]
-    return [0] * d, [0.0] * d, [1.0] * d
+        a = [NORMAL_PRIOR[0] if k else 0.0 for k in kinds]
+        b = [NORMAL_PRIOR[1] if k else 1.0 for k in kinds]
+    if not c.periodic:
+        return kinds, a, b
+    for p in c.periodic:     # intervals about 3 sigma wide around the mode: walkers wrap
+        s = float(np.sqrt(covs[0][p, p]))
+        kinds[p], a[p], b[p] = 0, float(means[0][p]) - 1.5 * s, float(means[0][p]) + 1.5 * s
+    return kinds, a, b, [int(i in c.periodic) for i in range(d)]
 
 
 def scratch_steps(c):
     return (FIRST, c.d + 7)
 
 
+def scratch_cap(c):
+    return sum(scratch_steps(c)) + 8 if c.emit else 0     # (no row is dropped)
+
+
 def scratch_pair_arguments(c):
-    kinds, a, b = scratch_prior(c)
-    kw = dict(K=c.K, kinds=kinds, a=a, b=b, seed=SEED, T=c.T, rng=np.random.default_rng(c.seed),
-              incremental=False, shared_basis=not c.own)
+    from tests.test_gpu_parity import random_target
+    means, covs = random_target(c.d, max(c.K, 1), np.random.default_rng(c.seed))
+    kinds, a, b, *per = scratch_prior(c, means, covs)
+    kw = dict(K=c.K, kinds=kinds, a=a, b=b, periodic=per[0] if per else None, seed=SEED, T=c.T,
+              rng=np.random.default_rng(c.seed), incremental=False, shared_basis=not c.own,
+              burn_in=2 if c.emit else 0, cap=scratch_cap(c))
     if c.K > 1:
         kw["weights"] = [1.0 / 3.0, 2.0 / 3.0]
     bl = scratch_blocks(c)
@@ -615,25 +664,139 @@ def scratch_pair_arguments(c):
     return (c.d, c.W, c.gs), kw
 
 
-def predict_scratch(c):
-    """(name, D) a from-scratch case reports: capi.hip mcmc_hip_step and the launchers, restated."""
-    d, multi, normal = c.d, c.K > 1, c.prior == 2 and c.d > 1
-    unit_t = c.T == 1.0
-    if d <= LANE_MAX:
+def predict_scratch(c, pair_big=True):
+    """(name, D) a from-scratch case reports, or (None, reason) where mcmc_hip_step refuses it: what
+    scratch_choice.h decides, restated on its own.  pair_big: the two-wave kernels of 32 < d <= 56 are there."""
+    d, K, W, gs = c.d, c.K, c.W, c.gs
+    multi, normal, periodic = K > 1, c.prior == 2 and d > 1, bool(c.periodic)
+    unit_t, own, big = c.T == 1.0, c.own and d > 1, d > LANE_MAX
+    blocked = c.blocks is not None or c.drag
+    cols, _ = scratch_columns(c)
+    if c.thin:
+        return None, R_EMIT_THIN
+    if own and blocked:
+        return None, R_OWN_BLOCKS
+    wg = 256 if W % 256 == 0 else 128 if W % 128 == 0 else 64
+    if big:
+        general = (own or blocked or K != 1 or periodic or c.emit
+                   or (W % 256 != 0 and (normal or d > SWEEP_MAX)))
+        if general and 8 * 64 * (2 * d + max(1, K)) > LDS_MAX:
+            return None, R_GENERAL_LDS
         if c.drag:
-            return f"mcmc::drag_kernel<{_b(multi)}>", d
-        if c.own and d > 1:
-            return f"mcmc::step_kernel<{_b(multi)}, true, own basis>", d
-        if pair_fits(d, c.W, c.gs, multi, normal):
+            return GENERAL_DRAG, 0
+        if general:
+            return GENERAL_STEP, 0
+        if pair_big and pair_fits(d, W, gs, multi, normal):
             return f"mcmc::step_pair_kernel<{_b(unit_t)}, {_b(normal)}>", d
-        return f"mcmc::step_kernel<{_b(multi)}, {_b(normal or d == 1)}>", d
-    if c.drag or c.own or multi or (c.W % 256 != 0 and (normal or d > 112)):       # general_big
-        return None
-    if pair_fits(d, c.W, c.gs, multi, normal):
+        if W % 256 == 0:     # (group_size 64, 128 or 256: each divides 256)
+            return f"mcmc::step_mfma_kernel<{_b(normal)}>", dp_of(d)
+        return "mcmc::step_big_reg_kernel", dp_of(d)
+    if c.drag:
+        return f"mcmc::drag_kernel<{_b(multi)}>", d
+    if own:
+        return f"mcmc::step_kernel<{_b(multi)}, true, own basis>", d
+    if 8 * (2 * (wg // gs) * v_slab(cols, d, False) + (K * wg if multi else 0)) > LDS_MAX:
+        return None, R_CYCLE_LDS
+    column_1d = c.blocks == "one"
+    if not (periodic or c.emit or column_1d) and K == 1 and pair_fits(d, W, gs, multi, normal, cols):
         return f"mcmc::step_pair_kernel<{_b(unit_t)}, {_b(normal)}>", d
-    if c.W % 256 == 0 and (256 % c.gs == 0 or c.gs % 256 == 0):
-        return f"mcmc::step_mfma_kernel<{_b(normal)}>", dp_of(d)
-    return "mcmc::step_big_reg_kernel", dp_of(d)
+    general = normal or periodic or K == 0 or c.emit or d == 1 or column_1d
+    return f"mcmc::step_kernel<{_b(multi)}, {_b(general)}>", d
+
+
+def scratch_shape_of(c):
+    """The arguments of cobaya_amd.engine.scratch_choice for a case."""
+    cols, cols_f = scratch_columns(c)
+    return dict(d=c.d, n_modes=c.K, n_walkers=c.W, group_size=c.gs, any_normal=c.prior == 2 and c.d > 1,
+                any_periodic=bool(c.periodic), emit=c.emit, emit_thin=c.thin, unit_t=c.T == 1.0, own_basis=c.own,
+                blocked=c.blocks is not None or c.drag, n_drag=DRAG_STEPS if c.drag else 0, cps=cols, cps_f=cols_f,
+                has_1d_column=c.blocks == "one")
+
+
+def scratch_name_of(ch):
+    """(name, unit) the launcher reports for an answer of cobaya_amd.engine.scratch_choice -- the
+    note_step_kernel strings of the launchers -- or (None, reason)."""
+    from cobaya_amd import engine as E
+    multi, general, unit_t, normp = (_b(ch[k]) for k in ("multi", "general", "unit_t", "normp"))
+    name = {E.SCRATCH_NOT_SERVED: None,
+            E.SCRATCH_STEP: f"mcmc::step_kernel<{multi}, {general}>",
+            E.SCRATCH_STEP_OWN: f"mcmc::step_kernel<{multi}, true, own basis>",
+            E.SCRATCH_PAIR: f"mcmc::step_pair_kernel<{unit_t}, {normp}>",
+            E.SCRATCH_MFMA: f"mcmc::step_mfma_kernel<{normp}>",
+            E.SCRATCH_BIG_REG: "mcmc::step_big_reg_kernel",
+            E.SCRATCH_GENERAL: GENERAL_STEP,
+            E.SCRATCH_DRAG: f"mcmc::drag_kernel<{multi}>",
+            E.SCRATCH_GENERAL_DRAG: GENERAL_DRAG}[ch["family"]]
+    return (name, ch["unit"]) if name else (None, ch["reason"])
+
+
+def general_cases():
+    """step_general_kernel and drag_general_kernel have a run-time d and one symbol each: no unit per
+    D.  One case per reason scratch_choose sends a shape to them, at the smallest and the largest d:
+    two modes, `one`, a periodic parameter, emitted rows, own bases; an ensemble of 64 walkers with
+    normal priors; d = 113 (above the column sweep) with 320 walkers; dragging."""
+    def case(name, d, W=64, **kw):
+        return SCase(name, "scratch_general", 0, d, W, 64, kw.pop("K", 1), kw.pop("prior", 0), 1.0,
+                     kw.pop("own", False), kw.pop("drag", False), 300 + d, **kw)
+    out = []
+    for d in (33, 128):
+        out += [case(GENERAL_STEP, d, K=2), case(GENERAL_STEP, d, K=0), case(GENERAL_STEP, d, periodic=(0,)),
+                case(GENERAL_STEP, d, emit=True), case(GENERAL_STEP, d, own=True)]
+    out += [case(GENERAL_STEP, 33, prior=2), case(GENERAL_STEP, 113, W=320), case(GENERAL_DRAG, 33, drag=True)]
+    return out
+
+
+# The grid the rule is held against: every d, ensembles on both sides of every workgroup width (and
+# 65 792 = 257 workgroups of 256: two per compute unit for the placement request), every group size
+# that divides them, `one` / one mode / two, every prior and option, every kind of blocking
+GRID_W = (64, 128, 192, 256, 320, 512, 65536, 65792)
+GRID_VARIANTS = (None, "drag", "two", "one", "over", "thin")
+
+
+def scratch_grid():
+    for d in range(1, 129):
+        for W in GRID_W:
+            for gs in (64, 128, 256):
+                if W % gs:
+                    continue
+                for K in (0, 1, 2):
+                    for normal in (False, True):
+                        for per in (False, True):
+                            for emit in (False, True):
+                                for own in (False, True):
+                                    for var in GRID_VARIANTS:
+                                        if d == 1 and var not in (None, "thin"):
+                                            continue      # (blocks and dragging need two parameters)
+                                        for T in (1.0, 2.0):
+                                            yield SCase("", "", 0, d, W, gs, K, 2 if normal else 0, T, own,
+                                                        var == "drag", 0, (0,) if per else (), emit,
+                                                        var if var in ("two", "one", "over") else None, var == "thin")
+
+
+_CENSUS = []
+
+
+def scratch_grid_census():
+    """One pass over the grid, shared by the host tests: {(name, unit) or (None, reason): shapes} as
+    mcmc_hip_scratch_choice answers, the number of shapes, and the first shapes where predict_scratch
+    answers otherwise."""
+    if not _CENSUS:
+        import ctypes
+        from cobaya_amd import engine as E
+        lib, shape, out = E.load_library(), E.ScratchShape(), E.ScratchChoice()
+        fields = [f for f, _ in E.ScratchChoice._fields_]
+        seen, wrong, n = {}, [], 0
+        for c in scratch_grid():
+            for k, v in scratch_shape_of(c).items():
+                setattr(shape, k, int(v))
+            assert lib.mcmc_hip_scratch_choice(ctypes.byref(shape), ctypes.byref(out)) == 0
+            got = scratch_name_of({f: getattr(out, f) for f in fields})
+            seen[got] = seen.get(got, 0) + 1
+            n += 1
+            if got != predict_scratch(c) and len(wrong) < 5:
+                wrong.append((c, got, predict_scratch(c)))
+        _CENSUS.append((seen, n, wrong))
+    return _CENSUS[0]
 
 
 def scratch_oracle_alone(c):
@@ -641,16 +804,18 @@ def scratch_oracle_alone(c):
     from oracle import cbind as O
     from tests.test_gpu_parity import random_target, start_points
     rng = np.random.default_rng(c.seed)
-    means, covs = random_target(c.d, c.K, rng)
-    kinds, a, b = scratch_prior(c)
-    x0 = start_points(rng, c.d, c.W, means, covs, kinds, a, b, None)
-    pcov = covs[0] * c.T
+    means, covs = random_target(c.d, c.K, rng) if c.K else (None, None)
+    kinds, a, b, *per = scratch_prior(c, means, covs)
+    periodic = per[0] if per else None
+    x0 = start_points(rng, c.d, c.W, means, covs, kinds, a, b, periodic)
+    pcov = (covs[0] if c.K else np.diag(np.full(c.d, 0.01))) * c.T
     kw, bl = {}, scratch_blocks(c)
     if bl is not None:
         kw = dict(blocks=bl[0], oversampling=bl[1], drag_last_slow=bl[2], drag_steps=bl[3])
         T = O.blocked_transform(pcov, bl[0], 2.4)
     else:
         T = O.proposal_transform(pcov, 2.4)
-    prob = O.Problem(c.d, kinds, a, b, means=means, covs=covs, weights=[1.0 / 3.0, 2.0 / 3.0] if c.K > 1 else None,
+    prob = O.Problem(c.d, kinds, a, b, periodic=periodic, means=means, covs=covs,
+                     weights=[1.0 / 3.0, 2.0 / 3.0] if c.K > 1 else None,
                      T=T, group_size=1 if (c.own and c.d > 1) else c.gs, seed=SEED, temperature=c.T, **kw)
-    return prob, O.State(prob, x0)
+    return prob, O.State(prob, x0, burn_in=2 if c.emit else 0, row_cap=scratch_cap(c))

@@ -915,6 +915,116 @@ def test_inc_choice_header_is_plain_cxx(tmp_path):
                     "-I", os.path.join(ROOT, "cobaya_amd", "csrc"), str(src)], check=True)
 
 
+def test_scratch_choice_is_the_rule_the_instantiation_tables_restate():
+    """mcmc_hip_scratch_choice (csrc/scratch_choice.h, no device) against predict_scratch of
+    tests/instantiations.py -- the restatement the device sweep has verified, name by name -- over
+    every d in 1..128, eight ensemble sizes, every group size that divides them, `one` / one / two
+    modes, normal priors, a periodic parameter, emitted rows (thinned too), own bases, dragging,
+    blocks with and without a one-parameter column or oversampling, T in {1, 2}.  The grid is not
+    vacuous: every family and every refusal an engine can meet occur on it.  The refusals no engine
+    can meet (more than kMaxModes modes; a group size mcmc_hip_create does not admit) are shown
+    alive off the grid."""
+    from tests import instantiations as I
+    seen, n, wrong = I.scratch_grid_census()
+    assert not wrong, wrong
+    assert n == (127 * 6 + 2) * 17 * 3 * 16 * 2 and sum(seen.values()) == n      # (d = 1: no blocks, no dragging)
+    names = {name for name, _ in seen if name}
+    for stem in ("step_kernel<false, false>", "step_kernel<true, true>", "step_kernel<false, true, own basis>",
+                 "step_pair_kernel<true, false>", "step_pair_kernel<false, true>", "step_mfma_kernel<true>",
+                 "step_big_reg_kernel", "step_general_kernel", "drag_kernel<true>", "drag_general_kernel"):
+        assert "mcmc::" + stem in names, stem
+    reasons = {r for name, r in seen if name is None}
+    assert reasons == {I.R_EMIT_THIN, I.R_OWN_BLOCKS, I.R_CYCLE_LDS}
+    assert min(seen[(None, r)] for r in reasons) > 100
+    ch = E.scratch_choice
+    assert ch(129)["reason"] == ch(30, n_walkers=100)["reason"] == ch(30, group_size=100)["reason"] == I.R_BAD_SHAPE
+    # the general d > 32 kernels hold 2 d + K doubles of 64 walkers: 64 modes (kMaxModes) fit at d = 128
+    assert ch(128, 64)["family"] == E.SCRATCH_GENERAL and ch(128, 64)["lds_bytes"] == 160 * 1024
+    assert ch(128, 65)["reason"] == I.R_GENERAL_LDS
+    # groups of 192 walkers (no engine has them) are neither a part nor a multiple of the matrix-core
+    # kernel's 256-walker workgroup: the column sweep, which is not compiled above DP = 112 and
+    # serves uniform priors only -- the launchers' two own refusals
+    assert ch(100, n_walkers=768, group_size=192)["family"] == E.SCRATCH_BIG_REG
+    assert ch(120, n_walkers=768, group_size=192)["reason"] == I.R_SWEEP_SIZE
+    assert ch(100, n_walkers=768, group_size=192, any_normal=True)["reason"] == I.R_SWEEP_NORMAL
+
+
+def test_the_thresholds_of_the_from_scratch_kernels_without_a_gpu():
+    """What the GPU tests pin through last_step_kernel(), asked of the rule itself
+    (mcmc_hip_scratch_choice; scratch_choice.h), and the launch geometry of the shapes the
+    benchmark runs, worked out by hand from the launchers as they were before the rule moved."""
+    ch = E.scratch_choice
+    fam = lambda *a, **k: ch(*a, **k)["family"]
+    one, four = dict(n_walkers=256, group_size=256), dict(n_walkers=256, group_size=64)
+    # the two-wave kernel from d = 14 (MCMC_PAIR_MIN) ...
+    assert fam(13, **four) == E.SCRATCH_STEP and fam(14, **four) == E.SCRATCH_PAIR
+    # ... up to d = 56 with uniform priors and d = 54 with normal ones, one group per workgroup
+    assert fam(56, **one) == E.SCRATCH_PAIR and fam(57, **one) == E.SCRATCH_MFMA
+    assert fam(54, any_normal=True, **one) == E.SCRATCH_PAIR and fam(55, any_normal=True, **one) == E.SCRATCH_MFMA
+    # four groups per workgroup: its LDS ends at d = 36 -- the later split of d = 37 and 38 (pair_split)
+    # exchanges less and fits once more -- and with normal priors, whose split is one row block later, at
+    # d = 41; matrix cores from there on
+    assert [d for d in range(33, 57) if fam(d, **four) == E.SCRATCH_PAIR] == [33, 34, 35, 37, 38]
+    assert [d for d in range(33, 57) if fam(d, any_normal=True, **four) == E.SCRATCH_PAIR] == list(range(33, 41))
+    assert fam(36, **four) == fam(39, **four) == fam(41, any_normal=True, **four) == E.SCRATCH_MFMA
+    assert ch(36, **four)["unit"] == 48 and ch(100, **four)["unit"] == 100 and ch(101, **four)["unit"] == 112
+    # not with a mixture, `one`, a periodic parameter, emitted rows, a one-parameter column, own bases
+    for other in (dict(n_modes=2), dict(n_modes=0), dict(any_periodic=True), dict(emit=True),
+                  dict(blocked=True, cps=33, has_1d_column=True)):
+        assert fam(30, **other, **four) == E.SCRATCH_STEP, other
+    assert fam(30, blocked=True, cps=33, **four) == E.SCRATCH_PAIR
+    assert fam(30, own_basis=True, **four) == E.SCRATCH_STEP_OWN
+    # the column sweep only for ensembles of no whole 256 walkers, uniform priors and d <= 112
+    odd = dict(n_walkers=320, group_size=64)
+    assert fam(33, **odd) == fam(112, **odd) == E.SCRATCH_BIG_REG and fam(112, n_walkers=512, group_size=64) == E.SCRATCH_MFMA
+    assert fam(113, **odd) == fam(100, any_normal=True, **odd) == E.SCRATCH_GENERAL
+    # step_general_kernel otherwise, drag_general_kernel with dragging
+    for other in (dict(n_modes=2), dict(n_modes=0), dict(any_periodic=True), dict(emit=True), dict(own_basis=True),
+                  dict(blocked=True, cps=40)):
+        assert fam(33, **other, **one) == fam(128, **other, **one) == E.SCRATCH_GENERAL, other
+    assert fam(64, any_normal=True, n_walkers=64, group_size=64) == E.SCRATCH_GENERAL
+    assert fam(33, blocked=True, n_drag=2, cps=16, cps_f=17, **one) == E.SCRATCH_GENERAL_DRAG
+    assert fam(30, blocked=True, n_drag=2, cps=15, cps_f=15, **one) == E.SCRATCH_DRAG
+    # the directions: column stride d and whole-KiB slabs at d <= 32 and with blocks, padded columns above
+    assert (ch(30)["v_ld"], ch(30)["slab"]) == (30, 8 * 128) and (ch(33)["v_ld"], ch(33)["slab"]) == (34, 10 * 128)
+    assert (ch(33, blocked=True, cps=40)["v_ld"], ch(33, blocked=True, cps=40)["slab"]) == (33, 11 * 128)
+    # geometry.  The headline shape (d = 30, 65 536 walkers in groups of 256): 256 workgroups of 512
+    # threads, one per compute unit, so each asks for 96 KiB -- more than half of the LDS
+    c = ch(30)
+    assert (c["family"], c["grid"], c["threads"], c["lds_bytes"], c["lds_attr"]) == (E.SCRATCH_PAIR, 256, 512, 96 << 10, 96 << 10)
+    # 257 workgroups: two per compute unit, 80 KiB each; at d = 100 the same count of matrix-core
+    # workgroups (1024 threads) asks for 160 KiB - 2 KiB
+    c = ch(14, n_walkers=65792)
+    assert (c["grid"], c["threads"], c["lds_bytes"]) == (257, 512, 80 << 10)
+    c = ch(100, n_walkers=65792)
+    assert (c["family"], c["grid"], c["threads"], c["lds_bytes"], c["lds_attr"]) == (E.SCRATCH_MFMA, 257, 1024, 158 << 10, 158 << 10)
+    # step_kernel at d = 8: 256 workgroups of 256 threads ask for 64 KiB and need no attribute;
+    # two slabs of 8 x 8 doubles (1 KiB) per group and the log-densities of two modes where nothing is asked for
+    c = ch(8)
+    assert (c["family"], c["grid"], c["threads"], c["lds_bytes"], c["lds_attr"]) == (E.SCRATCH_STEP, 256, 256, 64 << 10, 0)
+    c = ch(8, n_modes=2, n_walkers=1 << 20, group_size=64)
+    assert (c["grid"], c["lds_bytes"]) == (4096, max((160 << 10) // 16, 8 * (2 * 4 * 128 + 2 * 256)))
+    # the column sweep: DP x DP of L^-1, four rows of DP and two 1 KiB pieces of directions per group
+    c = ch(100, **odd)
+    assert (c["grid"], c["threads"], c["lds_bytes"]) == (5, 64, 8 * (100 * 100 + 4 * 100 + 2 * 128))
+    # the general kernels: 64 walkers per workgroup, x and the trial of each and one log-density per mode
+    c = ch(128, n_modes=2, **one)
+    assert (c["grid"], c["threads"], c["lds_bytes"], c["lds_attr"]) == (4, 64, 8 * 64 * 258, 8 * 64 * 258)
+    assert ch(33, n_modes=2, **one)["lds_attr"] == 0
+    # dragging at d <= 32: workgroups of 256 or 64 walkers, never 128
+    assert ch(30, blocked=True, n_drag=2, cps=15, cps_f=15, n_walkers=384, group_size=128)["threads"] == 64
+
+
+def test_scratch_choice_header_is_plain_cxx(tmp_path):
+    """csrc/scratch_choice.h holds the rule and nothing of HIP: it compiles with the host compiler alone."""
+    src = tmp_path / "choice.cpp"
+    src.write_text('#include "scratch_choice.h"\n'
+                   'static_assert(mcmc::pair_split(30, false) == 20 && mcmc::pair_xf(30, false) == 13, "");\n'
+                   'int main() { return mcmc::scratch_choose(mcmc::ScratchShape{}).family; }\n')
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only",
+                    "-I", os.path.join(ROOT, "cobaya_amd", "csrc"), str(src)], check=True)
+
+
 def test_window_sums_are_a_fixed_function_of_the_intervals_and_cost_log_n():
     """Round 4: the host-path checkpoint sums the window (the later half of the run) in
     O(log n) array additions -- `WindowSums`: aligned dyadic blocks over the run's interval

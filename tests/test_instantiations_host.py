@@ -346,14 +346,14 @@ def test_the_from_scratch_tables_and_their_cases():
     two-wave kernels, 11 x 2 + 9 of walker_kernels_big.hip; the cases cover exactly the reachable."""
     assert len({(n.name, n.D) for n in SNAMES}) == len(SNAMES) == 32 * 8 + 56 * 4 + 11 * 2 + 9
     assert len(SNAMES) - len(SREACHABLE) == 6 + 13 * 4 + 2 * 2
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # unreachable is proved by exhaustion: over the grid of tests/instantiations.py (every d, so every
+    # shape of a unit's D or DP) mcmc_hip_scratch_choice never answers a unit marked unreachable, and
+    # answers every other one at least once
+    seen, _, _ = I.scratch_grid_census()
     for n in SNAMES:
-        if n.why:
-            m = re.match(r"(\S+):(\d+) (\w+)", n.why)
-            with open(os.path.join(root, m.group(1))) as f:
-                lines = f.read().splitlines()
-            at = int(m.group(2))
-            assert any(w in lines[at - 1] for w in ("D == 1", "launch_drag", "kPair", "D >= 55", "cfg->d > 1")), n.why
+        assert ((n.name, n.D) in seen) == (not n.why), (n.name, n.D, n.why)
+        assert not n.why or n.why.startswith(I.SCRATCH_CHOICE + " "), n.why
+    assert {u for u in seen if u[0] and "general" not in u[0]} == {(n.name, n.D) for n in SREACHABLE}
     got = set()
     for n in SREACHABLE:
         for c in I.scratch_cases_of(n):
@@ -394,3 +394,25 @@ def test_every_from_scratch_case_makes_a_wrong_kernel_visible(family, D):
             if not 0.05 <= rate <= 0.95:
                 failed.append(f"{c.name} d={c.d}: acceptance {rate:.3f}")
     assert not failed, "\n".join(failed)
+
+
+def test_the_general_kernel_cases_reach_them_and_make_a_wrong_kernel_visible():
+    """tests/instantiations.py: general_cases (run by tests/test_gpu_scratch_general.py): the rule and its
+    restatement send each to step_general_kernel / drag_general_kernel; on the oracle alone each
+    launch accepts and rejects, acceptance within [0.05, 0.95]; the emitting ones emit."""
+    from cobaya_amd import engine as E
+    cases = I.general_cases()
+    assert len(cases) == 13 and {c.d for c in cases} == {33, 113, 128}
+    for c in cases:
+        assert I.predict_scratch(c) == (c.name, 0) == I.scratch_name_of(E.scratch_choice(**I.scratch_shape_of(c))), c
+        prob, st = I.scratch_oracle_alone(c)
+        total = 0
+        for steps in I.scratch_steps(c):
+            before = int(st.n_accept.sum())
+            st.run(steps, n_threads=4)
+            got = int(st.n_accept.sum()) - before
+            total += got
+            assert 0 < got < c.W * steps, c
+        assert 0.05 <= total / (c.W * sum(I.scratch_steps(c))) <= 0.95, c
+        if c.emit:
+            assert len(st.drain()) > c.W

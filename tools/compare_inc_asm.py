@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Do two source trees compile the incremental step kernels to the same machine code?
+"""Do two source trees compile the step kernels to the same machine code?
 
-    git worktree add /tmp/parent HEAD~1
-    python tools/compare_inc_asm.py /tmp/parent . [--jobs 8] > profiles/<name>.txt
+    git worktree add ../parent HEAD~1
+    python tools/compare_inc_asm.py ../parent . [--jobs 8] [--units PREFIX ...] > profiles/<name>.txt
 
-Compiles every incremental translation unit that cobaya_amd/build.py lists (incremental_<lo>, incremental_emit_<lo>,
-incremental_any_<part>, incremental_duo_<lo>) from both trees to assembly (tools/hip_asm.py) and compares, kernel by
-kernel, the instruction text: labels, instructions and the `.amdhsa_*` kernel descriptor; comments, blank lines and
+Compiles every translation unit that cobaya_amd/build.py lists and whose name begins with one of the prefixes
+(default `incremental_`: incremental_<lo>, incremental_emit_<lo>, incremental_any_<part>, incremental_duo_<lo>; the
+from-scratch kernels: `--units walker_d walker_big general blocked`) from both trees to assembly (tools/hip_asm.py) and
+compares, kernel by kernel, the instruction text: labels, instructions and the `.amdhsa_*` kernel descriptor; comments, blank lines and
 `.loc` / `.file` / `.ident` directives are dropped.  Prints the number of identical kernels per unit and, for every
 kernel that differs, VGPRs and scratch bytes on both sides and the first differing lines.  Exit code 1 if any differs."""
 import argparse
@@ -19,7 +20,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from hip_asm import compile_to_asm, split_kernels  # noqa: E402
-from cobaya_amd.build import translation_units  # noqa: E402
+from cobaya_amd.build import ALL_DIMS, translation_units  # noqa: E402
 
 
 def instruction_text(lines):
@@ -54,9 +55,11 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--lines", type=int, default=12, help="differing lines shown per kernel")
+    ap.add_argument("--units", nargs="+", default=["incremental_"], metavar="PREFIX",
+                    help="compare the translation units whose names begin with one of these")
     args = ap.parse_args()
-    units = [(src, name, defines) for src, name, defines in translation_units([], big=False)
-             if name.startswith("incremental_")]
+    units = [(src, name, defines) for src, name, defines in translation_units(ALL_DIMS, big=True)
+             if name.startswith(tuple(args.units))]
     tasks = [(os.path.abspath(root), src, defines) for root in (args.old, args.new) for src, _, defines in units]
     with ThreadPoolExecutor(max(1, min(args.jobs, 16))) as ex:
         sides = list(ex.map(lambda t: kernels_of(*t), tasks))
