@@ -10,22 +10,26 @@ pytestmark = pytest.mark.gpu
 from cobaya_amd import engine as E  # noqa: E402
 from cobaya_amd import pliklite as P  # noqa: E402
 from oracle import cbind as O  # noqa: E402
+from tests.binned_cases import permuted_problem  # noqa: E402
 from tests.pliklite_common import load_g13, sampling_problem, small_dataset  # noqa: E402
 from tests.test_gpu_parity import assert_bit_equal, compare_state  # noqa: E402
 
 RTOL = 1e-12   # the tolerance of the verdict's G13 bar (summation orders differ from numpy's BLAS)
 
 
-def make(target, emu, W=64, gs=64, seed=5, T=1.0, max_tries=None):
+def make(target, emu, W=64, gs=64, seed=5, T=1.0, max_tries=None, calib=None):
+    """Engine and oracle problem of one target; `calib`: position of the calibration parameter
+    among the sampled ones (default: last)."""
     d = emu.n + 1
-    kinds, a, b, C = sampling_problem(target, emu)
+    calib = emu.n if calib is None else calib
+    kinds, a, b, C = permuted_problem(target, emu, calib)     # (calib = emu.n: sampling_problem's own)
     eng = E.Engine(d, W, group_size=gs, seed=seed, temperature=T, max_tries=max_tries)
     eng.set_prior(kinds, a, b)
-    eng.set_target_binned_gaussian(target, emu, calib_index=emu.n)
+    eng.set_target_binned_gaussian(target, emu, calib_index=calib)
     eng.set_proposal_cov(C * T)
     k = eng.binned_constants()
     B = O.Binned(target.bin_table(), target.weights, target.X_data, Linv=k["Linv"],
-                 theta0=emu.theta0, D0=emu.D0, J=emu.J, calib=emu.n)
+                 theta0=emu.theta0, D0=emu.D0, J=emu.J, calib=calib)
     # the library's binned response is the oracle's, bit for bit (host fma chains both)
     assert_bit_equal(k["Bc0"], B.Bc0, "Bc0")
     assert_bit_equal(k["BJ"], B.BJ, "BJ")
