@@ -496,6 +496,121 @@ struct PairRng {
     }
 };
 
+// The four lazy variates of TWO consecutive Philox blocks (the step pairs `pair` and `pair + 1`: what one lane half
+// of step_inc_duo_kernel draws per octet) as ONE straight-line burst: variate v = 2 q + (step & 1) of pair + q holds,
+// operation for operation and in each variate's own order, what PairRng::draw<true> computes -- only the order ACROSS
+// the variates differs.  Drawn one after the other a variate is a chain of dependent latencies (ten Philox rounds, an
+// LDS round trip for the table, six Horner steps, v_rsq_f64 and nine more dependent operations) with next to nothing
+// to issue beside it; here the two blocks run round by round side by side, the four table reads are issued back to
+// back with the single-precision accept estimates underneath their return, and the four logarithms and the four
+// square roots advance level by level.  The stages are pinned by scheduling barriers, as the step's ladder is
+// (tools/check_burst.py reads the result off the assembly; measured: profiles/r25_burst_chains.txt).  The lowest bin of
+// a radial uniform (kr == 0, 2^-24 per variate) is NOT redrawn here: `low` names its lanes, and the caller redraws
+// behind its stores (a wave-uniform, rare branch).  An accept uniform in its lowest bin keeps its NaN estimate.
+struct OctetRng {
+    double r[4], Ea[4];
+    unsigned long long low;   // the lanes with a radial uniform in its lowest bin: their r waits for pair_tail
+    __device__ __forceinline__ void draw_lazy(uint32_t key0, uint32_t key1, uint32_t gid, unsigned long long pair,
+                                              short_log_tab tab)
+    {
+        constexpr double LN2 = 6.93147180559945286227e-01, C2 = -0.5, C3 = 3.33333333333333314830e-01,
+                         C4 = -0.25, C5 = 2.00000000000000011102e-01, C6 = -1.66666666666666657415e-01;
+        StepRng g[2];
+        g[0].begin(key0, key1, gid, pair);
+        g[0].c1 = kStreamStep | 0x4000u;
+        g[1] = g[0];   // (one set of round keys for both blocks)
+        g[1].c2 = (uint32_t)(pair + 1ull);
+        g[1].c3 = (uint32_t)((pair + 1ull) >> 32);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 10; ++k) {
+            g[0].round();
+            g[1].round();
+        }
+        uint32_t a[4], kr[4], ka[4], j[4];
+        double m[4], be[4];
+        dpair_t t[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const StepRng& q = g[v >> 1];
+            const uint32_t b = (v & 1) ? q.c3 : q.c1;
+            a[v] = (v & 1) ? q.c2 : q.c0;
+            kr[v] = ((a[v] & 0xFFFFFu) << 4) | (b >> 28);
+            ka[v] = b & 0x0FFFFFFFu;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // the integer front of the four logarithms, and their table reads in one run
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const double xd = (double)(2u * kr[v] + 1u);
+            m[v] = __builtin_amdgcn_frexp_mant(xd);
+            be[v] = (double)(25 - __builtin_amdgcn_frexp_exp(xd));
+            // (the read's address is formed here, through an empty asm: the four reads then stand in one run)
+            j[v] = (unsigned)(unsigned long long)(tab + (((unsigned)__double2hiint(m[v]) >> 13) & 0x7Fu));
+            asm volatile("" : "+v"(j[v]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) t[v] = *(short_log_tab)(unsigned long long)j[v];
+        __builtin_amdgcn_sched_barrier(0);
+        // underneath their return: the accept estimates
+#pragma unroll
+        for (int v = 0; v < 4; ++v) Ea[v] = accept_pack(ka[v]);
+        low = lanes((kr[0] == 0u) | (kr[1] == 0u) | (kr[2] == 0u) | (kr[3] == 0u));
+        __builtin_amdgcn_sched_barrier(0);
+        // neg_log_short(2 kr + 1, 25), level by level (each read retired by its own count)
+        double f[4], p[4], Er[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) f[v] = fma(m[v], t[v].x, -1.0);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) p[v] = fma(f[v], C6, C5);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) p[v] = fma(f[v], p[v], C4);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) p[v] = fma(f[v], p[v], C3);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) p[v] = fma(f[v], p[v], C2);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) p[v] = fma(f[v], p[v], 1.0);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) Er[v] = fma(be[v], LN2, t[v].y) - f[v] * p[v];
+        __builtin_amdgcn_sched_barrier(0);
+        // sqrt_midrange(2 Er), level by level: the four v_rsq_f64 first
+        double a2[4], y[4], gg[4], hh[4], rr[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) a2[v] = 2.0 * Er[v];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) y[v] = __builtin_amdgcn_rsq(a2[v]);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            gg[v] = a2[v] * y[v];
+            hh[v] = 0.5 * y[v];
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v) rr[v] = fma(-hh[v], gg[v], 0.5);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            gg[v] = fma(gg[v], rr[v], gg[v]);
+            hh[v] = fma(hh[v], rr[v], hh[v]);
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v) rr[v] = fma(-gg[v], gg[v], a2[v]);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) gg[v] = fma(rr[v], hh[v], gg[v]);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) rr[v] = fma(-gg[v], gg[v], a2[v]);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) gg[v] = fma(rr[v], hh[v], gg[v]);
+        __builtin_amdgcn_sched_barrier(0);
+        // the exponential branch and the sign (bit 31 of a set = positive)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const double s = sel(lanes(((a[v] >> 20) & 0x7FFu) < 676u), Er[v], gg[v]);
+            r[v] = __longlong_as_double(__double_as_longlong(s) ^ ((long long)(~a[v] & 0x80000000u) << 32));
+        }
+    }
+};
+
 // a / w given R = RN(1 / w): the correctly rounded quotient without a division: q0 = a R,
 // q1 = fma(fma(-q0, w, a), R, q0), q2 = fma(fma(-q1, w, a), R, q1) (q1 is faithful -- its exact
 // argument is within 2^-52 ulp of a / w -- and a faithful quotient corrected once with the

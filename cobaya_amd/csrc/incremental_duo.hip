@@ -79,6 +79,17 @@
 #ifndef MCMC_DUO1_LADDER
 #define MCMC_DUO1_LADDER 4   // (pairs per counted LDS wait of the one-mode step, >= 1: see its step loop)
 #endif
+// the variate burst of step_inc_duo_kernel: one straight-line burst of interleaved chains per octet (1: det_math.h
+// OctetRng) or a rolled loop over the lane half's two Philox blocks (0: PairRng, what step_duo_mix_kernel keeps)
+// (measured: profiles/r25_burst_chains.txt)
+#ifndef MCMC_DUO1_BURST_CHAINS
+#define MCMC_DUO1_BURST_CHAINS 1
+#endif
+// measurement hook: every octet's variates are drawn this many times into the same LDS slots (the outputs do not
+// change); the difference between 2 and 1 is what one burst costs.  The shipped build draws once
+#ifndef MCMC_DUO1_BURST_REPEAT
+#define MCMC_DUO1_BURST_REPEAT 1
+#endif
 
 namespace mcmc {
 namespace {
@@ -126,6 +137,13 @@ struct DuoVariates {
         pair_t* const mine = sRE + ((wave * 8 + 4 * h + 2 * q) * kDuoRow + (lane >> 1));
         mine[0] = pair_t{p.r[0], p.Ea[0]};
         mine[kDuoRow] = pair_t{p.r[1], p.Ea[1]};
+    }
+    // ... and the four of an octet's lane half at once (the same slots)
+    __device__ __forceinline__ void put(pair_t* sRE, int wave, int lane, int h, const OctetRng& p)
+    {
+        pair_t* const mine = sRE + ((wave * 8 + 4 * h) * kDuoRow + (lane >> 1));
+#pragma unroll
+        for (int v = 0; v < 4; ++v) mine[v * kDuoRow] = pair_t{p.r[v], p.Ea[v]};
     }
     __device__ __forceinline__ void seek(unsigned long long S) { off = base + (unsigned)(S & 7ull) * (16u * kDuoRow); }
     __device__ __forceinline__ void fetch(double& r, double& Ea) const
@@ -731,12 +749,33 @@ __global__ void __launch_bounds__(256, 2) step_inc_duo_kernel(const IncStepArgs 
             const unsigned long long S0 = s.step0 + (unsigned long long)(base + sl0);
             if ((S0 >> 3) != cur_oct) {   // (not the octet the chunk before ended in)
                 cur_oct = S0 >> 3;
+                // (the turn from the shader clock: taken from the octet index instead -- a turn every 16 octets, no
+                // s_memtime and no wait for it -- the kernel ran 5.5 % slower, profiles/r25_burst_chains.txt)
                 rotate_priority<2>(hw_slot);
+                // the lane half's two Philox blocks one after the other (rolled: one block's registers at a time)
+                auto rolled = [&](uint32_t id) {
 #pragma unroll 1
-                for (int q = 0; q < 2; ++q) {   // (rolled: one Philox block's registers at a time)
-                    PairRng pr;
-                    pr.run_lazy(s.key0, s.key1, gid, (cur_oct << 2) + (unsigned long long)(2 * h + q), slog);
-                    sv.put(sRE, wave, lane, h, q, pr);
+                    for (int q = 0; q < 2; ++q) {
+                        PairRng pr;
+                        pr.run_lazy(s.key0, s.key1, id, (cur_oct << 2) + (unsigned long long)(2 * h + q), slog);
+                        sv.put(sRE, wave, lane, h, q, pr);
+                    }
+                };
+#pragma unroll
+                for (int rep = 0; rep < MCMC_DUO1_BURST_REPEAT; ++rep) {
+                    uint32_t id = gid;
+                    if constexpr (MCMC_DUO1_BURST_REPEAT > 1) asm volatile("; burst again" : "+v"(id));
+                    if constexpr (MCMC_DUO1_BURST_CHAINS != 0) {
+                        // one straight-line burst (det_math.h: OctetRng) in the registers of the step's (v, u) pairs,
+                        // which are dead here.  A radial uniform in its lowest bin: the rolled loop, behind the
+                        // stores, draws the lane half's four variates again with the redrawn tail, over the same slots
+                        OctetRng o;
+                        o.draw_lazy(s.key0, s.key1, id, (cur_oct << 2) + (unsigned long long)(2 * h), slog);
+                        sv.put(sRE, wave, lane, h, o);
+                        if (__builtin_expect(o.low != 0ull, 0)) rolled(id);   // (wave-uniform, rare)
+                    } else {
+                        rolled(id);
+                    }
                 }
             }
             sv.seek(S0);
